@@ -6,6 +6,8 @@ Whisper-base + LLaMA-7B in bf16 on synthetic data — BASELINE cfg 3 at 32 sampl
 
     python bench.py --gpus 1 --steps 5 --warmup 2                 # cfg 3 = the metric's config
     python bench.py --config 2|4|5 ...                            # the other BASELINE.json configs
+    python bench.py --full ...                                    # + roofline, comm, cpu_baseline
+    python bench.py --dump-outputs DIR ...                        # + what the last timed step computed
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,13 +16,23 @@ Whisper-base + LLaMA-7B in bf16 on synthetic data — BASELINE cfg 3 at 32 sampl
 fp8 (e4m3) MFMA forward of the q|k|v and alignment K/V GEMMs, 32 per GPU, activation
 checkpointing on (one GPU holds the whole 13B training state: peak memory is printed).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps (all of
+them alike, uninstrumented) and prints the headline figures (metric, value, unit, ms_per_step,
+dtype, config).  --full adds what takes work of its own:
   roofline     : dominant kernel = the bf16 MFMA GEMM (csrc/gemm.hip); achieved = algorithmic
                  GEMM FLOPs (2*M*N*K per launch) / kernel time measured live with HIP events
-                 on the launch stream during the LAST timed step; peak = 2.5 PFLOP/s dense bf16.
+                 on the launch stream during the LAST timed step, which then runs serially and
+                 instrumented; peak = 2.5 PFLOP/s dense bf16.
+  comm         : the communication profile of the last timed step (BucketedStep.comm_report()).
   cpu_baseline : the CPU oracle (oracle/restate.py, a port of the reference's algorithm; the
-                 reference itself is not present on the GPU box) timed on this box's host cores,
+                 reference itself is not part of this repository) timed on the host cores,
                  composed from real-dimension components on a bounded sample (see `sample`).
+
+--dump-outputs DIR: after the timed steps, writes what the last timed step computed, as a caller
+of the training step receives it: DIR/loss.npy (float64, [1]) and DIR/params_sample.npy (float32,
+a fixed seeded sample of every trainable parameter after the step's AdamW update, at most 4096
+elements per tensor, in named_parameters() order).  Model and inputs are seeded, so two runs with
+the same arguments start from identical inputs.
 """
 from __future__ import annotations
 
@@ -248,6 +260,35 @@ def host_cores() -> int:
     return max(1, min(n, int(os.environ.get("MACAW_CPU_THREADS", "64"))))
 
 
+DUMP_PER_TENSOR = 4096      # sampled elements per trainable parameter in params_sample.npy
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: str, loss, model) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, as .npy files under `out_dir` -- the loss
+    (float64) and the parameters after the step's AdamW update, as a fixed seeded sample (the whole 7B state does not
+    fit the 64 MB budget): per trainable parameter, in named_parameters() order, DUMP_PER_TENSOR indices drawn by a
+    CPU generator seeded DUMP_SEED (all elements of a smaller tensor), gathered on the device, stored as float32
+    (exact for bf16).  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            if not p.requires_grad:
+                continue
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            idx = torch.randint(0, n, (DUMP_PER_TENSOR,), generator=g) if n > DUMP_PER_TENSOR else torch.arange(n)
+            parts.append(flat[idx.to(flat.device)].float().cpu())
+    out = {"loss": np.array([float(loss.detach())], dtype=np.float64),
+           "params_sample": torch.cat(parts).numpy().astype(np.float32)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as sk:
@@ -295,7 +336,13 @@ def main():
     ap.add_argument("--checkpoint", action="store_true", help="force activation checkpointing of the decoder layers")
     ap.add_argument("--layers", type=int, default=None, help="debug only: truncates the LLaMA stack "
                     "(the printed line is then marked invalid)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: "
+                    "the instrumented last step behind `roofline` and `comm`, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed "
+                    "(loss, a seeded sample of the updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N` (how the driver invokes N = 1): start the N ranks ourselves, exactly as
@@ -322,7 +369,8 @@ def main():
     dev = torch.device("cuda", dev_index)
     force_coll = bool(os.environ.get("MACAW_FORCE_COLLECTIVES"))   # 1-rank RCCL group: call-path check
     if world > 1 or force_coll:
-        os.environ.setdefault("TORCH_NCCL_ENABLE_TIMING", "1")     # per-collective device time for `comm` (below)
+        if args.full:
+            os.environ.setdefault("TORCH_NCCL_ENABLE_TIMING", "1")     # per-collective device time for `comm` (below)
         # each RCCL channel is a resident workgroup that holds a CU for the whole collective; the 256 x 256 GEMM
         # needs whole CUs (scripts/probe/cu_hold.cpp, profiles/r04_cu_hold.csv): cap the channels and let the
         # GEMMs plan for the CUs that remain (BucketedStep(comm_cus=...)).  16 channels over 7 xGMI links.
@@ -446,7 +494,7 @@ def main():
     dw_side_used = False
     t0 = time.perf_counter()
     for i in range(args.steps):
-        last = i == args.steps - 1
+        last = args.full and i == args.steps - 1
         if last:
             # the per-kernel figures (`roofline`) come from THIS step: it updates behind the backward in one launch, so
             # that no kernel of another stream runs beside the GEMMs and a launch's duration is its own (the other
@@ -461,8 +509,13 @@ def main():
         loss = step(eager=last)
     fence()
     dt = time.perf_counter() - t0
-    comm = runtime.comm_report()
-    runtime.profile_comm(False)
+    comm = None
+    if args.full:
+        comm = runtime.comm_report()
+        runtime.profile_comm(False)
+    else:
+        from macaw_llm_amd import engine as _engine
+        dw_side_used = bool(_engine.DW_SIDE["streams"])
     digest = None
     if os.environ.get("MACAW_BENCH_DIGEST") and rank == 0:
         # (after the timed region) sha1 over the trained LLaMA layer 0 / last layer / lm_head weights and the exact loss bits: two
@@ -474,10 +527,11 @@ def main():
                 hsh.update(n.encode())
                 hsh.update(p.detach().view(torch.int16 if p.element_size() == 2 else torch.int32).cpu().numpy().tobytes())
         digest = {"params_sha1": hsh.hexdigest(), "loss_hex": float(loss.detach()).hex()}
-    if os.environ.get("MACAW_GEMM_REPORT") and rank == 0:
-        ops.prof_report(os.environ["MACAW_GEMM_REPORT"])
-    att_f, att_b, gemm8 = ops.prof_sum(1), ops.prof_sum(2), ops.prof_sum(3)
-    gemm_ms, gemm_flops, gemm_n = ops.prof_end()
+    if args.full:
+        if os.environ.get("MACAW_GEMM_REPORT") and rank == 0:
+            ops.prof_report(os.environ["MACAW_GEMM_REPORT"])
+        att_f, att_b, gemm8 = ops.prof_sum(1), ops.prof_sum(2), ops.prof_sum(3)
+        gemm_ms, gemm_flops, gemm_n = ops.prof_end()
     peak_mem = torch.cuda.max_memory_allocated(dev) / 2 ** 30
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
@@ -485,24 +539,11 @@ def main():
     dt = t.item()
     ms_per_step = dt / args.steps * 1e3
     value = world * B / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
 
     if rank == 0:
         S = spec["seq"]
-        alg_tf = spec["alg_tf"]
-        traffic, traffic_src = pmc_gemm_traffic(args.config, gemm_n + gemm8[2])
-        # all mk_gemm launches: bf16 (kind 0) + fp8 (kind 3, cfg 5).  `frac` prices every launch against
-        # ITS OWN dense peak (2.5 PFLOP/s bf16, 5 PFLOP/s e4m3 -- MI355X_MICROARCH.md:42-43): the time the
-        # step's GEMM FLOPs would take at peak / the time they took.
-        ms8, fl8, n8 = gemm8
-        tot_ms, tot_fl = gemm_ms + ms8, gemm_flops + fl8
-        achieved = tot_fl / (tot_ms * 1e-3) if tot_ms > 0 else 0.0
-        gemm_frac = ((gemm_flops / MFMA_BF16_PEAK + fl8 / MFMA_FP8_PEAK) / (tot_ms * 1e-3)) if tot_ms > 0 else 0.0
-
-        def rate(t):      # (ms, flops, launches) -> dict
-            ms, fl, n = t
-            tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-            return {"achieved": round(tf, 1), "frac": round(tf * 1e12 / MFMA_BF16_PEAK, 4), "ms_per_step": round(ms, 3),
-                    "launches_per_step": n}
         line = {
             "metric": METRIC,
             "value": round(value, 3), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -519,71 +560,88 @@ def main():
                        "global_batch": world * B, "per_gpu_batch": B, "seq_len": S,
                        "parallelism": f"dp{world}: " + runtime.describe()
                                       + (f": DEGRADED from ZeRO-1 (its setup step failed: {degraded})" if degraded else ""),
-                       "step_launch": ("hipGraph replay of the whole step (train.GraphedStep); setup step and the "
-                                       "last timed step eager (per-launch HIP events)") if graphed is not None
-                                      else "eager, kernel by kernel",
-                       "grad_weight_side_stream": ("on except in the instrumented last step (engine.DW_SIDE auto: the [M, D] "
-                                                   "grad-input GEMMs leave CUs idle at this shape)") if dw_side_used
+                       "step_launch": ("hipGraph replay of the whole step (train.GraphedStep); setup step"
+                                       + (" and the last timed step eager (per-launch HIP events)" if args.full else " eager"))
+                                      if graphed is not None else "eager, kernel by kernel",
+                       "grad_weight_side_stream": (("on except in the instrumented last step" if args.full else "on")
+                                                   + " (engine.DW_SIDE auto: the [M, D] grad-input GEMMs leave CUs idle "
+                                                   "at this shape)") if dw_side_used
                                                   else "off (engine.DW_SIDE auto)",
                        "setup_steps": 1, "activation_checkpointing": bool(spec["ckpt"]),
                        "peak_mem_gib": round(peak_mem, 1),
                        "loss": round(float(loss.detach()), 4),
                        **({"digest": digest} if digest else {})},
-            "roofline": {"bound": "mfma", "kernel": "all mk_gemm launches of the step: gemm_bf16_v7_kernel (256x256, 8 waves, "
-                                                    "csrc/gemm_v7.hip; its <.., FP8> instantiation for e4m3 operands) + "
-                                                    "gemm_bf16_v9_kernel (256x256, 4 waves, generated inline-asm K loop, "
-                                                    "csrc/gemm_v9.hip: grad-weight and grad-input) + "
-                                                    "gemm_bf16_v2_kernel (128x128, csrc/gemm.hip)",
-                         "measured_on": ("the LAST timed step, HIP events around every launch on the compute stream; that "
-                                         "step updates behind the backward in one AdamW launch, so no kernel of another "
-                                         "stream runs beside the GEMMs"
-                                         + (" (the other timed steps overlap the per-bucket AdamW launches with the "
-                                            "backward on a high-priority side stream)"
-                                            if getattr(runtime, "local_overlap", False) else "")),
-                         "achieved": round(achieved / 1e12, 2), "peak": MFMA_BF16_PEAK / 1e12,
-                         "unit": "TFLOP/s", "frac": round(gemm_frac, 4),
-                         "traffic": traffic,
-                         "traffic_note": (f"HBM-side bytes per mk_gemm launch of the cfg {args.config} step (rocprofv3 "
-                                          f"PMC, profiles/{traffic_src}; includes Infinity-Cache hits)") if traffic
-                                         else f"no PMC profile of cfg {args.config} committed under profiles/",
-                         "launches_per_step": gemm_n + n8, "gemm_ms_per_step": round(tot_ms, 3),
-                         "gemm_tflop_per_step": round(tot_fl / 1e12, 2),
-                         **({"fp8_gemms": {"launches_per_step": n8, "ms_per_step": round(ms8, 3),
-                                           "achieved": round(fl8 / (ms8 * 1e-3) / 1e12, 1) if ms8 > 0 else 0.0,
-                                           "peak": MFMA_FP8_PEAK / 1e12,
-                                           "frac": round(fl8 / (ms8 * 1e-3) / MFMA_FP8_PEAK, 4) if ms8 > 0 else 0.0},
-                             "bf16_gemms": {"launches_per_step": gemm_n, "ms_per_step": round(gemm_ms, 3),
-                                            "achieved": round(gemm_flops / (gemm_ms * 1e-3) / 1e12, 1) if gemm_ms > 0 else 0.0,
-                                            "frac": round(gemm_flops / (gemm_ms * 1e-3) / MFMA_BF16_PEAK, 4) if gemm_ms > 0 else 0.0},
-                             "frac_note": "frac = (bf16 FLOPs / 2.5 PF + fp8 FLOPs / 5 PF) / GEMM time: each launch "
-                                          "priced against its own dense peak"} if n8 else {}),
-                         # context, not the contract's peak: a register-only MFMA loop sustains 2475 TFLOP/s on all-zero
-                         # operands but 1767-1781 on random bf16 data on this part (power-bound; profiles/r06_mfma_power.txt)
-                         **({"real_data_mfma_ceiling": {"tflops": 1775.0, "frac_of_it": round(achieved / 1775.0e12, 4),
-                                                        "source": "scripts/probe/mfma_power.hip, profiles/r06_mfma_power.txt"}}
-                            if not n8 else {}),          # (bf16 runs only: the probe measured the bf16 pipe)
-                         "whole_step_model_tflops": round(value / world * alg_tf, 1),
-                         "whole_step_frac": round(value / world * alg_tf * 1e12 / MFMA_BF16_PEAK, 4),
-                         # fused attention kernels (csrc/attention.hip), algorithmic FLOPs (causal =
-                         # lower triangle), same live HIP-event timing
-                         "attention_fwd": rate(att_f), "attention_bwd": rate(att_b)},
         }
-        # how the step's communication went on rank 0 (last timed step): the un-overlapped tail behind the backward
-        # and every bucket's reduce-scatter / all-gather duration and bytes -- see BucketedStep.comm_report()
-        line["comm"] = comm
-        if args.config == 3 and world in PREDICTED_CFG3 and B == CONFIGS[3]["batch"]:
-            pred = dict(PREDICTED_CFG3[world], source="DESIGN.md section 6 (model: RCCL ring bus bandwidth 230-350 GB/s at "
-                        "N = 8, ~170 at N = 4, ~60 at N = 2; 27 ms of step time per 100 ms of overlapped side work)")
-            if isinstance(line["comm"], dict):
-                line["comm"]["predicted"] = pred
-                line["comm"]["predicted_ms"] = pred["step_ms"]
-            else:
-                line["comm"] = {"world": world, "collective": "none", "predicted": pred, "predicted_ms": pred["step_ms"]}
+        if args.full:
+            alg_tf = spec["alg_tf"]
+            traffic, traffic_src = pmc_gemm_traffic(args.config, gemm_n + gemm8[2])
+            # all mk_gemm launches: bf16 (kind 0) + fp8 (kind 3, cfg 5).  `frac` prices every launch against
+            # ITS OWN dense peak (2.5 PFLOP/s bf16, 5 PFLOP/s e4m3: MFMA_BF16_PEAK / MFMA_FP8_PEAK): the time the
+            # step's GEMM FLOPs would take at peak / the time they took.
+            ms8, fl8, n8 = gemm8
+            tot_ms, tot_fl = gemm_ms + ms8, gemm_flops + fl8
+            achieved = tot_fl / (tot_ms * 1e-3) if tot_ms > 0 else 0.0
+            gemm_frac = ((gemm_flops / MFMA_BF16_PEAK + fl8 / MFMA_FP8_PEAK) / (tot_ms * 1e-3)) if tot_ms > 0 else 0.0
+
+            def rate(t):      # (ms, flops, launches) -> dict
+                ms, fl, n = t
+                tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+                return {"achieved": round(tf, 1), "frac": round(tf * 1e12 / MFMA_BF16_PEAK, 4), "ms_per_step": round(ms, 3),
+                        "launches_per_step": n}
+            line["roofline"] = {"bound": "mfma", "kernel": "all mk_gemm launches of the step: gemm_bf16_v7_kernel (256x256, 8 waves, "
+                                                          "csrc/gemm_v7.hip; its <.., FP8> instantiation for e4m3 operands) + "
+                                                          "gemm_bf16_v9_kernel (256x256, 4 waves, generated inline-asm K loop, "
+                                                          "csrc/gemm_v9.hip: grad-weight and grad-input) + "
+                                                          "gemm_bf16_v2_kernel (128x128, csrc/gemm.hip)",
+                               "measured_on": ("the LAST timed step, HIP events around every launch on the compute stream; that "
+                                               "step updates behind the backward in one AdamW launch, so no kernel of another "
+                                               "stream runs beside the GEMMs"
+                                               + (" (the other timed steps overlap the per-bucket AdamW launches with the "
+                                                  "backward on a high-priority side stream)"
+                                                  if getattr(runtime, "local_overlap", False) else "")),
+                               "achieved": round(achieved / 1e12, 2), "peak": MFMA_BF16_PEAK / 1e12,
+                               "unit": "TFLOP/s", "frac": round(gemm_frac, 4),
+                               "traffic": traffic,
+                               "traffic_note": (f"HBM-side bytes per mk_gemm launch of the cfg {args.config} step (rocprofv3 "
+                                                f"PMC, profiles/{traffic_src}; includes Infinity-Cache hits)") if traffic
+                                               else f"no PMC profile of cfg {args.config} committed under profiles/",
+                               "launches_per_step": gemm_n + n8, "gemm_ms_per_step": round(tot_ms, 3),
+                               "gemm_tflop_per_step": round(tot_fl / 1e12, 2),
+                               **({"fp8_gemms": {"launches_per_step": n8, "ms_per_step": round(ms8, 3),
+                                                 "achieved": round(fl8 / (ms8 * 1e-3) / 1e12, 1) if ms8 > 0 else 0.0,
+                                                 "peak": MFMA_FP8_PEAK / 1e12,
+                                                 "frac": round(fl8 / (ms8 * 1e-3) / MFMA_FP8_PEAK, 4) if ms8 > 0 else 0.0},
+                                   "bf16_gemms": {"launches_per_step": gemm_n, "ms_per_step": round(gemm_ms, 3),
+                                                  "achieved": round(gemm_flops / (gemm_ms * 1e-3) / 1e12, 1) if gemm_ms > 0 else 0.0,
+                                                  "frac": round(gemm_flops / (gemm_ms * 1e-3) / MFMA_BF16_PEAK, 4) if gemm_ms > 0 else 0.0},
+                                   "frac_note": "frac = (bf16 FLOPs / 2.5 PF + fp8 FLOPs / 5 PF) / GEMM time: each launch "
+                                                "priced against its own dense peak"} if n8 else {}),
+                               # context, not the contract's peak: a register-only MFMA loop sustains 2475 TFLOP/s on all-zero
+                               # operands but 1767-1781 on random bf16 data on this part (power-bound; profiles/r06_mfma_power.txt)
+                               **({"real_data_mfma_ceiling": {"tflops": 1775.0, "frac_of_it": round(achieved / 1775.0e12, 4),
+                                                              "source": "scripts/probe/mfma_power.hip, profiles/r06_mfma_power.txt"}}
+                                  if not n8 else {}),          # (bf16 runs only: the probe measured the bf16 pipe)
+                               "whole_step_model_tflops": round(value / world * alg_tf, 1),
+                               "whole_step_frac": round(value / world * alg_tf * 1e12 / MFMA_BF16_PEAK, 4),
+                               # fused attention kernels (csrc/attention.hip), algorithmic FLOPs (causal =
+                               # lower triangle), same live HIP-event timing
+                               "attention_fwd": rate(att_f), "attention_bwd": rate(att_b)}
+            # how the step's communication went on rank 0 (last timed step): the un-overlapped tail behind the backward
+            # and every bucket's reduce-scatter / all-gather duration and bytes -- see BucketedStep.comm_report()
+            line["comm"] = comm
+            if args.config == 3 and world in PREDICTED_CFG3 and B == CONFIGS[3]["batch"]:
+                pred = dict(PREDICTED_CFG3[world], source="DESIGN.md section 6 (model: RCCL ring bus bandwidth 230-350 GB/s "
+                            "at N = 8, ~170 at N = 4, ~60 at N = 2; 27 ms of step time per 100 ms of overlapped side work)")
+                if isinstance(line["comm"], dict):
+                    line["comm"]["predicted"] = pred
+                    line["comm"]["predicted_ms"] = pred["step_ms"]
+                else:
+                    line["comm"] = {"world": world, "collective": "none", "predicted": pred, "predicted_ms": pred["step_ms"]}
         if args.layers is not None:
             line["invalid"] = f"debug run with --layers {args.layers}"
         if share_gpu or backend != "nccl" or inject is not None:
             line["invalid"] = "call-path test (ranks sharing one GPU / gloo collectives / injected failure), not a benchmark"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cb = cpu_baseline(host_cores(), spec)
                 line["cpu_baseline"] = cb

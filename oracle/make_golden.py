@@ -31,13 +31,16 @@ FULL_GRAD_KEYS = (
 )
 
 
-def reference_greedy(llm, inputs_embeds, max_new_tokens, eos, pad):
-    """greedy decode through the reference's own cached forward; returns new token ids [B, <= max_new_tokens]"""
+def reference_greedy(llm, inputs_embeds, max_new_tokens, eos, pad, step_logits=None):
+    """greedy decode through the reference's own cached forward; returns new token ids [B, <= max_new_tokens]
+    (and appends each step's last-position logits to `step_logits` when a list is given)"""
     out = llm(inputs_embeds=inputs_embeds, use_cache=True)
     B = inputs_embeds.shape[0]
     done = torch.zeros(B, dtype=torch.bool)
     ids = []
     for _ in range(max_new_tokens):
+        if step_logits is not None:
+            step_logits.append(out.logits[:, -1, :].detach().clone())
         nxt = out.logits[:, -1, :].argmax(-1)
         nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
         ids.append(nxt)
@@ -134,16 +137,67 @@ def make_real7b_layer(name="real7b_layer", seed=4242, B=2, S=24, head_rows=512):
           f"{os.path.getsize(path)/1e6:.2f} MB", file=sys.stderr)
 
 
+# ---- recorded live-reference checks (tests/golden/reference_checks.pt): what tests/test_oracle.py and
+# tests/test_host_logic_cpu.py compare the restatement and the product's checkpoint surface with, recorded from the
+# reference's own classes on the micro config at seed 1234 (the weights of micro_state_seed1234.pt) so that the
+# tests need nothing outside the repository.
+LIVE_MODS = (("images", "audios", "videos"), ("images",), ("audios", "videos"))
+LIVE_INPUTS = dict(batch=3, text_len=10, seed=5, pad_tail=2)
+
+
+def make_reference_checks(name="reference_checks", seed=1234):
+    cfg = configs.get("micro")
+    model = ref_loader.build_reference_model(cfg, seed=seed)
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    hot = restate.hot_path_state(sd)
+    state_path = os.path.join(GOLDEN_DIR, f"micro_state_seed{seed}.pt")
+    committed = torch.load(state_path, weights_only=False)
+    if set(committed) != set(hot) or not all(torch.equal(committed[k], hot[k]) for k in hot):
+        raise SystemExit(f"{state_path} is not the hot-path state of the reference at seed {seed}")
+    fx = dict(seed=seed, state_file=os.path.basename(state_path),
+              state_rest={k: v.contiguous() for k, v in sd.items() if k not in hot}, live={})
+    with torch.no_grad():
+        for mods in LIVE_MODS:
+            inp = oin.make_inputs(cfg, LIVE_INPUTS["batch"], LIVE_INPUTS["text_len"], modalities=mods,
+                                  seed=LIVE_INPUTS["seed"], pad_tail=LIVE_INPUTS["pad_tail"])
+            emb, am, lab = model.prepare_inputs_for_generation(inp)
+            out = model(inputs=inp)
+            fx["live"]["+".join(mods)] = dict(inputs_embeds=emb, attention_mask=am, labels=lab, logits=out.logits,
+                                              loss=out.loss)
+        # the reference's text-only quirk (modeling.py:1043-1044): float labels, CrossEntropyLoss raises
+        inp = oin.make_inputs(cfg, 2, 10, modalities=(), seed=5)
+        try:
+            model(inputs=inp)
+            fx["text_only_error"] = None
+        except RuntimeError as e:
+            fx["text_only_error"] = f"{type(e).__name__}: {e}"[:300]
+        fx["positional_encoding_12x48"] = ref_loader.load_reference_modeling().create_positional_encoding(12, 48)
+        # the reference's cached greedy decode of micro_all (the same weights), step by step
+        case = torch.load(os.path.join(GOLDEN_DIR, "micro_all.pt"), weights_only=False)
+        steps = []
+        ids = reference_greedy(model.llm, case["inputs_embeds"], max_new_tokens=8, eos=2, pad=cfg["tags"]["pad"],
+                               step_logits=steps)
+        fx["decode_ids"], fx["decode_step_logits"] = ids, torch.stack(steps, dim=1)
+    path = os.path.join(GOLDEN_DIR, name + ".pt")
+    torch.save(fx, path)
+    print(f"{name}: {len(fx['state_rest'])} non-hot-path tensors, text-only: {fx['text_only_error']!r:.60}, "
+          f"decode ids {ids.tolist()}, {os.path.getsize(path) / 1e6:.2f} MB", file=sys.stderr)
+
+
 def main():
     if not ref_loader.reference_available():
         raise SystemExit("needs /root/reference")
     if "--real7b-only" in sys.argv:
         make_real7b_layer()
         return
+    if "--reference-checks-only" in sys.argv:
+        make_reference_checks()
+        return
     make("micro_all", "micro", batch=2, text_len=12, modalities=("images", "audios", "videos"),
          pad_tail=3, with_generate=True)
     make("micro_image", "micro", batch=1, text_len=9, modalities=("images",), pad_tail=0)
     make_real7b_layer()
+    make_reference_checks()
 
 
 if __name__ == "__main__":

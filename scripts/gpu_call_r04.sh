@@ -48,8 +48,8 @@ for step in "$@"; do
       timeout 600 python -m pytest tests/test_hf_trainer_gpu.py -q -rf --timeout 600 -p no:cacheprovider > $out/t_hf.log 2>&1
       echo "pytest rc=$?" >> $out/t_hf.log ;;
     rccl1)   # the collective path through a 1-rank RCCL group: bench line with `comm`, then a kernel trace of it
-      MACAW_FORCE_COLLECTIVES=1 timeout 400 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $out/bench_cfg3_1rank_rccl.json 2> $out/bench_cfg3_1rank_rccl.err
-      (cd /tmp && MACAW_FORCE_COLLECTIVES=1 timeout 500 rocprofv3 --kernel-trace -d /tmp/rccl1 -o t --output-format csv -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OLDPWD/$out/rccl1_trace.log 2>&1)
+      MACAW_FORCE_COLLECTIVES=1 timeout 400 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $out/bench_cfg3_1rank_rccl.json 2> $out/bench_cfg3_1rank_rccl.err
+      (cd /tmp && MACAW_FORCE_COLLECTIVES=1 timeout 500 rocprofv3 --kernel-trace -d /tmp/rccl1 -o t --output-format csv -- python $OLDPWD/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OLDPWD/$out/rccl1_trace.log 2>&1)
       f=$(find /tmp/rccl1 -name '*kernel_trace.csv' | head -1)
       [ -n "$f" ] && python scripts/trace_last_step.py "$f" > $out/cfg3_1rank_rccl_last_step.txt 2>&1 ;;
     cuhold)  # GEMMs beside a resident kernel holding 8 / 16 / 32 CUs, planned for 256 or for the free CUs
@@ -93,8 +93,8 @@ for step in "$@"; do
       echo "pytest rc=$?" >> $out/t_mix.log
       timeout 200 python scripts/bench_attn.py > $out/attn.txt 2>&1
       GB_COLD=1 GB_ITERS=10 GB_ROUNDS=3 timeout 300 $GB scripts/gemm_shapes_enc.txt > $out/gemm_enc_cold.csv 2> $out/gemm_enc.err
-      timeout 300 python bench.py --config 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_cfg2.json 2> $out/bench_cfg2.err
-      timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
+      timeout 300 python bench.py --full --config 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_cfg2.json 2> $out/bench_cfg2.err
+      timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
     decode)  # decode attention for many (sample, head) pairs: four heads per workgroup vs one (A/B), tests
       timeout 600 python -m pytest tests/test_kernels_gpu.py tests/test_model_gpu.py tests/test_fullsize_gpu.py -k "decode or generate" -q -rf --timeout 300 -p no:cacheprovider > $out/t_decode.log 2>&1
       echo "pytest rc=$?" >> $out/t_decode.log
@@ -107,9 +107,9 @@ for step in "$@"; do
       timeout 1200 python -m pytest tests -m gpu -q -rf --timeout 300 --durations=12 -p no:cacheprovider > $out/tests.log 2>&1
       echo "pytest rc=$?" >> $out/tests.log ;;
     bench)
-      timeout 600 python bench.py --steps 8 --warmup 3 > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
+      timeout 600 python bench.py --full --steps 8 --warmup 3 > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
     benchq)
-      timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
+      timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
     pcsamp)  # instruction-level stall evidence: stochastic PC sampling of the v7 / v8 main loops (beta feature: bounded)
       printf '4608 12288 4096 0 11 14\n4608 4096 12288 1 11 14\n' > /tmp/pcs_shapes.txt
       (cd /tmp && GB_ITERS=30 GB_ROUNDS=1 timeout 180 rocprofv3 --pc-sampling-beta-enabled --pc-sampling-method stochastic \

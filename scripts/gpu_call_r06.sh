@@ -18,9 +18,9 @@ for step in "$@"; do
       [ -n "$t" ] && python3 $R/scripts/trace_kernels_by_grid.py "$t" Cijk > $out/vendor_kernels_by_grid.txt
       rm -rf /tmp/vk ;;
     benchq)
-      timeout 600 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
+      timeout 600 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg3.json 2> $out/bench_cfg3.err ;;
     bench)
-      timeout 600 python bench.py --steps 20 --warmup 3 > $out/bench_cfg3_full.json 2> $out/bench_cfg3_full.err ;;
+      timeout 600 python bench.py --full --steps 20 --warmup 3 > $out/bench_cfg3_full.json 2> $out/bench_cfg3_full.err ;;
     tests)
       timeout 2400 python -m pytest tests -m gpu -q -rf --timeout 300 --durations=12 -p no:cacheprovider > $out/tests.log 2>&1
       echo "pytest rc=$?" >> $out/tests.log ;;

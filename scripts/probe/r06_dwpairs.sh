@@ -4,7 +4,7 @@ out=$1
 for i in 1 2; do
   for p in off o down qkv gu lm; do
     if [ $p = off ]; then export MACAW_DW_STREAM=0; unset MACAW_DW_PAIRS; else export MACAW_DW_STREAM=1 MACAW_DW_PAIRS=$p; fi
-    timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_${p}_$i.json 2> $out/bench_${p}_$i.err
+    timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_${p}_$i.json 2> $out/bench_${p}_$i.err
     python3 -c "
 import json
 d=json.load(open('$out/bench_${p}_$i.json'))

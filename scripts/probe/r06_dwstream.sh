@@ -7,7 +7,7 @@ for i in 1 2; do
   for c in 2 3; do
     for m in side plain; do
       if [ $m = side ]; then export MACAW_DW_STREAM=1; else unset MACAW_DW_STREAM; fi
-      timeout 300 python bench.py --config $c --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg${c}_${m}_$i.json 2> $out/bench_cfg${c}_${m}_$i.err
+      timeout 300 python bench.py --full --config $c --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg${c}_${m}_$i.json 2> $out/bench_cfg${c}_${m}_$i.err
       python3 -c "
 import json
 d=json.load(open('$out/bench_cfg${c}_${m}_$i.json'))

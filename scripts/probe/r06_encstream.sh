@@ -8,7 +8,7 @@ MACAW_ENC_STREAMS=1 timeout 900 python -m pytest tests/test_model_gpu.py tests/t
 for i in 1 2; do
   for m in side plain; do
     if [ $m = side ]; then export MACAW_ENC_STREAMS=1; else unset MACAW_ENC_STREAMS; fi
-    timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg3_${m}_$i.json 2> $out/bench_cfg3_${m}_$i.err
+    timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_cfg3_${m}_$i.json 2> $out/bench_cfg3_${m}_$i.err
     python3 -c "
 import json
 d=json.load(open('$out/bench_cfg3_${m}_$i.json'))

@@ -3,7 +3,7 @@
 out=$1
 run() { # tag env...
   tag=$1; shift
-  env "$@" timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_$tag.json 2> $out/bench_$tag.err
+  env "$@" timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_$tag.json 2> $out/bench_$tag.err
   python3 - $out/bench_$tag.json $tag <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_model_gpu.py tests/test_train_gpu.py -m 
 for i in 1 2; do
   for m in bwd full off; do
     export MACAW_ROPE_FUSE=$m
-    MACAW_GEMM_REPORT=$out/shapes_${m}_$i.csv timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_${m}_$i.json 2> $out/bench_${m}_$i.err
+    MACAW_GEMM_REPORT=$out/shapes_${m}_$i.csv timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $out/bench_${m}_$i.json 2> $out/bench_${m}_$i.err
     python3 -c "
 import json,sys
 d=json.load(open('$out/bench_${m}_$i.json'))

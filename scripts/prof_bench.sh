@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 --kernel-trace --stats of bench.py; copies the kernel-stats CSV to gpurun_out/<tag>_kernel_stats.csv
-# usage: scripts/prof_bench.sh <tag> [bench args...]     (env vars pass through)
+# usage: scripts/prof_bench.sh <tag> [bench args...]     (env vars pass through; pass --full for the instrumented last step)
 TAG=$1; shift
 ROOT=$(pwd)
 export TMPDIR=/tmp

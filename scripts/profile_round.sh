@@ -14,24 +14,24 @@ export TMPDIR=/tmp
 has() { [[ " $WHAT " == *" $1 "* ]]; }
 
 if has bench; then
-  MACAW_GEMM_REPORT=$OUT/${R}_gemm_shapes_per_step.csv timeout 400 python bench.py --steps 10 --warmup 3 > $OUT/${R}_bench_cfg3.json 2> $OUT/${R}_bench_cfg3.err
+  MACAW_GEMM_REPORT=$OUT/${R}_gemm_shapes_per_step.csv timeout 400 python bench.py --full --steps 10 --warmup 3 > $OUT/${R}_bench_cfg3.json 2> $OUT/${R}_bench_cfg3.err
   for c in 2 4 5; do
-    timeout 500 python bench.py --config $c --steps 5 --warmup 2 > $OUT/${R}_bench_cfg$c.json 2> $OUT/${R}_bench_cfg$c.err
+    timeout 500 python bench.py --full --config $c --steps 5 --warmup 2 > $OUT/${R}_bench_cfg$c.json 2> $OUT/${R}_bench_cfg$c.err
   done
   # cfg 5: the bf16 yardstick of its fp8 speed-up, and the fp8 path extended to the MLP GEMMs
-  timeout 500 python bench.py --config 5 --steps 5 --warmup 2 --no-cpu-baseline --no-fp8 > $OUT/${R}_bench_cfg5_bf16.json 2> $OUT/${R}_bench_cfg5_bf16.err
-  timeout 500 python bench.py --config 5 --steps 5 --warmup 2 --no-cpu-baseline --fp8-mlp > $OUT/${R}_bench_cfg5_fp8mlp.json 2> $OUT/${R}_bench_cfg5_fp8mlp.err
+  timeout 500 python bench.py --full --config 5 --steps 5 --warmup 2 --no-cpu-baseline --no-fp8 > $OUT/${R}_bench_cfg5_bf16.json 2> $OUT/${R}_bench_cfg5_bf16.err
+  timeout 500 python bench.py --full --config 5 --steps 5 --warmup 2 --no-cpu-baseline --fp8-mlp > $OUT/${R}_bench_cfg5_fp8mlp.json 2> $OUT/${R}_bench_cfg5_fp8mlp.err
 fi
 if has bench3; then     # only the metric's configuration (after a host-side change that leaves the kernels alone)
-  MACAW_GEMM_REPORT=$OUT/${R}_gemm_shapes_per_step.csv timeout 400 python bench.py --steps 10 --warmup 3 > $OUT/${R}_bench_cfg3.json 2> $OUT/${R}_bench_cfg3.err
-  timeout 500 python bench.py --config 2 --steps 5 --warmup 2 > $OUT/${R}_bench_cfg2.json 2> $OUT/${R}_bench_cfg2.err
+  MACAW_GEMM_REPORT=$OUT/${R}_gemm_shapes_per_step.csv timeout 400 python bench.py --full --steps 10 --warmup 3 > $OUT/${R}_bench_cfg3.json 2> $OUT/${R}_bench_cfg3.err
+  timeout 500 python bench.py --full --config 2 --steps 5 --warmup 2 > $OUT/${R}_bench_cfg2.json 2> $OUT/${R}_bench_cfg2.err
 fi
 PROF_CFGS="3 2 4 5"
 has prof3 && PROF_CFGS="3"
 if has prof || has prof3; then
   for c in $PROF_CFGS; do
     cd /tmp; rm -rf /tmp/prof_c$c
-    timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_c$c -o p --output-format csv -- python $ROOT/bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${R}_prof_cfg$c.json 2> $OUT/${R}_prof_cfg$c.err
+    timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_c$c -o p --output-format csv -- python $ROOT/bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${R}_prof_cfg$c.json 2> $OUT/${R}_prof_cfg$c.err
     f=$(find /tmp/prof_c$c -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $OUT/${R}_cfg${c}_kernel_stats.csv
     t=$(find /tmp/prof_c$c -name '*kernel_trace.csv' | head -1); [ -n "$t" ] && python3 $ROOT/scripts/trace_gaps.py "$t" > $OUT/${R}_cfg${c}_last_step.txt 2>&1
     cd $ROOT
@@ -46,7 +46,7 @@ if has traffic || has traffic3; then
   for c in $TRAFFIC_CFGS; do
     for ctr in FETCH_SIZE WRITE_SIZE; do
       rm -rf /tmp/pmc_$ctr
-      timeout 600 rocprofv3 --pmc $ctr -d /tmp/pmc_$ctr -o p --output-format csv -- python $ROOT/bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/${R}_pmc_${ctr}_cfg$c.err
+      timeout 600 rocprofv3 --pmc $ctr -d /tmp/pmc_$ctr -o p --output-format csv -- python $ROOT/bench.py --full --config $c --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/${R}_pmc_${ctr}_cfg$c.err
     done
     fr=$(find /tmp/pmc_FETCH_SIZE -name '*counter_collection.csv' | head -1)
     fw=$(find /tmp/pmc_WRITE_SIZE -name '*counter_collection.csv' | head -1)
@@ -83,10 +83,10 @@ if has gemmpmc; then
 fi
 if has rccl; then
   # the N > 1 call path through a 1-rank RCCL group (reduce-scatter / shard AdamW / all-gather really issued)
-  MACAW_FORCE_COLLECTIVES=1 timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${R}_bench_cfg3_1rank_rccl.json 2> $OUT/${R}_bench_rccl.err
+  MACAW_FORCE_COLLECTIVES=1 timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${R}_bench_cfg3_1rank_rccl.json 2> $OUT/${R}_bench_rccl.err
   # ... and two ranks sharing this GPU over gloo (bench.py's N > 1 branch end to end; not a benchmark)
   MACAW_SHARE_GPU=1 MACAW_DIST_BACKEND=gloo timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 3 --warmup 1 --batch-per-gpu 8 --no-cpu-baseline \
+    --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --steps 3 --warmup 1 --batch-per-gpu 8 --no-cpu-baseline \
     > $OUT/${R}_bench_cfg3_2ranks_1gpu_gloo.json 2>> $OUT/${R}_bench_rccl.err
 fi
 if has parity; then

@@ -109,3 +109,25 @@ def test_bare_gpus_n_without_a_gpu_fails_in_the_ranks_not_in_the_launcher(tmp_pa
                        env=env, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
     assert r.returncode != 0
     assert "needs an MI355X" in r.stderr and "torch.distributed" in r.stderr       # the message came from a spawned rank
+
+
+def test_dump_outputs_writes_a_fixed_seeded_sample(tmp_path):
+    """--dump-outputs: loss as float64, the trainable parameters as a seeded float32 sample of at most DUMP_PER_TENSOR
+    elements per tensor (frozen ones left out); the same model gives the same files, byte for byte"""
+    import numpy as np
+    import torch
+    b = _bench()
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(100, 64), torch.nn.Linear(64, 8)).to(torch.bfloat16)
+    model[1].bias.requires_grad_(False)
+    loss = torch.tensor(2.5, dtype=torch.bfloat16)
+    shapes = b.dump_outputs(str(tmp_path / "a"), loss, model)
+    b.dump_outputs(str(tmp_path / "b"), loss, model)
+    assert b.DUMP_PER_TENSOR == 4096
+    assert shapes == {"loss": [1], "params_sample": [4096 + 64 + 512]}      # 0.weight sampled, 0.bias + 1.weight whole
+    lo, ps = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "a" / "params_sample.npy")
+    assert lo.dtype == np.float64 and lo[0] == 2.5 and ps.dtype == np.float32
+    assert np.array_equal(ps[-512:], model[1].weight.detach().float().reshape(-1).numpy())
+    for name in ("loss.npy", "params_sample.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes()
+

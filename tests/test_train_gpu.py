@@ -527,7 +527,7 @@ def test_bench_py_runs_its_n_gt_1_branch_with_two_ranks_on_this_gpu(dev, inject)
         env["MACAW_BENCH_INJECT_FAIL"] = inject
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--layers", "2", "--batch-per-gpu", "2", "--no-cpu-baseline"]
+           "--warmup", "1", "--layers", "2", "--batch-per-gpu", "2", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -688,3 +688,29 @@ def test_bucketed_two_ranks_with_the_grad_weight_side_stream(dev, monkeypatch):
         for s_p, s_s in zip(plain[rank][3], side[rank][3]):
             for e_p, e_s in zip(s_p, s_s):
                 assert e_p["local_grad"] == e_s["local_grad"] and e_p["reduced"] == e_s["reduced"], (rank, e_p, e_s)
+
+
+def test_plain_bench_run_dumps_the_last_step_and_leaves_the_rest_to_full(dev, tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` times N alike steps and prints the headline line only (roofline, comm
+    and cpu_baseline are --full's); --dump-outputs writes the last timed step's loss and parameter sample"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--layers", "2",
+           "--batch-per-gpu", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 / (d["ms_per_step"] * 1e-3)) < 0.02 * d["value"]
+    assert not {"roofline", "comm", "cpu_baseline"} & set(d)
+    loss, ps = np.load(out / "loss.npy"), np.load(out / "params_sample.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and round(float(loss[0]), 4) == d["config"]["loss"]
+    assert ps.dtype == np.float32 and ps.size > 0 and np.isfinite(ps).all()
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
