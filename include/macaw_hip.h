@@ -36,7 +36,7 @@ extern "C" {
 #define MK_FP8 3 /* OCP e4m3fn bytes: mk_gemm operands / mk_fp8_quantize output only */
 
 /* library identification: returns MK_ABI_VERSION */
-#define MK_ABI_VERSION 6
+#define MK_ABI_VERSION 7
 int mk_abi_version(void);
 
 /* ------------------------------------------------------------------ GEMM --
@@ -446,6 +446,42 @@ int mk_adamw_chunk(void);
 int mk_adamw_multi(const void* items, const int64_t* chunk_start, int32_t n_items, int64_t n_chunks,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
                    float grad_scale, int32_t dtype, void* stream);
+
+/* ----------------------------------------------------------------- LoRA --
+ * Low-rank adapters of the LLaMA projections (macaw_llm_amd/lora.py, peft LoraLayer semantics):
+ * y = x W^T + s (drop(x) A^T) B^T with A [r, K], B [N, r] (row-major, 16-byte aligned), s = lora_alpha / r,
+ * r a multiple of 8 in [8, 128].  A GROUP is 1-3 modules that share an input (q|k|v, gate|up); unused
+ * pointers of a group may be NULL.  Every product runs on the 16x16x32 MFMA (bf16 / f16, fp32 accumulation);
+ * every reduction runs in a fixed order (no float atomics): the backward is bit-reproducible.
+ * Dropout (inverted, p in [0, 1)): module i keeps x[m, k] iff mk_hash32(seed + offset, tags[i] << 40 | m K + k)
+ * < (1 - p) 2^32, offset = the device value of mk_set_dropout_seed_offset (0 without one); tags: HOST
+ * uint64[G] (layer, module) read at the call.  Masks are regenerated, never stored.
+ *  - mk_lora_down:   U[m, i r + j] = sum_k drop_i(X)[m, k] A_i[j, k]  ->  U [M, G r] and Ut [G r, ldut]
+ *                    (pad8(M) <= ldut <= ceil16(M), a multiple of 8; columns [M, ldut) of Ut are written as 0;
+ *                    the same pitch for Ut / dUt in mk_lora_bwd_dy and mk_lora_bwd_x)
+ *  - mk_lora_up_add: Y_i[m, n] += s sum_j U[m, i r + j] B_i[n, j], rounded once (Y_i [M, N], pitch ldy)
+ *  - mk_lora_bwd_dy: dU = s dY_i B_i -> dU [M, G r], dUt [G r, ldut];  dB_i = s dY_i^T U_i (from Ut)
+ *  - mk_lora_bwd_x:  dX += sum_i drop'_i(dU_i A_i);  dA_i = dU_i^T drop_i(X)  (dU, dUt from mk_lora_bwd_dy)
+ *  - mk_lora_merge:  W[n, k] += s sum_j B[n, j] A[j, k], fp32, one rounding
+ * ws: DEVICE scratch of at least mk_lora_workspace(M, N or K, G, r) bytes (merge: with M = 1, G = 1).
+ * Launch kind 4 of the in-library profiler (mk_prof_sum). */
+int mk_lora_workspace(int32_t M, int32_t N, int32_t G, int32_t r, int64_t* bytes);
+int mk_lora_down(const void* X, int64_t ldx, int32_t M, int32_t K, const void* A0, const void* A1,
+                 const void* A2, int32_t G, int32_t r, void* U, void* Ut, int64_t ldut, float p,
+                 uint64_t seed, const uint64_t* tags, int32_t dtype, void* stream);
+int mk_lora_up_add(const void* U, int32_t M, int32_t r, int32_t G, const void* B0, const void* B1,
+                   const void* B2, void* Y0, void* Y1, void* Y2, int64_t ldy, int32_t N, float s,
+                   int32_t dtype, void* stream);
+int mk_lora_bwd_dy(const void* dY0, const void* dY1, const void* dY2, int64_t ldy, int32_t M, int32_t N,
+                   const void* B0, const void* B1, const void* B2, const void* Ut, int64_t ldut, int32_t G,
+                   int32_t r, float s, void* dU, void* dUt, void* dB0, void* dB1, void* dB2, void* ws,
+                   int64_t ws_bytes, int32_t dtype, void* stream);
+int mk_lora_bwd_x(const void* X, int64_t ldx, int32_t M, int32_t K, const void* dU, const void* dUt,
+                  int64_t ldut, const void* A0, const void* A1, const void* A2, int32_t G, int32_t r, float p,
+                  uint64_t seed, const uint64_t* tags, void* dX, int64_t lddx, void* dA0, void* dA1, void* dA2,
+                  void* ws, int64_t ws_bytes, int32_t dtype, void* stream);
+int mk_lora_merge(void* W, int64_t ldw, int32_t N, int32_t K, const void* A, const void* B, int32_t r,
+                  float s, void* ws, int64_t ws_bytes, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -535,6 +535,8 @@ extern "C" int mk_set_dropout_seed_offset(const uint64_t* dev_ptr) {
   g_seed_dev = dev_ptr;
   return MK_OK;
 }
+// the same offset for the LoRA dropout of lora.hip
+const uint64_t* mk_dropout_seed_dev() { return g_seed_dev; }
 
 namespace {
 template <typename T>

@@ -251,6 +251,53 @@ def _c2(x: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
 
 
 # =========================================================================
+# LoRA adapters of a decoder layer (macaw_llm_amd/lora.py, csrc/lora.hip)
+# =========================================================================
+LORA_MODULES = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+# the four groups of projections that share an input: name, members (indices into LORA_MODULES)
+LORA_GROUPS = (("qkv", (0, 1, 2)), ("o", (3,)), ("gu", (4, 5)), ("down", (6,)))
+
+
+class LoraSpec:
+    """what LlamaLayerFn needs to know about one layer's adapters: `mods` = the targeted indices into
+    LORA_MODULES (their (A, B) tensors follow as trailing arguments, in this order), the scaling
+    s = lora_alpha / r, the dropout probability of this call (0 outside training), the step's seed and the
+    layer index (the high bits of the mask's hash index: tag = 8 * layer + module)"""
+    __slots__ = ("mods", "s", "p", "seed", "layer")
+
+    def __init__(self, mods, s, p, seed, layer):
+        self.mods, self.s, self.p, self.seed, self.layer = tuple(mods), float(s), float(p), int(seed), int(layer)
+
+    def groups(self, ab):
+        """[(group name, [(module index, A, B)])] for the groups with at least one adapter"""
+        at = {m: (ab[2 * i], ab[2 * i + 1]) for i, m in enumerate(self.mods)}
+        out = []
+        for name, members in LORA_GROUPS:
+            g = [(m, *at[m]) for m in members if m in at]
+            if g:
+                out.append((name, g))
+        return out
+
+    def tags(self, g):
+        return [8 * self.layer + m for m, _, _ in g]
+
+
+def _lora_fwd(spec, g, x, ys):
+    """U = drop(x) A^T for the group, then ys_i += s U_i B_i^T; returns Ut (saved for the backward)"""
+    U, Ut = ops.lora_down(x, [A for _, A, _ in g], spec.p, spec.seed, spec.tags(g))
+    ops.lora_up_add_(U, [B for _, _, B in g], ys, spec.s)
+    return Ut
+
+
+def _lora_bwd(spec, g, x, Ut, dys, dx, grads):
+    """dB_i, dA_i of the group into grads[module], dx += the adapters' grad-input"""
+    dU, dUt, dB = ops.lora_bwd_dy(dys, [B for _, _, B in g], Ut, spec.s)
+    dA = ops.lora_bwd_x_(x, dU, dUt, [A for _, A, _ in g], dx, spec.p, spec.seed, spec.tags(g))
+    for (m, _, _), a, b in zip(g, dA, dB):
+        grads[m] = (a, b)
+
+
+# =========================================================================
 # LLaMA decoder layer  (modeling.py:234-299)
 # =========================================================================
 class LlamaLayerFn(torch.autograd.Function):
@@ -262,13 +309,17 @@ class LlamaLayerFn(torch.autograd.Function):
 
     @staticmethod
     def _fwd(x2, B, S, kmask, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu, wd, ln1, ln2, wqkv,
-             wgu, grad_mode):
+             wgu, grad_mode, lora=None, ab=()):
         """the layer's forward on [M, D] rows; returns (out, intermediates the backward needs).
         Deterministic (fixed reduction orders everywhere), so calling it again in the backward
         of a checkpointed layer reproduces the intermediates bit for bit."""
         M, D = x2.shape
         H, hd = n_heads, D // n_heads
         FF = wg.shape[0]
+        lg = dict(lora.groups(ab)) if lora is not None else {}
+        lut = {}       # group -> Ut of its adapters (the backward's dB needs it)
+        if lg and any(FP8.values()):
+            raise NotImplementedError("LoRA adapters cannot be combined with the fp8 switches (MM_LLMs.set_fp8)")
         fp8_qkv = (wqkv is not None and FP8["qkv"] and x2.is_contiguous() and x2.shape[1] <= 16384 and _fp8_ok(x2, wqkv))
         if fp8_qkv:      # (y1's e4m3 image and row scales leave the RMSNorm kernel with it: one pass over the row)
             _, y1, rstd1, y1q, y1s = ops.rmsnorm_fwd_fp8(x2, ln1, eps)
@@ -288,11 +339,15 @@ class LlamaLayerFn(torch.autograd.Function):
                 qkv = ops.linear_fwd(y1, wqkv)                # [M, 3D]
             q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
             ldq = 3 * D
+            if "qkv" in lg:        # (the adapters see q, k before the rotation, as in peft)
+                lut["qkv"] = _lora_fwd(lora, lg["qkv"], y1, [(q, k, v)[m] for m, _, _ in lg["qkv"]])
             if rope_in is None:
                 ops.rope_(qkv[:, :2 * D], cos, sin, pos, 2 * H, hd)   # q and k heads in one launch
         else:
             q, k, v = ops.linear_fwd(y1, wq), ops.linear_fwd(y1, wk), ops.linear_fwd(y1, wv)
             ldq = D
+            if "qkv" in lg:
+                lut["qkv"] = _lora_fwd(lora, lg["qkv"], y1, [(q, k, v)[m] for m, _, _ in lg["qkv"]])
             if rope_in is None:
                 ops.rope_(q, cos, sin, pos, H, hd)
                 ops.rope_(k, cos, sin, pos, H, hd)
@@ -309,20 +364,31 @@ class LlamaLayerFn(torch.autograd.Function):
                                      TDesc(v, ldq, S * ldq), TDesc(att, D, S * D), B, H, S, S, hd,
                                      1.0 / math.sqrt(hd), kmask=kmask, causal=True)
         h1 = ops.linear_fwd(att, wo, residual=x2)
+        if "o" in lg:
+            lut["o"] = _lora_fwd(lora, lg["o"], att, [h1])
         _, y2, rstd2 = ops.rmsnorm_fwd(h1, ln2, eps)
         fp8_mlp = FP8["mlp"] and wgu is not None and _fp8_ok(y2, wgu) and _fp8_dx_ok(y2, wd)
         if wgu is not None:
             gu = _fp8_linear(y2, wgu) if fp8_mlp else ops.linear_fwd(y2, wgu)     # [M, 2FF] = [gate | up]
+            if "gu" in lg:
+                lut["gu"] = _lora_fwd(lora, lg["gu"], y2, [(gu[:, :FF], gu[:, FF:])[m - 4] for m, _, _ in lg["gu"]])
             a = ops.swiglu2d_fwd(gu, FF)
             g = u = None
         else:
             g, u = ops.linear_fwd(y2, wg), ops.linear_fwd(y2, wu)
+            if "gu" in lg:
+                lut["gu"] = _lora_fwd(lora, lg["gu"], y2, [(g, u)[m - 4] for m, _, _ in lg["gu"]])
             a = ops.swiglu_fwd(g, u)
             gu = None
         if wgu is not None and fp8_mlp and _fp8_ok(a, wd):
             out = _fp8_linear(a, wd, residual=h1)
         else:
             out = ops.linear_fwd(a, wd, residual=h1)
+        if "down" in lg:
+            lut["down"] = _lora_fwd(lora, lg["down"], a, [out])
+        if lora is not None:
+            return out, (rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a,
+                         *(lut.get(n) for n, _ in LORA_GROUPS)), ({"full": 2, "bwd": 3, "off": 1}[fuse] if use_flash else 0)
         # (the third value tells the backward what its fused kernel has to do: 1 = nothing, 2 = q, k unrotated, RoPE
         # inside the kernels; 3 = q, k rotated, dq / dk rotated back at the store)
         return out, (rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a), \
@@ -330,29 +396,34 @@ class LlamaLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, kmask, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu, wd, ln1, ln2,
-                wqkv=None, wgu=None, recompute=False):
+                wqkv=None, wgu=None, recompute=False, lora=None, *ab):
         """recompute=True is activation checkpointing (modeling.py:474-489): only the layer
         input is kept and the backward re-runs `_fwd` first (identical results, ~13 fewer saved
-        [M, *] tensors per layer)."""
+        [M, *] tensors per layer).  lora (LoraSpec) with ab = (A, B) of every targeted projection:
+        LoRA adapters (y += s drop(x) A^T B^T), whose gradients the backward returns."""
         B, S, D = x.shape
         M, H, hd = B * S, n_heads, D // n_heads
         x2 = _c2(x, M, D)
         grad_mode = any(ctx.needs_input_grad)
         out, inter, use_flash = LlamaLayerFn._fwd(x2, B, S, kmask, pos, cos, sin, n_heads, eps, wq, wk,
                                                   wv, wo, wg, wu, wd, ln1, ln2, wqkv, wgu,
-                                                  grad_mode and not recompute)
+                                                  grad_mode and not recompute, lora, ab)
         if grad_mode:
             ctx.recompute = bool(recompute)
             ctx.n_heads, ctx.eps = n_heads, eps
+            ctx.lora = lora
             if recompute:
                 inter = (None,) * len(inter)
             ctx.save_for_backward(x2, *inter, pos, cos, sin, wq, wk, wv, wo, wg, wu, wd, ln1, ln2,
-                                  kmask, wqkv, wgu)
+                                  kmask, wqkv, wgu, *ab)
             ctx.dims = (B, S, D, H, hd, use_flash, wg.shape[0])
         return out.view(B, S, D)
 
     @staticmethod
     def backward(ctx, dout):
+        lora = ctx.lora
+        if lora is not None:
+            return LlamaLayerFn._backward_lora(ctx, dout)
         (x2, rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a, pos, cos, sin, wq, wk, wv,
          wo, wg, wu, wd, ln1, ln2, kmask, wqkv, wgu) = ctx.saved_tensors
         B, S, D, H, hd, use_flash, FF = ctx.dims
@@ -361,6 +432,43 @@ class LlamaLayerFn(torch.autograd.Function):
             _, (rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a), use_flash = LlamaLayerFn._fwd(
                 x2, B, S, kmask, pos, cos, sin, ctx.n_heads, ctx.eps, wq, wk, wv, wo, wg, wu, wd, ln1,
                 ln2, wqkv, wgu, True)
+        return LlamaLayerFn._backward_body(ctx, dout, x2, rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a,
+                                           pos, cos, sin, wq, wk, wv, wo, wg, wu, wd, ln1, ln2, kmask, wqkv, wgu,
+                                           B, S, D, H, hd, use_flash, FF, M)
+
+    @staticmethod
+    def _backward_lora(ctx, dout):
+        n_ab = 2 * len(ctx.lora.mods)
+        saved = ctx.saved_tensors
+        ab = saved[len(saved) - n_ab:]
+        (x2, rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a, ut_qkv, ut_o, ut_gu, ut_down, pos, cos, sin,
+         wq, wk, wv, wo, wg, wu, wd, ln1, ln2, kmask, wqkv, wgu) = saved[:len(saved) - n_ab]
+        B, S, D, H, hd, use_flash, FF = ctx.dims
+        M = B * S
+        if ctx.recompute:       # (same seed, same masks: U and the dropout are reproduced bit for bit)
+            _, (rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a, ut_qkv, ut_o, ut_gu, ut_down), use_flash = \
+                LlamaLayerFn._fwd(x2, B, S, kmask, pos, cos, sin, ctx.n_heads, ctx.eps, wq, wk, wv, wo, wg, wu, wd, ln1,
+                                  ln2, wqkv, wgu, True, ctx.lora, ab)
+        lut = {"qkv": ut_qkv, "o": ut_o, "gu": ut_gu, "down": ut_down}
+        grads = {}
+        res = LlamaLayerFn._backward_body(ctx, dout, x2, rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a,
+                                          pos, cos, sin, wq, wk, wv, wo, wg, wu, wd, ln1, ln2, kmask, wqkv, wgu,
+                                          B, S, D, H, hd, use_flash, FF, M, (ctx.lora, ab, lut, grads))
+        need = ctx.needs_input_grad
+        extra = []
+        for i, m in enumerate(ctx.lora.mods):
+            dA, dB = grads[m]
+            extra += [dA if need[20 + 2 * i] else None, dB if need[21 + 2 * i] else None]
+        return (*res, None, *extra)
+
+    @staticmethod
+    def _backward_body(ctx, dout, x2, rstd1, y1, q, k, v, probs, att, h1, rstd2, y2, g, u, gu, a, pos, cos, sin, wq, wk,
+                       wv, wo, wg, wu, wd, ln1, ln2, kmask, wqkv, wgu, B, S, D, H, hd, use_flash, FF, M, lo=None):
+        if lo is not None:
+            lora, ab, lut, grads = lo
+            lg = dict(lora.groups(ab))
+        else:
+            lg = {}
         need = ctx.needs_input_grad
         dout2 = _c2(dout, M, D)
         sd = _DwSide(x2.device, M, D)
@@ -369,12 +477,17 @@ class LlamaLayerFn(torch.autograd.Function):
         ev = sd.fork()
         da = _fp8_dx(dout2, wd) if fp8_mlp else ops.linear_dx(dout2, wd)
         dwd = sd.dw(ev, dout2, a, wd, "down") if need[13] else None
+        if "down" in lg:
+            _lora_bwd(lora, lg["down"], a, lut["down"], [dout2], da, grads)
         dwg = dwu = None
         if gu is not None:
             dgu = ops.swiglu2d_bwd(gu, da, FF)
             del da
             ev = sd.fork()
             dy2 = _fp8_dx(dgu, wgu) if (fp8_mlp and _fp8_dx_ok(dgu, wgu)) else ops.linear_dx(dgu, wgu)
+            if "gu" in lg:
+                _lora_bwd(lora, lg["gu"], y2, lut["gu"], [(dgu[:, :FF], dgu[:, FF:])[m - 4] for m, _, _ in lg["gu"]],
+                          dy2, grads)
             if need[11] or need[12]:
                 dwgu = sd.dw(ev, dgu, y2, wgu, "gu")             # [2FF, D]
                 dwg, dwu = dwgu[:FF], dwgu[FF:]
@@ -384,6 +497,8 @@ class LlamaLayerFn(torch.autograd.Function):
             del da
             dy2 = ops.linear_dx(dg, wg)
             ops.linear_dx(du, wu, out=dy2, accumulate=True)
+            if "gu" in lg:
+                _lora_bwd(lora, lg["gu"], y2, lut["gu"], [(dg, du)[m - 4] for m, _, _ in lg["gu"]], dy2, grads)
             dwg = ops.linear_dw(dg, y2) if need[11] else None
             dwu = ops.linear_dw(du, y2) if need[12] else None
             del dg, du
@@ -392,6 +507,8 @@ class LlamaLayerFn(torch.autograd.Function):
         ev = sd.fork()
         datt = ops.linear_dx(dh1, wo)
         dwo = sd.dw(ev, dh1, att, wo, "o") if need[10] else None
+        if "o" in lg:
+            _lora_bwd(lora, lg["o"], att, lut["o"], [dh1], datt, grads)
         ldq = q.stride(0)
         if wqkv is not None:
             dqkv = torch.empty((M, 3 * D), dtype=q.dtype, device=q.device)
@@ -416,12 +533,15 @@ class LlamaLayerFn(torch.autograd.Function):
             ops.rope_(dq, cos, sin, pos, H, hd, inverse=True)
             ops.rope_(dk, cos, sin, pos, H, hd, inverse=True)
         dwq = dwk = dwv = None
+        lora_qkv = lg.get("qkv")
         if wqkv is not None:
             ev = sd.fork()
             if FP8["qkv"] and _fp8_dx_ok(dqkv, wqkv) and _fp8_ok(y1, wqkv):
                 dy1 = _fp8_dx(dqkv, wqkv)                      # e4m3 dy x e4m3 W^T (cfg 5)
             else:
                 dy1 = ops.linear_dx(dqkv, wqkv)
+            if lora_qkv:
+                _lora_bwd(lora, lora_qkv, y1, lut["qkv"], [(dq, dk, dv)[m] for m, _, _ in lora_qkv], dy1, grads)
             if need[7] or need[8] or need[9]:
                 dwqkv = sd.dw(ev, dqkv, y1, wqkv, "qkv")          # [3D, D]
                 dwq, dwk, dwv = dwqkv[:D], dwqkv[D:2 * D], dwqkv[2 * D:]
@@ -429,6 +549,8 @@ class LlamaLayerFn(torch.autograd.Function):
             dy1 = ops.linear_dx(dq, wq)
             ops.linear_dx(dk, wk, out=dy1, accumulate=True)
             ops.linear_dx(dv, wv, out=dy1, accumulate=True)
+            if lora_qkv:
+                _lora_bwd(lora, lora_qkv, y1, lut["qkv"], [(dq, dk, dv)[m] for m, _, _ in lora_qkv], dy1, grads)
             dwq = ops.linear_dw(dq, y1) if need[7] else None
             dwk = ops.linear_dw(dk, y1) if need[8] else None
             dwv = ops.linear_dw(dv, y1) if need[9] else None

@@ -19,7 +19,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "libmacaw_hip.so"
 
 MK_F32, MK_BF16, MK_F16, MK_FP8 = 0, 1, 2, 3
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _ERR = {-1: "MK_ERR_BAD_ARG", -2: "MK_ERR_UNSUPPORTED", -3: "MK_ERR_LAUNCH"}
 
@@ -119,6 +119,14 @@ SIGNATURES = {
     "mk_fp8_quantize_cols_t": [_vp, _i32, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
     "mk_image_transform": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp],
     "mk_log_mel": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
+    "mk_lora_workspace": [_i32, _i32, _i32, _i32, _vp],
+    "mk_lora_down": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _f32, _u64, _vp, _i32, _vp],
+    "mk_lora_up_add": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp],
+    "mk_lora_bwd_dy": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp,
+                       _vp, _vp, _i64, _i32, _vp],
+    "mk_lora_bwd_x": [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp, _vp, _i64, _vp,
+                      _vp, _vp, _vp, _i64, _i32, _vp],
+    "mk_lora_merge": [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _f32, _vp, _i64, _i32, _vp],
 }
 
 _lib = None

@@ -270,11 +270,21 @@ class LlamaDecoderLayer(nn.Module):
         wqkv, wgu = self.fused_weights()
         cos, sin = a.rotary_emb.tables(hidden_states.shape[1], hidden_states.dtype,
                                        hidden_states.device)
+        lora = ()
+        st = getattr(self, "_lora_state", None)
+        if st is not None:          # LoRA adapters (macaw_llm_amd/lora.py): their (A, B) follow as trailing inputs
+            from .lora import layer_adapters
+            ad = layer_adapters(self)
+            if ad:
+                cfg = st.config
+                spec = eng.LoraSpec([i for i, _ in ad], cfg.scaling, cfg.lora_dropout if self.training else 0.0,
+                                    st.seed, self._lora_layer)
+                lora = (spec, *[t for _, lin in ad for t in (lin.lora_A.weight, lin.lora_B.weight)])
         out = eng.LlamaLayerFn.apply(
             hidden_states, kmask, pos, cos, sin, a.num_heads, self.input_layernorm.variance_epsilon,
             a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight,
             m.up_proj.weight, m.down_proj.weight, self.input_layernorm.weight,
-            self.post_attention_layernorm.weight, wqkv, wgu, recompute)
+            self.post_attention_layernorm.weight, wqkv, wgu, recompute, *lora)
         return (out,)
 
 
@@ -418,6 +428,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, labels=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None):
+        st = getattr(self, "_lora", None)
+        if st is not None:
+            st.begin_step(self.training)
         self.model._defer_final_norm = True
         try:
             h = self.model(input_ids=input_ids, attention_mask=attention_mask,
@@ -548,17 +561,29 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         cos, sin = rot.tables(Tmax, dtype, dev)
         kvc = [torch.empty((B, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]   # [keys | values]
 
+        if getattr(self, "_lora", None) is not None:
+            # LoRA adapters: the decode path runs on MERGED copies of the adapted weights (W + s B A, csrc/lora.hip),
+            # made once for this call and dropped at its end -- temporarily one extra copy of every adapted
+            # projection (all seven of a 7B layer: 0.4 GB bf16 per layer, 12.9 GB for 32 layers)
+            from .lora import lora_layers, merged_layer_weights
+            merged = dict(merged_layer_weights(self, lyr) for _, lyr in lora_layers(self))
+        else:
+            merged = {}
+
         def run(x2, Sn, t0, pos=None, t_dev=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
             for i, lyr in enumerate(layers):
                 a, m = lyr.self_attn, lyr.mlp
+                if lyr in merged:
+                    ws = merged[lyr]
+                else:
+                    ws = (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight,
+                          m.up_proj.weight, m.down_proj.weight, *lyr.fused_weights())
                 x2 = eng.llama_layer_cached(
                     x2, B, Sn, t0, kvc[i], Tmax, pos, cos, sin, a.num_heads,
-                    lyr.input_layernorm.variance_epsilon, a.q_proj.weight, a.k_proj.weight,
-                    a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight, m.up_proj.weight,
-                    m.down_proj.weight, lyr.input_layernorm.weight,
-                    lyr.post_attention_layernorm.weight, *lyr.fused_weights(), t_dev=t_dev)
+                    lyr.input_layernorm.variance_epsilon, *ws[:7], lyr.input_layernorm.weight,
+                    lyr.post_attention_layernorm.weight, *ws[7:], t_dev=t_dev)
             return x2
 
         h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)                 # prefill
@@ -740,6 +765,9 @@ class MM_LLMs(PreTrainedModel):
     def forward(self, inputs=None):
         _dtype_check(self._param_dtype())
         text_embeddings, attention_mask, labels = self.prepare_inputs_for_generation(inputs)
+        lora = getattr(self.llm, "_lora", None)
+        if lora is not None:        # the adapters' dropout follows this model's step seeds (slot 41)
+            lora.ext_seed = self._dropout_seed(lora.SLOT)
         if "inference" in inputs and inputs["inference"] is True:
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006)

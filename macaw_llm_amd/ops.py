@@ -804,3 +804,81 @@ def prof_end():
     ms, fl, n = C.c_double(0), C.c_double(0), C.c_int64(0)
     _L.check(_L.load().mk_prof_end(C.byref(ms), C.byref(fl), C.byref(n)), "mk_prof_end")
     return ms.value, fl.value, n.value
+
+
+# ------------------------------------------------------------------- LoRA --
+# csrc/lora.hip: the rank-r products of the adapters (macaw_llm_amd/lora.py).  A GROUP is 1-3 modules sharing
+# one input (q|k|v, gate|up); U / dU are [M, G r] in the activation dtype, Ut / dUt their transposes with a
+# pitch of pad8(M).  Launch kind 4 of the in-library profiler.
+PROF_LORA = 4
+
+
+def _ptrs3(ts):
+    return [_p(t) for t in ts] + [None] * (3 - len(ts))
+
+
+def _tags(tags, G):
+    return (C.c_uint64 * 3)(*(list(tags or []) + [0] * (3 - len(tags or []))))
+
+
+def lora_workspace(M, N, G, r, device):
+    b = C.c_int64(0)
+    _L.check(_L.load().mk_lora_workspace(M, N, G, r, C.byref(b)), "mk_lora_workspace")
+    return torch.empty(b.value, dtype=torch.uint8, device=device)
+
+
+def lora_down(x, As, p=0.0, seed=0, tags=None):
+    """U[:, i r:(i+1) r] = drop_i(x) A_i^T for the group As ([r, K] each); returns (U, Ut)"""
+    M, K = x.shape
+    G, r = len(As), As[0].shape[0]
+    U = torch.empty((M, G * r), dtype=x.dtype, device=x.device)
+    Ut = torch.empty((G * r, pad8(M)), dtype=x.dtype, device=x.device)
+    _L.check(_L.load().mk_lora_down(_p(x), _rowmajor(x), M, K, *_ptrs3(As), G, r, _p(U), _p(Ut), Ut.shape[1],
+                                    float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _tags(tags, G), dt(x), _st()),
+             "mk_lora_down")
+    return U, Ut
+
+
+def lora_up_add_(U, Bs, Ys, s):
+    """Y_i += s U_i B_i^T in place (Ys: [M, N] views sharing one pitch)"""
+    M, N = Ys[0].shape
+    G, r = len(Bs), Bs[0].shape[1]
+    _L.check(_L.load().mk_lora_up_add(_p(U), M, r, G, *_ptrs3(Bs), *_ptrs3(Ys), _rowmajor(Ys[0]), N, float(s), dt(U),
+                                      _st()), "mk_lora_up_add")
+
+
+def lora_bwd_dy(dYs, Bs, Ut, s):
+    """(dU, dUt, [dB_i]) with dU = s dY_i B_i, dB_i = s dY_i^T U_i"""
+    M, N = dYs[0].shape
+    G, r = len(Bs), Bs[0].shape[1]
+    dev, dtype = dYs[0].device, dYs[0].dtype
+    dU = torch.empty((M, G * r), dtype=dtype, device=dev)
+    dUt = torch.empty((G * r, pad8(M)), dtype=dtype, device=dev)
+    dB = [torch.empty((N, r), dtype=dtype, device=dev) for _ in range(G)]
+    ws = lora_workspace(M, N, G, r, dev)
+    _L.check(_L.load().mk_lora_bwd_dy(*_ptrs3(dYs), _rowmajor(dYs[0]), M, N, *_ptrs3(Bs), _p(Ut), Ut.shape[1], G, r,
+                                      float(s), _p(dU), _p(dUt), *_ptrs3(dB), _p(ws), ws.numel(), dt(dU), _st()),
+             "mk_lora_bwd_dy")
+    return dU, dUt, dB
+
+
+def lora_bwd_x_(x, dU, dUt, As, dx, p=0.0, seed=0, tags=None):
+    """dx += sum_i drop'_i(dU_i A_i) in place; returns [dA_i] with dA_i = dU_i^T drop_i(x)"""
+    M, K = x.shape
+    G, r = len(As), As[0].shape[0]
+    dA = [torch.empty((r, K), dtype=x.dtype, device=x.device) for _ in range(G)]
+    ws = lora_workspace(M, K, G, r, x.device)
+    _L.check(_L.load().mk_lora_bwd_x(_p(x), _rowmajor(x), M, K, _p(dU), _p(dUt), dUt.shape[1], *_ptrs3(As), G, r,
+                                     float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _tags(tags, G), _p(dx), _rowmajor(dx),
+                                     *_ptrs3(dA), _p(ws), ws.numel(), dt(x), _st()), "mk_lora_bwd_x")
+    return dA
+
+
+def lora_merge_(W, A, B, s):
+    """W += s B A (fp32 product, one rounding) in place"""
+    N, K = W.shape
+    r = A.shape[0]
+    ws = lora_workspace(1, K, 1, r, W.device)
+    _L.check(_L.load().mk_lora_merge(_p(W), _rowmajor(W), N, K, _p(A), _p(B), r, float(s), _p(ws), ws.numel(), dt(W),
+                                     _st()), "mk_lora_merge")
+    return W
