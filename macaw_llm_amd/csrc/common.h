@@ -52,6 +52,14 @@ template <typename T> MK_DEV float to_f32(T v);
 template <> MK_DEV float to_f32<float>(float v) { return v; }
 template <> MK_DEV float to_f32<bf16>(bf16 v) { return (float)v; }
 template <> MK_DEV float to_f32<_Float16>(_Float16 v) { return (float)v; }
+// torch.argmax order of the candidates (value, column) of one row: a NaN ranks above every number
+// (the first NaN wins), then the larger value, ties to the lower column.  Starting from (-inf,
+// INT_MAX), a row of -inf therefore selects its first column, as torch.argmax does.
+MK_DEV bool mk_argmax_better(float v, int i, float best, int bi) {
+  const bool vn = __builtin_isnan(v), bn = __builtin_isnan(best);
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > best || (v == best && i < bi);
+}
 template <typename T> MK_DEV T from_f32(float v);
 template <> MK_DEV float from_f32<float>(float v) { return v; }
 template <> MK_DEV bf16 from_f32<bf16>(float v) { return (bf16)v; }  // RNE (v_cvt_pk_bf16_f32)

@@ -43,20 +43,22 @@ __global__ __launch_bounds__(1024) void decode_emit_kernel(const T* logits, long
       v[j] = c < V ? (float)xr[c] : -INFINITY;
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (v[j] > best) { best = v[j]; idx = c0 + j * 1024; }      // ascending columns: first maximum
+    for (int j = 0; j < 8; ++j) {                                 // torch.argmax order (common.h)
+      const int c = c0 + j * 1024;
+      if (c < V && mk_argmax_better(v[j], c, best, idx)) { best = v[j]; idx = c; }
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(idx, o, 64);
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    if (mk_argmax_better(ov, oi, best, idx)) { best = ov; idx = oi; }
   }
   if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 16; ++w)
-      if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+      if (mk_argmax_better(bv[w], bi[w], best, idx)) { best = bv[w]; idx = bi[w]; }
     const int col = state[1];
     const long nxt = done[b] ? pad : (long)idx;
     out[(long)b * out_ld + col] = nxt;

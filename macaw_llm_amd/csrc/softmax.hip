@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* logits, T* dlogits
 
 // --------------------------------------------------------------- argmax ----
 // Greedy token selection (HF greedy_search, modeling.py:959): index of the first maximum of
-// every row; fp32 compare, ties -> lowest index (torch.argmax semantics).
+// every row; fp32 compare in torch.argmax order (mk_argmax_better: first NaN, else first maximum).
 template <typename T>
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* x, long ld, int cols,
                                                           int64_t* out) {
@@ -309,19 +309,19 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* x, long ld, i
   int idx = 0x7fffffff;
   for (int c = threadIdx.x; c < cols; c += 256) {
     const float v = to_f32<T>(xr[c]);
-    if (v > best || (v == best && c < idx)) { best = v; idx = c; }
+    if (mk_argmax_better(v, c, best, idx)) { best = v; idx = c; }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(idx, o, 64);
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    if (mk_argmax_better(ov, oi, best, idx)) { best = ov; idx = oi; }
   }
   if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w)
-      if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+      if (mk_argmax_better(bv[w], bi[w], best, idx)) { best = bv[w]; idx = bi[w]; }
     out[row] = idx;
   }
 }

@@ -1228,25 +1228,28 @@ def test_adamw_unaligned_slice_and_param_groups(dev):
         FusedAdamW([ps]).step()
 
 
+DECODE_ATTN_SHAPES = [(128, 32, 1, 173), (128, 4, 3, 1), (64, 8, 2, 64), (32, 4, 2, 333), (16, 4, 3, 40)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("hd,H,B,T", [(128, 32, 1, 173), (128, 4, 3, 1), (64, 8, 2, 64), (32, 4, 2, 333), (16, 4, 3, 40)])
-def test_decode_attn_and_kv_append_with_device_position(hd, H, B, T):
+@pytest.mark.parametrize("hd,H,B,T", DECODE_ATTN_SHAPES)
+def test_decode_attn_and_kv_append_with_device_position(hd, H, B, T, dtype=torch.bfloat16):
     """mk_kv_append / mk_decode_attn read the position from device memory: one query row per
     (sample, head) against the first T cached keys, fp32 reference"""
     from macaw_llm_amd import ops
     dev = torch.device("cuda:0")
     torch.manual_seed(hd + T)
     D, Tmax = H * hd, T + 7
-    cache = torch.zeros((B, Tmax, 2 * D), dtype=torch.bfloat16, device=dev)
-    cache[:, : T - 1] = torch.randn((B, T - 1, 2 * D), device=dev).to(torch.bfloat16)
-    qkv = torch.randn((B, 3 * D), device=dev).to(torch.bfloat16)
+    cache = torch.zeros((B, Tmax, 2 * D), dtype=dtype, device=dev)
+    cache[:, : T - 1] = torch.randn((B, T - 1, 2 * D), device=dev).to(dtype)
+    qkv = torch.randn((B, 3 * D), device=dev).to(dtype)
     t_dev = torch.tensor([T - 1], dtype=torch.int32, device=dev)
     before = cache.clone()
     ops.kv_append(qkv, cache, 2 * D, B, 3 * D, Tmax * 2 * D, 2 * D, t_dev, Tmax, src_off=D)
     assert torch.equal(cache[:, T - 1], qkv[:, D:])
     before[:, T - 1] = qkv[:, D:]
     assert torch.equal(cache, before)                     # nothing else touched
-    out = torch.empty((B, D), dtype=torch.bfloat16, device=dev)
+    out = torch.empty((B, D), dtype=dtype, device=dev)
     scale = 1.0 / hd ** 0.5
     ops.decode_attn(qkv, cache, cache, out, t_dev, 1, Tmax, B, H, hd, 3 * D, 2 * D, Tmax * 2 * D, 2 * D,
                     Tmax * 2 * D, D, scale, v_off=D)
@@ -1263,12 +1266,15 @@ def test_decode_attn_and_kv_append_with_device_position(hd, H, B, T):
     assert torch.allclose(out.float(), cache[:, 0, D:].float(), atol=1e-6)   # one key: output = its value
 
 
+DECODE_STEP_SHAPES = [(128, 32, 1, 173), (128, 4, 2, 1), (64, 8, 2, 65), (32, 4, 2, 300), (16, 4, 3, 40),
+                      # B x H >= 512: the four-heads-per-workgroup kernel (first position, one trip, several trips
+                      # with a ragged last one)
+                      (128, 32, 16, 1), (128, 32, 32, 150), (128, 32, 17, 139), (128, 64, 8, 7)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("hd,H,B,T", [(128, 32, 1, 173), (128, 4, 2, 1), (64, 8, 2, 65), (32, 4, 2, 300), (16, 4, 3, 40),
-                                      # B x H >= 512: the four-heads-per-workgroup kernel (first position, one
-                                      # trip, several trips with a ragged last one)
-                                      (128, 32, 16, 1), (128, 32, 32, 150), (128, 32, 17, 139), (128, 64, 8, 7)])
-def test_decode_step_attn_equals_rope_append_attention(hd, H, B, T):
+@pytest.mark.parametrize("hd,H,B,T", DECODE_STEP_SHAPES)
+def test_decode_step_attn_equals_rope_append_attention(hd, H, B, T, dtype=torch.bfloat16):
     """mk_decode_step_attn = mk_rope (q and k heads) + cache append + attention over keys 0 ... p with
     p read from device memory: rotated key / value rows bit-identical to the separate kernels, output
     against an fp32 reference"""
@@ -1276,12 +1282,12 @@ def test_decode_step_attn_equals_rope_append_attention(hd, H, B, T):
     dev = torch.device("cuda:0")
     torch.manual_seed(3 * hd + T)
     D, Tmax, p = H * hd, T + 5, T - 1
-    cache = torch.zeros((B, Tmax, 2 * D), dtype=torch.bfloat16, device=dev)
-    cache[:, :p] = torch.randn((B, p, 2 * D), device=dev).to(torch.bfloat16)
-    qkv = torch.randn((B, 3 * D), device=dev).to(torch.bfloat16)
+    cache = torch.zeros((B, Tmax, 2 * D), dtype=dtype, device=dev)
+    cache[:, :p] = torch.randn((B, p, 2 * D), device=dev).to(dtype)
+    qkv = torch.randn((B, 3 * D), device=dev).to(dtype)
     inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2).float() / hd))
     ang = torch.cat((torch.outer(torch.arange(Tmax).float(), inv),) * 2, dim=-1)
-    cos, sin = ang.cos().to(dev).to(torch.bfloat16), ang.sin().to(dev).to(torch.bfloat16)
+    cos, sin = ang.cos().to(dev).to(dtype), ang.sin().to(dev).to(dtype)
     t_dev = torch.tensor([p], dtype=torch.int32, device=dev)
     # separate kernels
     ref_qkv = qkv.clone()
@@ -1289,7 +1295,7 @@ def test_decode_step_attn_equals_rope_append_attention(hd, H, B, T):
     ops.rope_(ref_qkv[:, :2 * D], cos, sin, pos, 2 * H, hd)
     want_cache = cache.clone()
     want_cache[:, p] = ref_qkv[:, D:]
-    out = torch.empty((B, D), dtype=torch.bfloat16, device=dev)
+    out = torch.empty((B, D), dtype=dtype, device=dev)
     scale = 1.0 / hd ** 0.5
     ops.decode_step_attn(qkv, qkv, qkv, 3 * D, cos, sin, cache, t_dev, Tmax, B, H, hd, out, scale,
                          k_off=D, v_off=2 * D)
@@ -1302,24 +1308,30 @@ def test_decode_step_attn_equals_rope_append_attention(hd, H, B, T):
     assert err <= 2e-2 * max(1.0, ref.abs().max().item()), err
 
 
+DECODE_LINEAR_SHAPES = [(1, 12288, 4096), (3, 4096, 4096), (16, 520, 704), (4, 32007, 4096), (1, 4096, 11008),
+                        (1, 1001, 704), (1, 32007, 5120), (1, 5120, 13824)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("M,N,K", [(1, 12288, 4096), (3, 4096, 4096), (16, 520, 704), (4, 32007, 4096), (1, 4096, 11008),
-                                   (1, 1001, 704), (1, 32007, 5120), (1, 5120, 13824)])
-def test_decode_linear_prologues_match_the_separate_kernels(M, N, K):
+@pytest.mark.parametrize("M,N,K", DECODE_LINEAR_SHAPES + [(24, 4096, 4096)])   # 24 rows: plain only (prologues <= 16)
+def test_decode_linear_prologues_match_the_separate_kernels(M, N, K, dtype=torch.bfloat16):
     """mk_decode_linear with the RMSNorm / SwiGLU prologue against rmsnorm_fwd / swiglu2d_fwd followed
     by the plain linear (same rounding points: the results may differ only through the order of the
     fp32 sum of squares), and against fp32 math"""
     from macaw_llm_amd import ops
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(M + N + K)
-    x = _rand((M, K), torch.bfloat16, g).to(dev)
-    W = (_rand((N, K), torch.bfloat16, g).float() * 0.05).to(torch.bfloat16).to(dev)
-    res = _rand((M, N), torch.bfloat16, g).to(dev)
-    nw = (1.0 + 0.1 * _rand((K,), torch.float32, g)).to(torch.bfloat16).to(dev)
+    x = _rand((M, K), dtype, g).to(dev)
+    W = (_rand((N, K), dtype, g).float() * 0.05).to(dtype).to(dev)
+    res = _rand((M, N), dtype, g).to(dev)
+    nw = (1.0 + 0.1 * _rand((K,), torch.float32, g)).to(dtype).to(dev)
     # plain
     y0 = ops.decode_linear(x, W, residual=res)
-    _close(y0, x.float().cpu() @ W.float().cpu().t() + res.float().cpu(), torch.bfloat16, scale=math.sqrt(K) * 0.05 + 1.0,
+    _close(y0, x.float().cpu() @ W.float().cpu().t() + res.float().cpu(), dtype, scale=math.sqrt(K) * 0.05 + 1.0,
            what="decode_linear plain")
+    if not ops.decode_linear_ok(x, W, 1):                       # 17 ... 32 rows: the plain form only
+        assert M > 16 and ops.decode_linear_ok(x, W, 0)
+        return
     # RMSNorm prologue
     _, yn, _ = ops.rmsnorm_fwd(x, nw, 1e-6)
     want = ops.linear_fwd(yn, W)
@@ -1328,7 +1340,7 @@ def test_decode_linear_prologues_match_the_separate_kernels(M, N, K):
     assert d <= 0.02 * want.float().abs().max().item() + 1e-3, d
     assert (got == want).float().mean().item() > 0.98           # a differing rstd ulp flips few roundings
     # SwiGLU prologue: x2 = [gate | up]
-    gu = _rand((M, 2 * K), torch.bfloat16, g).to(dev)
+    gu = _rand((M, 2 * K), dtype, g).to(dev)
     a = ops.swiglu2d_fwd(gu, K)
     want = ops.linear_fwd(a, W, residual=res)
     got = ops.decode_linear(gu, W, 2, residual=res)
@@ -1336,29 +1348,57 @@ def test_decode_linear_prologues_match_the_separate_kernels(M, N, K):
 
 
 @pytest.mark.gpu
-def test_decode_emit_argmax_pad_eos_and_step_state():
+def test_decode_emit_argmax_pad_eos_and_step_state(dtype=torch.bfloat16):
     """mk_decode_emit: first argmax per row, pad for finished samples, eos marks a sample finished,
     output column and position advance exactly once per launch"""
     from macaw_llm_amd import ops
     dev = torch.device("cuda:0")
     torch.manual_seed(5)
-    B, V, ld = 5, 32007, 32064
-    logits = torch.randn((B, ld), device=dev).to(torch.bfloat16)
+    B, V, ld = 7, 32007, 32064
+    logits = torch.randn((B, ld), device=dev).to(dtype)
     logits[:, V:] = 100.0                                   # pad columns must be ignored
     logits[1, 777] = logits[1, 20001] = 50.0                # tie: lowest index
     logits[2, 9] = 60.0                                     # will be eos
+    logits[5, :V] = float("-inf")                           # all -inf: torch.argmax gives column 0
+    logits[6, 3000] = logits[6, 30000] = float("nan")       # NaN: torch.argmax gives the first NaN
     tok = torch.zeros(B, dtype=torch.long, device=dev)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
     done[3] = True
     out = torch.full((B, 4), -1, dtype=torch.long, device=dev)
     state = torch.tensor([144, 1, 0, 0], dtype=torch.int32, device=dev)
     ops.decode_emit(logits, V, 106, 9, tok, done, out, state)
-    want = logits[:, :V].float().argmax(1)
+    want = logits[:, :V].float().cpu().argmax(1).to(dev)
+    assert want[5] == 0 and want[6] == 3000
     want[1] = 777
     want[3] = 106
     assert torch.equal(out[:, 1], want) and torch.equal(tok, want)
     assert torch.equal(out[:, 0], torch.full((B,), -1, device=dev)) and torch.equal(out[:, 2:], torch.full((B, 2), -1, device=dev))
-    assert done.tolist() == [False, False, True, True, False]
+    assert done.tolist() == [False, False, True, True, False, False, False]
     assert state.tolist() == [145, 2, 0, 0]
     ops.decode_emit(logits, V, 106, 9, tok, done, out, state)
     assert out[2, 2].item() == 106 and state.tolist() == [146, 3, 0, 0]
+
+
+# the fp16 instantiations of the four decode entry points (csrc/decode.hip, decode_impl.inc): generate() runs them for
+# fp16 models; same shapes and bounds as the bf16 tests above
+@pytest.mark.gpu
+@pytest.mark.parametrize("hd,H,B,T", DECODE_ATTN_SHAPES)
+def test_decode_attn_and_kv_append_with_device_position_fp16(hd, H, B, T):
+    test_decode_attn_and_kv_append_with_device_position(hd, H, B, T, torch.float16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hd,H,B,T", DECODE_STEP_SHAPES)
+def test_decode_step_attn_equals_rope_append_attention_fp16(hd, H, B, T):
+    test_decode_step_attn_equals_rope_append_attention(hd, H, B, T, torch.float16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,K", DECODE_LINEAR_SHAPES + [(24, 4096, 4096)])
+def test_decode_linear_prologues_match_the_separate_kernels_fp16(M, N, K):
+    test_decode_linear_prologues_match_the_separate_kernels(M, N, K, torch.float16)
+
+
+@pytest.mark.gpu
+def test_decode_emit_argmax_pad_eos_and_step_state_fp16():
+    test_decode_emit_argmax_pad_eos_and_step_state(torch.float16)

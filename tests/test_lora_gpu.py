@@ -59,10 +59,55 @@ CASES += [(shape, dtype, r, M, p) for shape in ("gu", "down") for dtype, r in ((
           for M, p in ((4600, 0.05), (4601, 0.05), (4608, 0.0))]
 
 
+# the rank-tile instantiations (RT = ceil(r / 16) = 1, 2, 4, 8: csrc/lora.hip rowred_launch / colred_launch) with ragged
+# ranks (r % 16 == 8: a half-used last tile), one partial row tile (M = 1, 9), a row tile past 16 (17), three LORA_SLAB
+# slabs of the dA / dB partials (1025), widths whose last 64- and 256-column blocks are cut (K = 1000, N = 1032) and the
+# 13B widths (5120 / 13824) at the largest rank
+WIDTHS = {"qkv": (4096, 4096, 3), "gu": (4096, 11008, 2), "down": (11008, 4096, 1), "odd": (1000, 1032, 3),
+          "odd2": (1032, 1000, 2), "qkv13": (5120, 5120, 3), "gu13": (5120, 13824, 2), "down13": (13824, 5120, 1)}
+RANK_CASES = [("qkv", torch.bfloat16, 24, 9, 0.05), ("qkv", torch.float16, 32, 1025, 0.0),
+              ("qkv", torch.bfloat16, 40, 17, 0.0), ("qkv", torch.float16, 72, 1, 0.05),
+              ("qkv", torch.bfloat16, 128, 1025, 0.05), ("gu", torch.float16, 24, 17, 0.0),
+              ("gu", torch.bfloat16, 72, 9, 0.05), ("gu", torch.bfloat16, 32, 1, 0.05),
+              ("down", torch.bfloat16, 40, 1025, 0.05), ("down", torch.float16, 128, 9, 0.0),
+              ("odd", torch.bfloat16, 72, 17, 0.05), ("odd", torch.float16, 24, 1025, 0.05),
+              ("odd", torch.bfloat16, 8, 1, 0.0), ("odd2", torch.float16, 40, 9, 0.0),
+              ("odd2", torch.bfloat16, 128, 17, 0.05), ("qkv13", torch.bfloat16, 128, 1025, 0.0),
+              ("gu13", torch.bfloat16, 128, 17, 0.05), ("down13", torch.float16, 128, 9, 0.05)]
+
+
+def _rank_tiles(r):
+    return (r + 15) // 16 if r <= 32 else 4 if r <= 64 else 8
+
+
+def test_lora_cases_select_every_rank_tile_instantiation():
+    """guard on the parametrization: every RT bucket, full and half-used last tile, both dtypes, dropout on / off, every
+    group shape and the M edges stay covered"""
+    cases = [(dtype, r, M, p, WIDTHS[shape][2]) for shape, dtype, r, M, p in RANK_CASES + CASES]
+    assert {_rank_tiles(c[1]) for c in cases} == {1, 2, 4, 8}
+    for rt in (1, 2, 4, 8):
+        rs = {c[1] for c in cases if _rank_tiles(c[1]) == rt}
+        assert any(r % 16 == 8 for r in rs) and any(r % 16 == 0 for r in rs), (rt, rs)
+        for dtype in (torch.bfloat16, torch.float16):
+            assert any(c[0] == dtype for c in cases if _rank_tiles(c[1]) == rt), (rt, dtype)
+        assert {c[3] > 0 for c in cases if _rank_tiles(c[1]) == rt} == {True, False}, rt
+    assert {c[4] for c in cases} == {1, 2, 3}
+    assert {1, 9, 17, 1025} <= {c[2] for c in cases}
+    assert any(K % 64 and N % 64 for K, N, _ in WIDTHS.values())
+    assert {WIDTHS[s][:2] for s, _, r, _, _ in RANK_CASES if r == 128} >= {(5120, 13824), (13824, 5120)}
+
+
 @pytest.mark.parametrize("shape,dtype,r,M,p", CASES)
 def test_lora_kernels_against_fp32_restatement(dev, shape, dtype, r, M, p):
-    D, FF = 4096, 11008
-    K, N, G = {"qkv": (D, D, 3), "gu": (D, FF, 2), "down": (FF, D, 1)}[shape]
+    _check_lora_kernels(dev, *WIDTHS[shape], dtype, r, M, p)
+
+
+@pytest.mark.parametrize("shape,dtype,r,M,p", RANK_CASES)
+def test_lora_kernels_every_rank_tile_and_edge(dev, shape, dtype, r, M, p):
+    _check_lora_kernels(dev, *WIDTHS[shape], dtype, r, M, p)
+
+
+def _check_lora_kernels(dev, K, N, G, dtype, r, M, p):
     g = torch.Generator(device=dev).manual_seed(r * 7 + M)
     s, seed, tags = 2.0, 123456789 + r, [8 * 5 + i for i in range(G)]
     x = _rand((M, K), dtype, dev, 1.0, g)
