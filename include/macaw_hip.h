@@ -328,6 +328,20 @@ int mk_argmax_rows(const void* x, int64_t ld, int32_t rows, int32_t cols, int64_
 int mk_decode_linear(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy,
                      const void* residual, int64_t ldr, int32_t M, int32_t N, int32_t K,
                      int32_t prologue, const void* norm_w, float eps, int32_t dtype, void* stream);
+/* mk_decode_linear_fp8: y[M][N] = prologue(x) (scale * Wq)^T (+ residual), mk_decode_linear with the weight
+ *   streamed as OCP e4m3 bytes (W8A16): Wq uint8 [N][K] row-major at pitch ldw BYTES, scale f32[N] one
+ *   de-quantisation scale per output channel (the pair mk_fp8_quantize_rows writes for a weight); x,
+ *   residual, y bf16 or f16 (dtype), fp32 accumulation.  A lane widens the bytes to the 16-bit type in
+ *   registers (exact, subnormals included) and feeds the 16-bit MFMA; tokens are NOT quantised.  The scale
+ *   multiplies the fp32 sum before the residual add and the one rounding to the output type.  Prologues
+ *   and their rounding points as mk_decode_linear (1: x [M][K], norm_w [K]; 2: x [M][2K]).  Domain,
+ *   else MK_ERR_UNSUPPORTED: M <= 16 with a prologue, M <= 32 plain; K % 64 == 0; ldw % 16 == 0 and
+ *   ldx % 8 == 0 (elements), pitches not below the row lengths; x, Wq (and norm_w) 16-byte aligned,
+ *   scale 4-byte aligned; with a prologue M * (K + 8) * 2 bytes <= 40 KiB of LDS.  Deterministic: the
+ *   cross-wave sum has a fixed order. */
+int mk_decode_linear_fp8(const void* x, int64_t ldx, const void* Wq, int64_t ldw, const float* scale, void* y,
+                         int64_t ldy, const void* residual, int64_t ldr, int32_t M, int32_t N, int32_t K,
+                         int32_t prologue, const void* norm_w, float eps, int32_t dtype, void* stream);
 /* mk_decode_emit: greedy selection + bookkeeping of one decode step (modeling.py:959, HF greedy_search):
  *   for every sample b: nxt = done[b] ? pad : first argmax of logits[b][0:V]; out[b][state[1]] = nxt;
  *   done[b] |= (nxt == eos); tok[b] = nxt.  Then, once: state[0] += 1 (the position the other decode
@@ -387,7 +401,7 @@ int mk_set_dropout_seed_offset(const uint64_t* dev_ptr);
  * amax_ws: device float[1] scratch.  n % 8 == 0, 16-byte aligned x, 8-byte aligned q. */
 int mk_fp8_quantize(const void* x, int64_t n, int32_t dtype, uint8_t* q, float* amax_ws,
                     float* dequant_scale, void* stream);
-/* Per-ROW scaled e4m3 of a row-major (pitched) [rows, cols] bf16 matrix (activations, gradients,
+/* Per-ROW scaled e4m3 of a row-major (pitched) [rows, cols] bf16 (or f16) matrix (activations, gradients,
  * K-major weights = one scale per output channel): q[r, c] = e4m3(x[r, c] * 448 / amax_r),
  * scales[r] = amax_r / 448 (1 for a zero row).  cols % 8 == 0; GEMM operands need cols % 128 == 0. */
 int mk_fp8_quantize_rows(const void* x, int32_t rows, int32_t cols, int64_t ld, int32_t dtype,

@@ -455,16 +455,17 @@ MK_DEV int2 fp8_pack8(const float (&v)[8], float sc) {
   return make_int2(lo, hi);
 }
 
-__global__ __launch_bounds__(256) void fp8_rowquant_kernel(const bf16* x, long ld, int cols, uint8_t* q,
+template <typename T>
+__global__ __launch_bounds__(256) void fp8_rowquant_kernel(const T* x, long ld, int cols, uint8_t* q,
                                                            long ldq, float* scale) {
   __shared__ float red[16];
   const long row = blockIdx.x;
-  const bf16* xr = x + row * ld;
+  const T* xr = x + row * ld;
   const int nch = cols / 8;
   float m = 0.f;
   for (int c = threadIdx.x; c < nch; c += 256) {
     float v[8];
-    VecIO<bf16>::load(xr + c * 8, v);
+    VecIO<T>::load(xr + c * 8, v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(v[k]));
   }
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(256) void fp8_rowquant_kernel(const bf16* x, long l
   uint8_t* qr = q + row * ldq;
   for (int c = threadIdx.x; c < nch; c += 256) {
     float v[8];
-    VecIO<bf16>::load(xr + c * 8, v);
+    VecIO<T>::load(xr + c * 8, v);
     *reinterpret_cast<int2*>(qr + c * 8) = fp8_pack8(v, sc);
   }
 }
@@ -482,12 +483,12 @@ __global__ __launch_bounds__(256) void fp8_rowquant_kernel(const bf16* x, long l
 // Round 6: the row stays in REGISTERS between the amax pass and the quantisation (CH chunks of 8 per thread: rows of up
 // to 2048 * CH elements) -- one load per element instead of two dependent sweeps (load -> block reduce -> load -> store
 // serialised per 4-wave block: 2.4 TB/s effective on the 13B step's 14 GB, profiles/r05_cfg5_last_step.txt).  Same bytes out.
-template <int CH>
-__global__ __launch_bounds__(256) void fp8_rowquant_reg_kernel(const bf16* x, long ld, int cols, uint8_t* q,
+template <int CH, typename T>
+__global__ __launch_bounds__(256) void fp8_rowquant_reg_kernel(const T* x, long ld, int cols, uint8_t* q,
                                                                long ldq, float* scale) {
   __shared__ float red[16];
   const long row = blockIdx.x;
-  const bf16* xr = x + row * ld;
+  const T* xr = x + row * ld;
   const int nch = cols / 8;
   float v[CH][8];
   float m = 0.f;
@@ -496,7 +497,7 @@ __global__ __launch_bounds__(256) void fp8_rowquant_reg_kernel(const bf16* x, lo
     const int c = threadIdx.x + 256 * k;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[k][e] = 0.f;
-    if (c < nch) VecIO<bf16>::load(xr + c * 8, v[k]);
+    if (c < nch) VecIO<T>::load(xr + c * 8, v[k]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[k][e]));
   }
@@ -934,25 +935,34 @@ extern "C" int mk_fp8_quantize(const void* x, int64_t n, int32_t dtype, uint8_t*
   return mk_check_launch();
 }
 
-extern "C" int mk_fp8_quantize_rows(const void* x, int32_t rows, int32_t cols, int64_t ld, int32_t dtype,
-                                    uint8_t* q, int64_t ldq, float* scales, void* stream) {
-  if (!x || !q || !scales || rows <= 0 || cols <= 0) return MK_ERR_BAD_ARG;
-  if (dtype != MK_BF16 || (cols % 8) || (ld % 8) || (ldq % 8) || (reinterpret_cast<uintptr_t>(x) & 15) ||
-      (reinterpret_cast<uintptr_t>(q) & 7))
-    return MK_ERR_UNSUPPORTED;
-  const int ch = mk_cdiv(cols / 8, 256);
-  static const bool two_pass = getenv("MK_FP8_ROWQUANT_TWO_PASS") != nullptr;       // A/B: the round-3 kernel
-#define MK_RQ(CHV) MK_LAUNCH(fp8_rowquant_reg_kernel<CHV>, dim3(rows), dim3(256), 0, MK_ST, (const bf16*)x, (long)ld, cols, q, \
-                             (long)ldq, scales)
-  if (two_pass || ch > 8)
-    MK_LAUNCH(fp8_rowquant_kernel, dim3(rows), dim3(256), 0, MK_ST, (const bf16*)x, (long)ld, cols, q,
-              (long)ldq, scales);
+namespace {
+// (f16 rows: the weights of an fp16 model for generate(decode_weights="fp8"); same kernels, same rounding)
+template <typename T>
+void rowquant_launch(const void* x, int rows, int cols, long ld, uint8_t* q, long ldq, float* scales, bool two_pass,
+                     int ch, void* stream) {
+#define MK_RQ(CHV) MK_LAUNCH((fp8_rowquant_reg_kernel<CHV, T>), dim3(rows), dim3(256), 0, MK_ST, (const T*)x, ld, cols, q, \
+                             ldq, scales)
+  if (two_pass)
+    MK_LAUNCH(fp8_rowquant_kernel<T>, dim3(rows), dim3(256), 0, MK_ST, (const T*)x, ld, cols, q, ldq, scales);
   else if (ch <= 1) MK_RQ(1);
   else if (ch <= 2) MK_RQ(2);
   else if (ch <= 3) MK_RQ(3);
   else if (ch <= 4) MK_RQ(4);
   else MK_RQ(8);
 #undef MK_RQ
+}
+}  // namespace
+
+extern "C" int mk_fp8_quantize_rows(const void* x, int32_t rows, int32_t cols, int64_t ld, int32_t dtype,
+                                    uint8_t* q, int64_t ldq, float* scales, void* stream) {
+  if (!x || !q || !scales || rows <= 0 || cols <= 0) return MK_ERR_BAD_ARG;
+  if ((dtype != MK_BF16 && dtype != MK_F16) || (cols % 8) || (ld % 8) || (ldq % 8) || (reinterpret_cast<uintptr_t>(x) & 15) ||
+      (reinterpret_cast<uintptr_t>(q) & 7))
+    return MK_ERR_UNSUPPORTED;
+  const int ch = mk_cdiv(cols / 8, 256);
+  static const bool two_pass = getenv("MK_FP8_ROWQUANT_TWO_PASS") != nullptr;       // A/B: the round-3 kernel
+  if (dtype == MK_F16) rowquant_launch<_Float16>(x, rows, cols, ld, q, ldq, scales, two_pass || ch > 8, ch, stream);
+  else rowquant_launch<bf16>(x, rows, cols, ld, q, ldq, scales, two_pass || ch > 8, ch, stream);
   return mk_check_launch();
 }
 

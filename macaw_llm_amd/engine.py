@@ -560,8 +560,39 @@ class LlamaLayerFn(torch.autograd.Function):
                 dwd, dln1 if need[14] else None, dln2 if need[15] else None, None, None, None)
 
 
+def _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, FF, wo, wd, ln1, ln2, wqkv, wgu, t_dev, w8):
+    """llama_layer_cached's five-launch decode step with the four linear launches on e4m3 weight copies.
+    Where the prepared token rows of a prologue form do not fit the kernel's LDS budget (M > 4 at K = 4096) the
+    separate RMSNorm / SwiGLU kernel runs first, as in the 16-bit step, and the PLAIN fp8 launch follows: every
+    batch size up to 32 streams e4m3 bytes."""
+    M, D = x2.shape
+    H, hd = n_heads, D // n_heads
+    q_qkv, q_o, q_gu, q_d = w8
+
+    def linear(x, W, q8, pro, w_ln=None, residual=None):
+        if q8 is not None and ops.decode_linear_fp8_ok(x, q8[0], pro):
+            return ops.decode_linear_fp8(x, q8[0], q8[1], pro, w_ln, eps, residual)
+        if q8 is None and ops.decode_linear_ok(x, W, pro):
+            return ops.decode_linear(x, W, pro, w_ln, eps, residual)
+        if pro == 1:
+            x = ops.rmsnorm_fwd(x, w_ln, eps)[1]
+        elif pro == 2:
+            x = ops.swiglu2d_fwd(x, FF)
+        if q8 is not None:
+            return ops.decode_linear_fp8(x, q8[0], q8[1], residual=residual)
+        return ops.linear_fwd(x, W, residual=residual)
+
+    qkv = linear(x2, wqkv, q_qkv, 1, ln1)
+    att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
+    ops.decode_step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, t_dev, Tmax, B, H, hd, att,
+                         1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
+    h1 = linear(att, wo, q_o, 0, residual=x2)
+    gu = linear(h1, wgu, q_gu, 1, ln2)
+    return linear(gu, wd, q_d, 2, residual=h1)
+
+
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
-                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None):
+                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None):
     """No-grad decoder layer over `Sn` NEW positions per sample (rows of x2 are (b, s)) that
     start at position t0, with a preallocated KV cache kvc [B, Tmax, 2D] = [keys | values] per
     position (post-RoPE keys, modeling.py:183-195 semantics without the torch.cat per step).
@@ -572,11 +603,22 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
 
     t_dev (int32[1] on the device, Sn = 1 only): the position is read from device memory by the
     cache append and the attention kernel (`pos` already is a device tensor) and t0 is ignored, so
-    the launch sequence does not depend on the step and can be replayed from a hipGraph."""
+    the launch sequence does not depend on the step and can be replayed from a hipGraph.
+
+    w8 (with t_dev and fused storage only): the e4m3 copies (q uint8 [N, K], scales f32 [N]: ops.fp8_weight) of
+    the four streamed weights, in the order fused q|k|v, o, fused gate|up, down.  The same five launches then
+    stream e4m3 bytes (ops.decode_linear_fp8: W8A16, tokens / KV cache / accumulation unchanged).  An entry
+    may be None for a projection outside the plain fp8 domain: that one keeps its 16-bit launch."""
     M, D = x2.shape
     dyn = t_dev is not None
     if dyn and Sn != 1:
         raise ValueError("llama_layer_cached: t_dev is for single-position decode steps")
+    if w8 is not None:
+        if not (dyn and wqkv is not None and wgu is not None and ops.decode_linear_ok(x2, wqkv)):
+            raise ValueError("llama_layer_cached: w8 is for the five-launch decode step (t_dev, fused q|k|v and "
+                             "gate|up storage, at most 32 rows)")
+        return _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, wg.shape[0], wo, wd, ln1, ln2,
+                                     wqkv, wgu, t_dev, w8)
     if dyn and wqkv is not None and wgu is not None and ops.decode_linear_ok(x2, wqkv):
         # five launches: RMSNorm folded into the q|k|v and gate|up weight streams, SwiGLU into down's
         # (each where the prepared token rows fit the kernel's LDS budget, else the separate kernel)

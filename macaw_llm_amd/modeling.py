@@ -52,6 +52,8 @@ def _dtype_check(dtype):
 # them separate storage), so a model built the reference's way -- MM_LLMs(config), .to(), Trainer --
 # runs the same fused GEMMs as factory.build_model.  MACAW_NO_AUTO_FUSE=1 disables it.
 AUTO_FUSE = os.environ.get("MACAW_NO_AUTO_FUSE") is None
+# MM_LLMs.set_decode_weights: the decode_weights MM_LLMs.forward hands to generate() (None or "fp8")
+DECODE_WEIGHTS = [None]
 
 
 def _rows_view(ts):
@@ -499,9 +501,34 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
         return res.clone()
 
+    def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph):
+        """generate(decode_weights="fp8") runs on the five-launch hipGraph decode step only: name what keeps a
+        call off that path instead of decoding it in 16 bits"""
+        why = None
+        a0 = self.model.layers[0].self_attn
+        hd = self.config.hidden_size // a0.num_heads
+        if dtype not in (torch.bfloat16, torch.float16):
+            why = f"fp32 parameters ({dtype}): the decode kernels stream bf16 / fp16 tokens"
+        elif not use_cache:
+            why = "use_cache=False recomputes the prefix with the 16-bit weights"
+        elif not decode_graph:
+            why = "decode_graph=False selects the eager decode loop"
+        elif os.environ.get("MACAW_NO_DECODE_GRAPH"):
+            why = "MACAW_NO_DECODE_GRAPH selects the eager decode loop"
+        elif max_new_tokens <= 2:
+            why = f"max_new_tokens={max_new_tokens} <= 2: no decode step is captured"
+        elif B > 32:
+            why = f"{B} sequences: the weight-streaming decode step takes at most 32"
+        elif not ops.decode_attn_ok(dtype, hd, S0 + max_new_tokens):
+            why = (f"ops.decode_attn_ok is false for head size {hd} and {S0 + max_new_tokens} positions: the eager "
+                   "decode loop would run")
+        if why is not None:
+            raise ValueError(f"generate(decode_weights='fp8'): {why}")
+
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
-                 bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, **_):
+                 bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
+                 **_):
         """Greedy decode — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -509,7 +536,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         through the layers against the cache (fused attention, Lq = 1) instead of the
         reference's per-step `torch.cat` of the cache (modeling.py:190-195).  Finished samples
         emit pad_token_id.  Returns the NEW token ids [B, <= max_new_tokens].
-        use_cache=False recomputes the whole prefix each step (same ids; test reference)."""
+        use_cache=False recomputes the whole prefix each step (same ids; test reference).
+
+        decode_weights="fp8": weight-only quantised decode (W8A16).  The decode steps and the lm_head stream
+        OCP e4m3 copies of the weights, one scale per output channel (ops.fp8_weight: made once, re-made when
+        the weight version moves; shared with the fp8 training configuration), through ops.decode_linear_fp8;
+        tokens, KV cache and accumulation keep their precision, and the prefill keeps the 16-bit weights (a
+        large-M GEMM, not a stream; the prompt's KV cache is written at full weight precision).  This is a
+        LATENCY mode, not a memory one: the 16-bit masters stay resident and the copies add half their size.
+        With LoRA adapters the per-call merged copies are quantised, once per call.  It needs the hipGraph
+        decode path and raises ValueError naming the condition when that path would not be taken (fp32
+        parameters, unfused q/k/v or gate/up storage, use_cache=False, decode_graph=False or
+        MACAW_NO_DECODE_GRAPH, max_new_tokens <= 2, more than 32 sequences, a head size / length outside
+        ops.decode_attn_ok) instead of silently decoding in 16 bits.  None (default): the 16-bit path."""
+        if decode_weights not in (None, "fp8"):
+            raise ValueError(f"generate: decode_weights must be None or 'fp8', got {decode_weights!r}")
         emb_w = self.model.embed_tokens.weight
         if inputs_embeds is None:
             inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(*input_ids.shape, -1)
@@ -522,7 +563,16 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         V = self.lm_head.weight.shape[0]
         out = []
 
+        if decode_weights == "fp8":
+            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph)
+        w8_head = None            # decode_weights="fp8": (q, scales) of the lm_head
+
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
+            if w8_head is not None and h_last.is_contiguous():
+                if ops.decode_linear_fp8_ok(h_last, w8_head[0], 1):
+                    return ops.decode_linear_fp8(h_last, *w8_head, 1, self.model.norm.weight, eps)
+                _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
+                return ops.decode_linear_fp8(y, *w8_head)
             if h_last.is_contiguous() and ops.decode_linear_ok(h_last, self.lm_head.weight, 1):
                 return ops.decode_linear(h_last, self.lm_head.weight, 1, self.model.norm.weight, eps)
             _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
@@ -570,6 +620,27 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         else:
             merged = {}
 
+        w8 = None                 # decode_weights="fp8": per layer the copies of q|k|v, o, gate|up, down
+        if decode_weights == "fp8":
+            probe = torch.empty((B, 0), dtype=dtype, device=dev)
+
+            def q8(W, own):       # own: a stored parameter (version-keyed cache); else a merged copy of this call
+                if W is None or not ops.decode_linear_fp8_ok(probe, W):
+                    return None   # outside the plain fp8 domain: this projection keeps its 16-bit launch
+                return ops.fp8_weight(W) if own is not None and own.data_ptr() == W.data_ptr() else ops.quantize_fp8_rows(W)
+
+            w8 = []
+            for lyr in layers:
+                a, m = lyr.self_attn, lyr.mlp
+                own = (*lyr.fused_weights(), a.o_proj.weight, m.down_proj.weight)
+                if own[0] is None or own[1] is None:
+                    raise ValueError("generate(decode_weights='fp8'): unfused q/k/v or gate/up storage (the fp8 "
+                                     "decode step streams the fused q|k|v and gate|up weights: fuse_projections())")
+                ws = merged.get(lyr)
+                cur = (ws[7], ws[8], ws[3], ws[6]) if ws is not None else own
+                w8.append((q8(cur[0], own[0]), q8(cur[2], own[2]), q8(cur[1], own[1]), q8(cur[3], own[3])))
+            w8_head = q8(self.lm_head.weight, self.lm_head.weight)
+
         def run(x2, Sn, t0, pos=None, t_dev=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
@@ -583,7 +654,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 x2 = eng.llama_layer_cached(
                     x2, B, Sn, t0, kvc[i], Tmax, pos, cos, sin, a.num_heads,
                     lyr.input_layernorm.variance_epsilon, *ws[:7], lyr.input_layernorm.weight,
-                    lyr.post_attention_layernorm.weight, *ws[7:], t_dev=t_dev)
+                    lyr.post_attention_layernorm.weight, *ws[7:], t_dev=t_dev,
+                    w8=w8[i] if w8 is not None and t_dev is not None else None)
             return x2
 
         h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)                 # prefill
@@ -770,7 +842,8 @@ class MM_LLMs(PreTrainedModel):
             lora.ext_seed = self._dropout_seed(lora.SLOT)
         if "inference" in inputs and inputs["inference"] is True:
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
-                                     eos_token_id=2, bos_token_id=1, pad_token_id=32006)
+                                     eos_token_id=2, bos_token_id=1, pad_token_id=32006,
+                                     decode_weights=DECODE_WEIGHTS[0])
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -784,6 +857,15 @@ class MM_LLMs(PreTrainedModel):
         Process-wide switch."""
         eng.FP8["qkv"], eng.FP8["align"], eng.FP8["mlp"] = bool(qkv), bool(align), bool(mlp)
         ops.clear_fp8_cache()
+
+    @staticmethod
+    def set_decode_weights(mode=None):
+        """Weight format of the decode steps of `inputs["inference"] = True` (LlamaForCausalLM.generate's
+        decode_weights): None = the 16-bit weights, "fp8" = weight-only e4m3 copies (W8A16: a latency mode, the
+        16-bit masters stay resident).  Process-wide switch, like set_fp8."""
+        if mode not in (None, "fp8"):
+            raise ValueError(f"set_decode_weights: mode must be None or 'fp8', got {mode!r}")
+        DECODE_WEIGHTS[0] = mode
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

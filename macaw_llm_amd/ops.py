@@ -560,6 +560,31 @@ def decode_linear_ok(x, W, prologue=0):
             and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
 
 
+def decode_linear_fp8(x, Wq, s, prologue=0, norm_w=None, eps=0.0, residual=None, out=None):
+    """decode_linear with the weight streamed as e4m3 bytes (W8A16): y[M <= 16, N] = prologue(x) (s * Wq)^T
+    (+ residual); Wq uint8 [N, K] row-major, s f32 [N] (the pair fp8_weight(W) returns); x, residual, y bf16
+    or fp16, tokens not quantised, fp32 accumulation, the scale applied before the residual add"""
+    lib = _L.load()
+    M = x.shape[0]
+    N, K = Wq.shape
+    if Wq.dtype != torch.uint8 or s.dtype != torch.float32 or s.numel() != N or not s.is_contiguous():
+        raise MacawHipError(f"decode_linear_fp8: weight {Wq.dtype} {tuple(Wq.shape)}, scales {s.dtype} {tuple(s.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _L.check(lib.mk_decode_linear_fp8(_p(x), _rowmajor(x), _p(Wq), _rowmajor(Wq), _p(s), _p(out), _rowmajor(out),
+                                      _p(residual), _rowmajor(residual) if residual is not None else 0, M, N, K,
+                                      prologue, _p(norm_w), eps, dt(x), _st()), "mk_decode_linear_fp8")
+    return out
+
+
+def decode_linear_fp8_ok(x, Wq, prologue=0):
+    """mk_decode_linear_fp8's domain (Wq: the e4m3 copy, or the [N, K] 16-bit weight it will be made from); with
+    a prologue the prepared token rows must fit 40 KiB of LDS"""
+    M, K = x.shape[0], Wq.shape[1]
+    return (x.dtype in (torch.bfloat16, torch.float16) and M <= (16 if prologue else 32) and K % 64 == 0
+            and Wq.is_contiguous() and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
+
+
 def decode_emit(logits, V, pad, eos, tok, done, out, state):
     """greedy selection + step bookkeeping in one launch (see mk_decode_emit): logits [B, >= V]
     row-major, tok int64 [B], done bool [B], out int64 [B, n], state int32 [>= 3] = (position, output

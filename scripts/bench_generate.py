@@ -11,7 +11,42 @@ with torch.no_grad():
     model.llm.generate(inputs_embeds=model.prepare_inputs_for_generation(_w)[0], max_new_tokens=4, eos_token_id=-1)
 # usage: bench_generate.py [B ...]; BG_SKINNY32="19,22" repeats every batch size > 16 with each kernel for
 # 17 ... 32 token rows (MK_GEMM_SKINNY32, read per call by csrc/gemm.hip: one process and one model serve all variants)
-BATCHES = [int(a) for a in sys.argv[1:]] or [1, 8, 32]
+#        bench_generate.py --fp8-ab [--reps R] [B ...]: every batch size with decode_weights=None and "fp8" in THIS process
+# on THIS model, alternated bf16 / fp8 / bf16 / fp8 ... (R repetitions each, default 3): ms per token of every run, the
+# medians, their ratio, the bf16 run-to-run spread (a difference counts only beyond it) and the achieved weight-stream
+# bandwidth of each mode (fp8 bytes: half the projections' plus f32[N] scales)
+AB = "--fp8-ab" in sys.argv
+REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--fp8-ab" and a != "--reps" and sys.argv[i - 1] != "--reps"]
+if AB:
+    streamed = [lyr.fused_weights() + (lyr.self_attn.o_proj.weight, lyr.mlp.down_proj.weight) for lyr in model.llm.model.layers]
+    streamed = [w for ws in streamed for w in ws] + [model.llm.lm_head.weight]
+    BYTES = {None: sum(2 * w.numel() for w in streamed), "fp8": sum(w.numel() + 4 * w.shape[0] for w in streamed)}
+    print(f"streamed per token: bf16 {BYTES[None] / 1e9:.3f} GB, fp8 {BYTES['fp8'] / 1e9:.3f} GB (e4m3 bytes + f32 scales)")
+    with torch.no_grad():       # the e4m3 copies are made here, outside the timed calls
+        model.llm.generate(inputs_embeds=model.prepare_inputs_for_generation(_w)[0], max_new_tokens=4, eos_token_id=-1,
+                           decode_weights="fp8")
+    for B in [int(a) for a in _args] or [1, 8, 16, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {None: [], "fp8": []}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for rep in range(REPS):
+                for mode in (None, "fp8"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, decode_weights=mode)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {mode or 'bf16':4s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = (max(ms[None]) - min(ms[None])) / med[None]
+        print(f"B={B:2d}: bf16 {med[None]:6.3f} ms/token ({BYTES[None] / med[None] / 1e9:4.2f} TB/s), fp8 {med['fp8']:6.3f} ms/token "
+              f"({BYTES['fp8'] / med['fp8'] / 1e9:4.2f} TB/s), fp8 / bf16 = {med['fp8'] / med[None]:5.3f} "
+              f"(bf16 run-to-run spread {spread * 100:4.1f} %)", flush=True)
+    sys.exit(0)
+BATCHES = [int(a) for a in _args] or [1, 8, 32]
 SK = [v for v in os.environ.get("BG_SKINNY32", "").split(",") if v]
 for B, sk in [(B, s) for B in BATCHES for s in (SK if (SK and B > 16) else [None])]:
     if sk is not None:
