@@ -36,7 +36,7 @@ extern "C" {
 #define MK_FP8 3 /* OCP e4m3fn bytes: mk_gemm operands / mk_fp8_quantize output only */
 
 /* library identification: returns MK_ABI_VERSION */
-#define MK_ABI_VERSION 7
+#define MK_ABI_VERSION 8
 int mk_abi_version(void);
 
 /* ------------------------------------------------------------------ GEMM --
@@ -359,6 +359,35 @@ int mk_decode_step_attn(const void* q, const void* k_new, const void* v_new, int
                         int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
                         int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale, int32_t dtype,
                         void* stream);
+/* e4m3 KV cache (generate(kv_cache="fp8")): the partner of mk_decode_linear_fp8 for the other stream of a decode
+ *   step.  ONE format:
+ *     bytes   uint8 [B][t_max][2 * D]  a row = [keys of all heads | values of all heads] (D = H * hd), OCP e4m3fn,
+ *                                      the shape of the 16-bit cache; keys are quantised AFTER RoPE;
+ *     scales  f32   [B][t_max][2 * H]  a row = [key scale of every head | value scale of every head]: one scale per
+ *                                      (sample, position, key or value, head) = amax / 448 over that head's hd
+ *                                      elements, 1 for an all-zero head.
+ *   Quantisation as mk_fp8_quantize_rows with rows = heads: sc = 448 / amax in fp32, x * sc, clamp to +-448,
+ *   round to nearest even.  Scales cost 2H * 4 bytes per 2D cache bytes (3 % at hd = 128): 0.52 of the 16-bit cache.
+ * mk_kv_quant_append: the prefill's cache write.  k (already rotated) and v: Sn new rows [H * hd] per sample, bf16
+ *   or f16, row pitch ld and sample stride in_bs (elements; two pointers, so slices of a fused [M][3D] buffer and
+ *   separate k / v storage both work).  Writes bytes and scales of cache rows [t0, t0 + Sn) of every sample and
+ *   touches no other row.  MK_ERR_BAD_ARG unless 0 <= t0 and t0 + Sn <= t_max.
+ * mk_decode_step_attn_kv8: mk_decode_step_attn over that cache, one launch: p = clamp(*t_dev, 0, t_max - 1); q and
+ *   k_new are rotated with rows p of the cos / sin tables (rounding points of mk_rope); the rotated key and v_new
+ *   are quantised per head and their bytes and scales go to cache row p; o = attention of the rotated 16-bit query
+ *   over rows 0 ... p of the cache AS STORED AFTER THE APPEND (row p enters as the de-quantised quantised value,
+ *   which is what later steps read).  De-quantisation in fp32, the scale applied once per key: s_t = scale *
+ *   k_scale[t] * sum(q . e4m3), o += p_t * v_scale[t] * e4m3; nothing is rounded to 16 bits in between.
+ * Domain of both, else MK_ERR_UNSUPPORTED and nothing is launched: dtype bf16 / f16; hd in {16, 32, 64, 128}; every
+ *   pointer 16-byte aligned (the output excepted); ld % 8 == 0 and in_bs % 8 == 0 (elements), pitches and strides
+ *   not below H * hd. */
+int mk_kv_quant_append(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,
+                       int32_t t0, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd, int32_t dtype,
+                       void* stream);
+int mk_decode_step_attn_kv8(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                            const void* sin_t, void* cache, float* scales, void* o, int64_t o_bs,
+                            const int32_t* t_dev, int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale,
+                            int32_t dtype, void* stream);
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);

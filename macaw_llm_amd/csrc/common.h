@@ -205,6 +205,20 @@ template <> struct E16<_Float16> {
   }
 };
 
+// ---- e4m3 packing shared by the quantisation kernels (elementwise.hip) and the e4m3 KV cache (decode.hip):
+// 8 fp32 values x sc -> 8 OCP e4m3fn bytes, element index ascending with the byte address.  v_cvt_pk_fp8_f32
+// rounds to nearest even and does NOT saturate (anything above 448 becomes the NaN code 0x7f): hence the clamp.
+MK_DEV int2 fp8_pack8(const float (&v)[8], float sc) {
+  float t[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) t[k] = fminf(fmaxf(v[k] * sc, -448.f), 448.f);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], hi, true);
+  return make_int2(lo, hi);
+}
+
 // ---- wave / block reductions -------------------------------------------
 MK_DEV float wave_sum(float v) {
 #pragma unroll

@@ -6,6 +6,8 @@
 //   mk_kv_append    cache[b][*t_dev][0:cols] = src[b][0:cols]   (post-RoPE keys | values of the new token)
 //   mk_decode_attn  one query row per (sample, head) against the first *t_dev + t_add cached keys
 //   mk_decode_step_attn  RoPE(q, k_new) + append(k_new, v_new) + that attention in one launch
+//   mk_kv_quant_append / mk_decode_step_attn_kv8  the prefill's cache write and the step's attention block over an
+//                   e4m3 KV cache (bytes + one fp32 scale per head and position: decode_kv8_impl.inc)
 //
 // The fused training / prefill attention (attention.hip) works on 128-row query tiles: at Lq = 1
 // it would spend 127 of 128 MFMA rows on padding and, more to the point here, takes its key count
@@ -80,6 +82,7 @@ __global__ __launch_bounds__(1024) void decode_emit_kernel(const T* logits, long
 #define MK_E16_T bf16
 #define MK_E16_NS e_bf16
 #include "decode_impl.inc"
+#include "decode_kv8_impl.inc"
 #undef MK_E16_T
 #undef MK_E16_NS
 #define MK_E16_T _Float16
@@ -87,10 +90,15 @@ __global__ __launch_bounds__(1024) void decode_emit_kernel(const T* logits, long
 #define decode_attn_kernel decode_attn_f16_kernel
 #define decode_step_attn_kernel decode_step_attn_f16_kernel
 #define decode_step_attn4_kernel decode_step_attn4_f16_kernel
+#define kv_quant_append_kernel kv_quant_append_f16_kernel
+#define decode_step_attn_kv8_kernel decode_step_attn_kv8_f16_kernel
 #include "decode_impl.inc"
+#include "decode_kv8_impl.inc"
 #undef decode_attn_kernel
 #undef decode_step_attn_kernel
 #undef decode_step_attn4_kernel
+#undef kv_quant_append_kernel
+#undef decode_step_attn_kv8_kernel
 #undef MK_E16_T
 #undef MK_E16_NS
 
@@ -101,6 +109,21 @@ extern "C" int mk_decode_step_attn(const void* q, const void* k_new, const void*
                                    int32_t hd, float scale, int32_t dtype, void* stream) {
   if (dtype == MK_F16) return e_f16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream);
   return e_bf16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream);
+}
+
+extern "C" int mk_kv_quant_append(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,
+                                  int32_t t0, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd,
+                                  int32_t dtype, void* stream) {
+  if (dtype == MK_F16) return e_f16::kv_quant_append_impl(k, v, ld, in_bs, cache, scales, t0, Sn, t_max, B, H, hd, dtype, stream);
+  return e_bf16::kv_quant_append_impl(k, v, ld, in_bs, cache, scales, t0, Sn, t_max, B, H, hd, dtype, stream);
+}
+
+extern "C" int mk_decode_step_attn_kv8(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                                       const void* cos_t, const void* sin_t, void* cache, float* scales, void* o,
+                                       int64_t o_bs, const int32_t* t_dev, int32_t t_max, int32_t B, int32_t H,
+                                       int32_t hd, float scale, int32_t dtype, void* stream) {
+  if (dtype == MK_F16) return e_f16::decode_step_attn_kv8_impl(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream);
+  return e_bf16::decode_step_attn_kv8_impl(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream);
 }
 
 extern "C" int mk_decode_attn(const void* q, const void* k, const void* v, void* o,

@@ -444,16 +444,7 @@ __global__ __launch_bounds__(256) void fp8_quant_kernel(const T* x, long n, uint
 // ---- per-ROW scaled e4m3 (activations, gradients, K-major weights): one workgroup per row.
 // q[r, c] = e4m3(clamp(x[r, c] * 448 / amax_r)), scale[r] = amax_r / 448 (1 for an all-zero row).
 // The row is read twice (the second pass hits L2): HBM traffic = 2 B in + 1 B out per element.
-MK_DEV int2 fp8_pack8(const float (&v)[8], float sc) {
-  float t[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) t[k] = fminf(fmaxf(v[k] * sc, -448.f), 448.f);
-  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], lo, true);
-  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], hi, true);
-  return make_int2(lo, hi);
-}
+// (fp8_pack8: common.h)
 
 template <typename T>
 __global__ __launch_bounds__(256) void fp8_rowquant_kernel(const T* x, long ld, int cols, uint8_t* q,

@@ -560,7 +560,16 @@ class LlamaLayerFn(torch.autograd.Function):
                 dwd, dln1 if need[14] else None, dln2 if need[15] else None, None, None, None)
 
 
-def _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, FF, wo, wd, ln1, ln2, wqkv, wgu, t_dev, w8):
+def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off):
+    """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
+    e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8"""
+    if kv8 is not None:
+        return ops.decode_step_attn_kv8(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off)
+    return ops.decode_step_attn(q, k, v, in_bs, cos, sin, kvc, t_dev, Tmax, B, H, hd, att, scale, **off)
+
+
+def _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, FF, wo, wd, ln1, ln2, wqkv, wgu, t_dev, w8,
+                          kv8=None):
     """llama_layer_cached's five-launch decode step with the four linear launches on e4m3 weight copies.
     Where the prepared token rows of a prologue form do not fit the kernel's LDS budget (M > 4 at K = 4096) the
     separate RMSNorm / SwiGLU kernel runs first, as in the 16-bit step, and the PLAIN fp8 launch follows: every
@@ -584,15 +593,15 @@ def _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, FF, wo, wd, 
 
     qkv = linear(x2, wqkv, q_qkv, 1, ln1)
     att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
-    ops.decode_step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, t_dev, Tmax, B, H, hd, att,
-                         1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
+    _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att,
+               1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
     h1 = linear(att, wo, q_o, 0, residual=x2)
     gu = linear(h1, wgu, q_gu, 1, ln2)
     return linear(gu, wd, q_d, 2, residual=h1)
 
 
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
-                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None):
+                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None):
     """No-grad decoder layer over `Sn` NEW positions per sample (rows of x2 are (b, s)) that
     start at position t0, with a preallocated KV cache kvc [B, Tmax, 2D] = [keys | values] per
     position (post-RoPE keys, modeling.py:183-195 semantics without the torch.cat per step).
@@ -608,9 +617,18 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     w8 (with t_dev and fused storage only): the e4m3 copies (q uint8 [N, K], scales f32 [N]: ops.fp8_weight) of
     the four streamed weights, in the order fused q|k|v, o, fused gate|up, down.  The same five launches then
     stream e4m3 bytes (ops.decode_linear_fp8: W8A16, tokens / KV cache / accumulation unchanged).  An entry
-    may be None for a projection outside the plain fp8 domain: that one keeps its 16-bit launch."""
+    may be None for a projection outside the plain fp8 domain: that one keeps its 16-bit launch.
+
+    kv8 (the f32 [B, Tmax, 2H] scales of an e4m3 KV cache; kvc then is its uint8 [B, Tmax, 2D] bytes:
+    ops.kv8_cache): every decode step (t_dev) runs ops.decode_step_attn_kv8 in place of ops.decode_step_attn, with
+    or without w8.  The prefill (t0 = 0) attends over the fresh 16-bit q, k, v of the prompt -- the data a 16-bit
+    cache would have held -- and then writes the cache through ops.kv_quant_append; there is no quantised
+    attention over several new positions, so t0 > 0 without t_dev raises ValueError."""
     M, D = x2.shape
     dyn = t_dev is not None
+    if kv8 is not None and not dyn and t0 != 0:
+        raise ValueError("llama_layer_cached: kv8 takes a prefill from position 0 (t0 = 0) or single-position decode "
+                         f"steps (t_dev), not {Sn} new positions at t0 = {t0}")
     if dyn and Sn != 1:
         raise ValueError("llama_layer_cached: t_dev is for single-position decode steps")
     if w8 is not None:
@@ -618,7 +636,7 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
             raise ValueError("llama_layer_cached: w8 is for the five-launch decode step (t_dev, fused q|k|v and "
                              "gate|up storage, at most 32 rows)")
         return _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, wg.shape[0], wo, wd, ln1, ln2,
-                                     wqkv, wgu, t_dev, w8)
+                                     wqkv, wgu, t_dev, w8, kv8)
     if dyn and wqkv is not None and wgu is not None and ops.decode_linear_ok(x2, wqkv):
         # five launches: RMSNorm folded into the q|k|v and gate|up weight streams, SwiGLU into down's
         # (each where the prepared token rows fit the kernel's LDS budget, else the separate kernel)
@@ -631,8 +649,8 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
 
         qkv = norm_linear(x2, ln1, wqkv)
         att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
-        ops.decode_step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, t_dev, Tmax, B, H, hd, att,
-                             1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
+        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att,
+                   1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
         h1 = ops.decode_linear(att, wo, residual=x2)
         gu = norm_linear(h1, ln2, wgu)
         if ops.decode_linear_ok(gu, wd, 2):
@@ -649,27 +667,40 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         q = qkv[:, :D]
         ldq = 3 * D
         if dyn:     # RoPE + cache append + attention of the new position: one launch
-            ops.decode_step_attn(qkv, qkv, qkv, ldq, cos, sin, kvc, t_dev, Tmax, B, H, hd, att, scale,
-                                 k_off=D, v_off=2 * D)
+            _step_attn(qkv, qkv, qkv, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale,
+                       k_off=D, v_off=2 * D)
         else:
             ops.rope_(qkv[:, :2 * D], cos, sin, pos, 2 * H, hd)
-            ops.copy2d(qkv, kvc, Sn, 2 * D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, src_off=D,
-                       dst_off=t0 * ldc)
+            k, v = qkv[:, D:2 * D], qkv[:, 2 * D:]
+            if kv8 is None:
+                ops.copy2d(qkv, kvc, Sn, 2 * D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, src_off=D,
+                           dst_off=t0 * ldc)
     else:
         q, k, v = ops.linear_fwd(y1, wq), ops.linear_fwd(y1, wk), ops.linear_fwd(y1, wv)
         ldq = D
         if dyn:
-            ops.decode_step_attn(q, k, v, ldq, cos, sin, kvc, t_dev, Tmax, B, H, hd, att, scale)
+            _step_attn(q, k, v, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale)
         else:
             ops.rope_(q, cos, sin, pos, H, hd)
             ops.rope_(k, cos, sin, pos, H, hd)
-            # append the new keys / values to the cache rows [t0, t0 + Sn) of every sample
-            ops.copy2d(k, kvc, Sn, D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, dst_off=t0 * ldc)
-            ops.copy2d(v, kvc, Sn, D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, dst_off=t0 * ldc + D)
+            if kv8 is None:
+                # append the new keys / values to the cache rows [t0, t0 + Sn) of every sample
+                ops.copy2d(k, kvc, Sn, D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, dst_off=t0 * ldc)
+                ops.copy2d(v, kvc, Sn, D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, dst_off=t0 * ldc + D)
     kc, vc = kvc[:, :, :D], kvc[:, :, D:]
     T = t0 + Sn
     if dyn:
         pass
+    elif kv8 is not None:
+        # e4m3 cache, prefill: causal attention over the prompt's own 16-bit q, k, v (read at the ldq pitch), then the
+        # quantising cache write
+        if flash_ok(x2.dtype, hd):
+            ops.flash_attn_fwd(q, k, v, att, B, H, Sn, Sn, hd, ldq, Sn * ldq, ldq, Sn * ldq, ldq, Sn * ldq,
+                               D, Sn * D, scale, causal=True)
+        else:
+            attention_fwd(TDesc(q, ldq, Sn * ldq), TDesc(k, ldq, Sn * ldq), TDesc(v, ldq, Sn * ldq),
+                          TDesc(att, D, Sn * D), B, H, Sn, Sn, hd, scale, causal=True)
+        ops.kv_quant_append(k, v, ldq, Sn * ldq, kvc, kv8, 0, Sn, Tmax, B, H, hd)
     elif flash_ok(x2.dtype, hd):
         ops.flash_attn_fwd(q, kc, vc, att, B, H, Sn, T, hd, ldq, Sn * ldq, ldc, Tmax * ldc, ldc, Tmax * ldc,
                            D, Sn * D, scale, causal=True)

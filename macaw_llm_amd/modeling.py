@@ -54,6 +54,8 @@ def _dtype_check(dtype):
 AUTO_FUSE = os.environ.get("MACAW_NO_AUTO_FUSE") is None
 # MM_LLMs.set_decode_weights: the decode_weights MM_LLMs.forward hands to generate() (None or "fp8")
 DECODE_WEIGHTS = [None]
+# MM_LLMs.set_kv_cache: the kv_cache MM_LLMs.forward hands to generate() (None or "fp8")
+KV_CACHE = [None]
 
 
 def _rows_view(ts):
@@ -501,34 +503,36 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
         return res.clone()
 
-    def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph):
-        """generate(decode_weights="fp8") runs on the five-launch hipGraph decode step only: name what keeps a
-        call off that path instead of decoding it in 16 bits"""
+    def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="decode_weights"):
+        """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
+        what keeps a call off that path instead of decoding it in 16 bits.  The limit of 32 sequences belongs to the
+        weight-streaming step (switch="decode_weights"); the e4m3 cache takes any batch."""
         why = None
         a0 = self.model.layers[0].self_attn
         hd = self.config.hidden_size // a0.num_heads
         if dtype not in (torch.bfloat16, torch.float16):
             why = f"fp32 parameters ({dtype}): the decode kernels stream bf16 / fp16 tokens"
         elif not use_cache:
-            why = "use_cache=False recomputes the prefix with the 16-bit weights"
+            why = ("use_cache=False recomputes the prefix with the 16-bit weights" if switch == "decode_weights" else
+                   "use_cache=False keeps no KV cache")
         elif not decode_graph:
             why = "decode_graph=False selects the eager decode loop"
         elif os.environ.get("MACAW_NO_DECODE_GRAPH"):
             why = "MACAW_NO_DECODE_GRAPH selects the eager decode loop"
         elif max_new_tokens <= 2:
             why = f"max_new_tokens={max_new_tokens} <= 2: no decode step is captured"
-        elif B > 32:
+        elif B > 32 and switch == "decode_weights":
             why = f"{B} sequences: the weight-streaming decode step takes at most 32"
         elif not ops.decode_attn_ok(dtype, hd, S0 + max_new_tokens):
             why = (f"ops.decode_attn_ok is false for head size {hd} and {S0 + max_new_tokens} positions: the eager "
                    "decode loop would run")
         if why is not None:
-            raise ValueError(f"generate(decode_weights='fp8'): {why}")
+            raise ValueError(f"generate({switch}='fp8'): {why}")
 
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
-                 **_):
+                 kv_cache=None, **_):
         """Greedy decode — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -548,9 +552,24 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         decode path and raises ValueError naming the condition when that path would not be taken (fp32
         parameters, unfused q/k/v or gate/up storage, use_cache=False, decode_graph=False or
         MACAW_NO_DECODE_GRAPH, max_new_tokens <= 2, more than 32 sequences, a head size / length outside
-        ops.decode_attn_ok) instead of silently decoding in 16 bits.  None (default): the 16-bit path."""
+        ops.decode_attn_ok) instead of silently decoding in 16 bits.  None (default): the 16-bit path.
+
+        kv_cache="fp8": the KV cache holds OCP e4m3 bytes with one fp32 scale per (sample, position, key or value,
+        head) (amax / 448 over the head's elements; keys quantised after RoPE; the format of include/macaw_hip.h):
+        0.52 of the 16-bit cache's memory and of the bytes a decode step reads from it.  The query stays 16-bit,
+        de-quantisation and accumulation are fp32 (ops.decode_step_attn_kv8).  The prefill attends over the prompt's
+        own 16-bit keys and values and then writes the quantised cache (ops.kv_quant_append), so the first new token
+        is the 16-bit path's.  The gain grows with batch x context (the weight stream of a step is fixed, the cache
+        stream is not); at batch 1 and a short context the attention launch is latency-bound and the switch buys
+        memory, not time (profiles/decode_kv8_generate.txt).  Composes with decode_weights="fp8".  Like that switch it
+        needs the hipGraph decode path and raises ValueError naming the condition otherwise (fp32 parameters,
+        use_cache=False, decode_graph=False or MACAW_NO_DECODE_GRAPH, max_new_tokens <= 2, a head size / length
+        outside ops.decode_attn_ok); any batch size, fused or unfused projection storage.  None (default): the 16-bit
+        cache."""
         if decode_weights not in (None, "fp8"):
             raise ValueError(f"generate: decode_weights must be None or 'fp8', got {decode_weights!r}")
+        if kv_cache not in (None, "fp8"):
+            raise ValueError(f"generate: kv_cache must be None or 'fp8', got {kv_cache!r}")
         emb_w = self.model.embed_tokens.weight
         if inputs_embeds is None:
             inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(*input_ids.shape, -1)
@@ -565,6 +584,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         if decode_weights == "fp8":
             self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph)
+        if kv_cache == "fp8":
+            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="kv_cache")
         w8_head = None            # decode_weights="fp8": (q, scales) of the lm_head
 
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
@@ -609,7 +630,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         layers = self.model.layers
         rot = layers[0].self_attn.rotary_emb
         cos, sin = rot.tables(Tmax, dtype, dev)
-        kvc = [torch.empty((B, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]   # [keys | values]
+        kvs = None                # kv_cache="fp8": per layer the f32 scales of the e4m3 cache (kvc: its bytes)
+        if kv_cache == "fp8":
+            H0 = layers[0].self_attn.num_heads
+            kvc, kvs = zip(*(ops.kv8_cache(B, Tmax, H0, D // H0, dev) for _ in layers))
+        else:
+            kvc = [torch.empty((B, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]   # [keys | values]
 
         if getattr(self, "_lora", None) is not None:
             # LoRA adapters: the decode path runs on MERGED copies of the adapted weights (W + s B A, csrc/lora.hip),
@@ -655,7 +681,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     x2, B, Sn, t0, kvc[i], Tmax, pos, cos, sin, a.num_heads,
                     lyr.input_layernorm.variance_epsilon, *ws[:7], lyr.input_layernorm.weight,
                     lyr.post_attention_layernorm.weight, *ws[7:], t_dev=t_dev,
-                    w8=w8[i] if w8 is not None and t_dev is not None else None)
+                    w8=w8[i] if w8 is not None and t_dev is not None else None,
+                    kv8=kvs[i] if kvs is not None else None)
             return x2
 
         h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)                 # prefill
@@ -843,7 +870,7 @@ class MM_LLMs(PreTrainedModel):
         if "inference" in inputs and inputs["inference"] is True:
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
-                                     decode_weights=DECODE_WEIGHTS[0])
+                                     decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0])
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -866,6 +893,15 @@ class MM_LLMs(PreTrainedModel):
         if mode not in (None, "fp8"):
             raise ValueError(f"set_decode_weights: mode must be None or 'fp8', got {mode!r}")
         DECODE_WEIGHTS[0] = mode
+
+    @staticmethod
+    def set_kv_cache(mode=None):
+        """KV-cache format of `inputs["inference"] = True` (LlamaForCausalLM.generate's kv_cache): None = 16-bit,
+        "fp8" = e4m3 bytes + one fp32 scale per head and position (half the cache's memory and decode traffic;
+        composes with set_decode_weights).  Process-wide switch, like set_decode_weights."""
+        if mode not in (None, "fp8"):
+            raise ValueError(f"set_kv_cache: mode must be None or 'fp8', got {mode!r}")
+        KV_CACHE[0] = mode
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

@@ -610,6 +610,46 @@ def decode_step_attn(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_max, 
     return out
 
 
+def kv8_cache(B, t_max, H, hd, device):
+    """an empty e4m3 KV cache in the one format of include/macaw_hip.h: (bytes uint8 [B, t_max, 2 * H * hd] =
+    [keys of all heads | values of all heads] per position, scales f32 [B, t_max, 2 * H])"""
+    return (torch.empty((B, t_max, 2 * H * hd), dtype=torch.uint8, device=device),
+            torch.empty((B, t_max, 2 * H), dtype=torch.float32, device=device))
+
+
+def _kv8_check(op, cache, scales, t_max, B, H, hd):
+    if (cache.dtype != torch.uint8 or scales.dtype != torch.float32 or tuple(cache.shape) != (B, t_max, 2 * H * hd)
+            or tuple(scales.shape) != (B, t_max, 2 * H) or not cache.is_contiguous() or not scales.is_contiguous()):
+        raise MacawHipError(f"{op}: cache {cache.dtype} {tuple(cache.shape)}, scales {scales.dtype} "
+                            f"{tuple(scales.shape)}; expected uint8 {(B, t_max, 2 * H * hd)} and float32 "
+                            f"{(B, t_max, 2 * H)}, contiguous")
+
+
+def kv_quant_append(k, v, ld, in_bs, cache, scales, t0, Sn, t_max, B, H, hd):
+    """the prefill's write of an e4m3 KV cache (kv8_cache): Sn rows per sample of the ROTATED keys k and of the values
+    v (16-bit; row pitch ld, sample stride in_bs in elements; k / v may be slices of one fused [M, 3D] buffer) are
+    quantised per head (scale = amax / 448 over hd) into cache rows [t0, t0 + Sn); no other row is touched"""
+    lib = _L.load()
+    _kv8_check("kv_quant_append", cache, scales, t_max, B, H, hd)
+    _L.check(lib.mk_kv_quant_append(_p(k), _p(v), ld, in_bs, _p(cache), _p(scales), t0, Sn, t_max, B, H, hd, dt(k),
+                                    _st()), "mk_kv_quant_append")
+    return cache, scales
+
+
+def decode_step_attn_kv8(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, t_dev, t_max, B, H, hd, out, scale,
+                         q_off=0, k_off=0, v_off=0):
+    """decode_step_attn over an e4m3 KV cache (kv8_cache): RoPE(q, k_new) at position *t_dev + per-head quantisation
+    of the rotated key and of v_new + append of their bytes and scales at cache row *t_dev + attention of the 16-bit
+    q over rows 0 ... *t_dev of the cache as stored after the append (fp32 de-quantisation), one launch"""
+    lib = _L.load()
+    es = q.element_size()
+    _kv8_check("decode_step_attn_kv8", cache, scales, t_max, B, H, hd)
+    _L.check(lib.mk_decode_step_attn_kv8(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es, in_bs,
+                                         _p(cos_t), _p(sin_t), _p(cache), _p(scales), _p(out), H * hd, _p(t_dev),
+                                         t_max, B, H, hd, scale, dt(q), _st()), "mk_decode_step_attn_kv8")
+    return out
+
+
 def decode_attn_ok(dtype, hd, t_max):
     return dtype in (torch.bfloat16, torch.float16) and hd in (16, 32, 64, 128) and t_max * 4 <= 60 * 1024
 

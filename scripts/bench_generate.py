@@ -15,9 +15,41 @@ with torch.no_grad():
 # on THIS model, alternated bf16 / fp8 / bf16 / fp8 ... (R repetitions each, default 3): ms per token of every run, the
 # medians, their ratio, the bf16 run-to-run spread (a difference counts only beyond it) and the achieved weight-stream
 # bandwidth of each mode (fp8 bytes: half the projections' plus f32[N] scales)
+#        bench_generate.py --kv8-ab [--prompt-tokens N] [--reps R] [B ...]: the same alternation for kv_cache=None / "fp8" (the
+# e4m3 KV cache), with the KV bytes a decode step reads in each mode at the middle of the timed window; --prompt-tokens N
+# replaces the 128 text tokens of the prompt (the image and audio prefixes stay), e.g. 1900 for a context near 2048
 AB = "--fp8-ab" in sys.argv
+KV8 = "--kv8-ab" in sys.argv
+_VAL = ("--reps", "--prompt-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--fp8-ab" and a != "--reps" and sys.argv[i - 1] != "--reps"]
+PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else 128
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--kv8-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if KV8:
+    lcfg = model.llm.config
+    NL, D, H = lcfg.num_hidden_layers, lcfg.hidden_size, lcfg.num_attention_heads
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, PROMPT, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {None: [], "fp8": []}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            S0 = emb.shape[1]
+            ctx = S0 + 40                           # keys a step reads at the middle of the timed window (tokens 8 ... 72)
+            kvb = {None: NL * B * ctx * 2 * D * 2, "fp8": NL * B * ctx * (2 * D + 2 * H * 4)}
+            for rep in range(REPS):
+                for mode in (None, "fp8"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, kv_cache=mode)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} S0={S0} rep {rep} kv {mode or 'bf16':4s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = (max(ms[None]) - min(ms[None])) / med[None]
+        print(f"B={B:2d} S0={S0}: kv bf16 {med[None]:6.3f} ms/token ({kvb[None] / 1e9:6.3f} GB of KV per token), kv fp8 "
+              f"{med['fp8']:6.3f} ms/token ({kvb['fp8'] / 1e9:6.3f} GB), fp8 / bf16 = {med['fp8'] / med[None]:5.3f} "
+              f"(bf16 run-to-run spread {spread * 100:4.1f} %)", flush=True)
+    sys.exit(0)
 if AB:
     streamed = [lyr.fused_weights() + (lyr.self_attn.o_proj.weight, lyr.mlp.down_proj.weight) for lyr in model.llm.model.layers]
     streamed = [w for ws in streamed for w in ws] + [model.llm.lm_head.weight]
