@@ -247,7 +247,14 @@ int mk_softmax_bwd(const void* probs, void* dprobs, int32_t nz, int32_t Lq, int3
  * per (batch, head) without materialising the scores (modeling.py:197-215 / HF encoder
  * attention).  q/k/v/o are addressed as base + b*bs + token*ld + h*hd (elements); kmask
  * [B, Lk] int32 (0 = masked) optional; causal masks key > query + (Lk - Lq); lse [B, H, Lq]
- * f32 optional (log-sum-exp of the scaled, masked scores). */
+ * f32 optional (log-sum-exp of the scaled, masked scores).
+ * A query row WITHOUT a visible key (every key padded, or causal with Lq > Lk: rows 0 .. Lq - Lk - 1)
+ * gets o = 0 and lse = -inf, exactly, and mk_flash_attn_bwd gives it dq = 0 and adds nothing to any
+ * dk / dv (a key no query sees gets dk = dv = 0); nothing is NaN.  This deliberately DIFFERS from
+ * mk_softmax_fwd, whose finfo.min masking makes such a row uniform over all Lk keys (the reference's
+ * eager behaviour): the fused kernels drop masked keys before the exponential, so a row that has none
+ * has no weight to spread.  Rows of k / v beyond Lk are never read (a cache with unwritten rows
+ * behind T is safe).  Pinned by tests/test_attention_edges_gpu.py. */
 int mk_flash_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                       const int32_t* kmask, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
                       int32_t hd, int64_t q_ld, int64_t q_bs, int64_t k_ld, int64_t k_bs,
