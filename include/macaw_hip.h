@@ -36,7 +36,7 @@ extern "C" {
 #define MK_FP8 3 /* OCP e4m3fn bytes: mk_gemm operands / mk_fp8_quantize output only */
 
 /* library identification: returns MK_ABI_VERSION */
-#define MK_ABI_VERSION 8
+#define MK_ABI_VERSION 9
 int mk_abi_version(void);
 
 /* ------------------------------------------------------------------ GEMM --
@@ -357,6 +357,28 @@ int mk_decode_linear_fp8(const void* x, int64_t ldx, const void* Wq, int64_t ldw
 int mk_decode_emit(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, int64_t eos,
                    int64_t* tok, void* done, int64_t* out, int64_t out_ld, int32_t* state, int32_t dtype,
                    void* stream);
+/* Sampled decoding (generate(do_sample=True); HF's temperature -> top-k -> top-p warpers and multinomial draw), one
+ *   token per row of logits[rows][V] (pitch ld; columns [V, ld) are never read):
+ *   1. x_c = float(logit_c) / temperature in fp32; a NaN or -inf logit is never drawn, and a row without a finite logit
+ *      emits what mk_argmax_rows emits.
+ *   2. top_k, when 0 < top_k < V: exactly top_k columns stay, the largest values, ties at the k-th value to the LOWER
+ *      column (top_k = 1 is greedy; HF keeps the whole tie group).  0 switches it off.
+ *   3. top_p, when top_p < 1, over the survivors: with e_c = exp(x_c - x_max) and Z their sum, column c stays iff
+ *      sum{e_j : x_j > x_c} < top_p * Z (HF's rule by value: the top value always stays, a tie group stays or goes whole).
+ *   4. u = ((mk_hash32(seed, (uint64(step) << 32) | row) >> 8) + 0.5) * 2^-24 (the counter hash of the dropout masks); the
+ *      token is the first kept column, in column order, whose inclusive cumulative mass exceeds u * Z_kept.
+ *   Selection is an exact radix select; masses are 2^-40 fixed-point integers, so every sum is an integer sum and the
+ *   result is bitwise reproducible.  bf16 / f16 / f32.  MK_ERR_BAD_ARG: null pointers, rows <= 0, V <= 0, ld < V,
+ *   temperature <= 0 or not finite, top_p outside (0, 1], top_k < 0.  V <= 2^23, else MK_ERR_UNSUPPORTED.
+ * mk_sample_rows: out_ids[row] = that token, the sampled twin of mk_argmax_rows.
+ * mk_decode_emit_sample: mk_decode_emit with the argmax replaced by that draw for the samples not yet finished, row = b
+ *   and step = state[1] (the output column, read on the device: a captured step draws a fresh number on every replay);
+ *   pad, eos, tok, done, out and the state hand-off exactly as mk_decode_emit. */
+int mk_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                   float top_p, uint64_t seed, int32_t step, int64_t* out_ids, int32_t dtype, void* stream);
+int mk_decode_emit_sample(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, int64_t eos,
+                          int64_t* tok, void* done, int64_t* out, int64_t out_ld, int32_t* state, float temperature,
+                          int32_t top_k, float top_p, uint64_t seed, int32_t dtype, void* stream);
 /* mk_decode_step_attn: the attention block of one decode step in one launch: p = clamp(*t_dev, 0,
  *   t_max - 1); q and k_new (rows [H * hd] at batch stride in_bs) are rotated with rows p of the
  *   [positions][hd] cos / sin tables (modeling.py:76-91, rope rounding points of mk_rope); the rotated

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import copy
 import math
+import numbers
 import os
 from typing import List, Optional, Tuple, Union
 
@@ -56,6 +57,20 @@ AUTO_FUSE = os.environ.get("MACAW_NO_AUTO_FUSE") is None
 DECODE_WEIGHTS = [None]
 # MM_LLMs.set_kv_cache: the kv_cache MM_LLMs.forward hands to generate() (None or "fp8")
 KV_CACHE = [None]
+# MM_LLMs.set_sampling: the sampling arguments MM_LLMs.forward hands to generate()
+SAMPLING = [dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None)]
+
+
+def _sampling_check(where, temperature, top_k, top_p):
+    """the sampling arguments of generate(do_sample=True) / set_sampling -> (temperature, top_k with 0 = off, top_p)"""
+    if not (isinstance(temperature, numbers.Real) and math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"{where}: temperature must be a finite number > 0, got {temperature!r}")
+    if not (isinstance(top_p, numbers.Real) and 0 < top_p <= 1):
+        raise ValueError(f"{where}: top_p must lie in (0, 1], got {top_p!r}")
+    top_k = 0 if top_k is None else top_k
+    if not isinstance(top_k, numbers.Integral) or top_k < 0:
+        raise ValueError(f"{where}: top_k must be None or an integer >= 0, got {top_k!r}")
+    return float(temperature), int(top_k), float(top_p)
 
 
 def _rows_view(ts):
@@ -459,13 +474,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                       hidden_states=None, attentions=None)
 
     @torch.no_grad()
-    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev):
+    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
         memory -- the position (int32 counter read by the fused RoPE + cache append + attention
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
         by ops.decode_emit) -- so the launches of a step (5 per layer + 3) are captured once, after
         one eager step that also serves as the warm-up, and replayed; the host only looks at the
-        finished flags every few tokens."""
+        finished flags every few tokens.  sample = (temperature, top_k, top_p, seed): ops.decode_emit_sample draws the
+        token instead, its random number a hash of (seed, output column, sample) computed on the device."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         tok = torch.zeros(B, dtype=torch.long, device=dev)
@@ -474,7 +490,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         V = self.lm_head.weight.shape[0]
 
         def emit(h_last):                # argmax, pad / eos handling, output column, position += 1
-            ops.decode_emit(logits(h_last), V, pad, eos, tok, done, out_buf, state)
+            if sample is not None:
+                ops.decode_emit_sample(logits(h_last), V, pad, eos, tok, done, out_buf, state, *sample)
+            else:
+                ops.decode_emit(logits(h_last), V, pad, eos, tok, done, out_buf, state)
 
         def step():
             emit(run(ops.embedding_fwd(emb_w, tok), 1, 0, pos=t_dev, t_dev=t_dev))
@@ -532,8 +551,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
-                 kv_cache=None, **_):
-        """Greedy decode — the only mode the reference uses (modeling.py:959:
+                 kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, **_):
+        """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
         preallocated per-layer KV cache [B, T_max, D]; every decode step runs one position
@@ -565,11 +584,29 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         needs the hipGraph decode path and raises ValueError naming the condition otherwise (fp32 parameters,
         use_cache=False, decode_graph=False or MACAW_NO_DECODE_GRAPH, max_new_tokens <= 2, a head size / length
         outside ops.decode_attn_ok); any batch size, fused or unfused projection storage.  None (default): the 16-bit
-        cache."""
+        cache.
+
+        do_sample=True: sampled decoding with HF's defaults and warper order -- logits / temperature, then top_k (0 or
+        None = off, as is top_k >= vocabulary), then top_p over the survivors, then one draw per sample (ops.sample_rows;
+        on the hipGraph path ops.decode_emit_sample, the random number computed on the device from the output column, so
+        the host still does not touch a step).  The random number of (sample b, new token t) is a counter hash of
+        (seed, t, b): the same seed gives the same ids, call after call and on every decode path by itself (the paths'
+        logits differ in their last bits, so ids may differ BETWEEN paths where a draw falls on a boundary).  seed=None
+        draws a 63-bit seed from torch's default CPU generator (torch.manual_seed governs it); an integer is used as
+        given.  One difference to HF: top_k keeps EXACTLY k columns, ties at the k-th value going to the lower column
+        (HF keeps the whole tie group), which makes top_k=1 greedy.  temperature <= 0, top_p outside (0, 1] and a
+        negative top_k raise ValueError.  With do_sample=False (default) the four arguments are ignored and not one
+        launch differs.  Composes with decode_weights, kv_cache and LoRA (they only change where the logits come from)."""
         if decode_weights not in (None, "fp8"):
             raise ValueError(f"generate: decode_weights must be None or 'fp8', got {decode_weights!r}")
         if kv_cache not in (None, "fp8"):
             raise ValueError(f"generate: kv_cache must be None or 'fp8', got {kv_cache!r}")
+        sample = None
+        if do_sample:
+            temperature, top_k, top_p = _sampling_check("generate", temperature, top_k, top_p)
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+            sample = (temperature, top_k, top_p, int(seed))
         emb_w = self.model.embed_tokens.weight
         if inputs_embeds is None:
             inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(*input_ids.shape, -1)
@@ -599,12 +636,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
             return ops.linear_fwd(y, self.lm_head.weight)
 
-        def select(h_last):       # h_last [B, D] -> next token ids [B]
+        def select(h_last, t):    # h_last [B, D] -> ids [B] of new token t
+            if sample is not None:
+                return ops.sample_rows(logits(h_last), V, *sample, step=t)
             return ops.argmax_rows(logits(h_last), V)
 
         if not use_cache:
             emb = inputs_embeds.contiguous()
-            for _ in range(max_new_tokens):
+            for t in range(max_new_tokens):
                 S = emb.shape[1]
                 self.model._defer_final_norm = True
                 try:
@@ -614,7 +653,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 last = torch.empty((B, D), dtype=dtype, device=dev)
                 ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=B, s_src=S * D, s_dst=D,
                            src_off=(S - 1) * D)
-                nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last))
+                nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
                 out.append(nxt)
                 done = done | (nxt == eos_token_id)
                 if bool(done.all()):
@@ -691,9 +730,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         hd = D // layers[0].self_attn.num_heads
         if (decode_graph and max_new_tokens > 2 and ops.decode_attn_ok(dtype, hd, Tmax)
                 and not os.environ.get("MACAW_NO_DECODE_GRAPH")):
-            return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev)
+            return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample)
         for t in range(max_new_tokens):
-            nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last))
+            nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
             out.append(nxt)
             done = done | (nxt == eos_token_id)
             if t + 1 == max_new_tokens or bool(done.all()):
@@ -870,7 +909,7 @@ class MM_LLMs(PreTrainedModel):
         if "inference" in inputs and inputs["inference"] is True:
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
-                                     decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0])
+                                     decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0], **SAMPLING[0])
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -902,6 +941,16 @@ class MM_LLMs(PreTrainedModel):
         if mode not in (None, "fp8"):
             raise ValueError(f"set_kv_cache: mode must be None or 'fp8', got {mode!r}")
         KV_CACHE[0] = mode
+
+    @staticmethod
+    def set_sampling(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None):
+        """Token selection of `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the same names):
+        greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution, seed=None
+        taking a fresh seed from torch's default generator at every call.  Validated here when do_sample is set.
+        Process-wide switch, like set_decode_weights and set_kv_cache."""
+        if do_sample:
+            _sampling_check("set_sampling", temperature, top_k, top_p)
+        SAMPLING[0] = dict(do_sample=bool(do_sample), temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

@@ -595,6 +595,17 @@ def decode_emit(logits, V, pad, eos, tok, done, out, state):
                                 out.stride(0), _p(state), dt(logits), _st()), "mk_decode_emit")
 
 
+def decode_emit_sample(logits, V, pad, eos, tok, done, out, state, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    """decode_emit with the argmax replaced by a draw (see mk_decode_emit_sample): temperature, top-k (0 = off),
+    top-p, and the counter hash of (seed, state[1], sample) as the random number -- the same ids as
+    sample_rows(step=state[1]) on the same logits"""
+    lib = _L.load()
+    B = logits.shape[0]
+    _L.check(lib.mk_decode_emit_sample(_p(logits), _rowmajor(logits), V, B, pad, eos, _p(tok), _p(done), _p(out),
+                                       out.stride(0), _p(state), float(temperature), int(top_k), float(top_p),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, dt(logits), _st()), "mk_decode_emit_sample")
+
+
 def decode_step_attn(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_max, B, H, hd, out, scale,
                      q_off=0, k_off=0, v_off=0):
     """RoPE(q, k_new) at position *t_dev + append [k_new | v_new] to cache [B, t_max, 2 * H * hd] row
@@ -839,6 +850,19 @@ def argmax_rows(x, cols=None):
     out = torch.empty(rows, dtype=torch.int64, device=x.device)
     _L.check(lib.mk_argmax_rows(_p(x), _rowmajor(x), rows, cols, _p(out), dt(x), _st()),
              "mk_argmax_rows")
+    return out
+
+
+def sample_rows(x, cols=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0):
+    """one sampled column per row of a 2-D row-major (pitched) tensor -> int64 [rows] (see mk_sample_rows): temperature,
+    then top-k (0 = off; exactly k columns, ties to the lower column), then top-p, then the draw with the counter hash
+    of (seed, step, row); the sampled twin of argmax_rows"""
+    lib = _L.load()
+    rows = x.shape[0]
+    cols = x.shape[1] if cols is None else cols
+    out = torch.empty(rows, dtype=torch.int64, device=x.device)
+    _L.check(lib.mk_sample_rows(_p(x), _rowmajor(x), rows, cols, float(temperature), int(top_k), float(top_p),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _p(out), dt(x), _st()), "mk_sample_rows")
     return out
 
 

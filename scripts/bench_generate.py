@@ -18,12 +18,56 @@ with torch.no_grad():
 #        bench_generate.py --kv8-ab [--prompt-tokens N] [--reps R] [B ...]: the same alternation for kv_cache=None / "fp8" (the
 # e4m3 KV cache), with the KV bytes a decode step reads in each mode at the middle of the timed window; --prompt-tokens N
 # replaces the 128 text tokens of the prompt (the image and audio prefixes stay), e.g. 1900 for a context near 2048
+#        bench_generate.py --sample-ab [--reps R] [B ...]: greedy against do_sample=True, top_k=50, top_p=0.9 (seed 1), alternated
+# the same way: ms per token of every run, the medians, their difference and the greedy run-to-run spread (the difference
+# counts only beyond it), then the stand-alone time of one ops.sample_rows launch against ops.argmax_rows on [B, 32000] logits
 AB = "--fp8-ab" in sys.argv
+SAMPLE = "--sample-ab" in sys.argv
 KV8 = "--kv8-ab" in sys.argv
 _VAL = ("--reps", "--prompt-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else 128
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--kv8-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--kv8-ab", "--sample-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if SAMPLE:
+    from macaw_llm_amd import ops
+    SKW = dict(do_sample=True, top_k=50, top_p=0.9, seed=1)
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {"greedy": [], "sample": []}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for rep in range(REPS):
+                for mode in ("greedy", "sample"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, **(SKW if mode == "sample" else {}))
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {mode:6s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = max(ms["greedy"]) - min(ms["greedy"])
+        diff = med["sample"] - med["greedy"]
+        print(f"B={B:2d}: greedy {med['greedy']:6.3f} ms/token, sampled {med['sample']:6.3f} ms/token, sampled - greedy = {diff * 1e3:+7.1f} us "
+              f"({diff / med['greedy'] * 100:+5.2f} %), greedy run-to-run spread {spread * 1e3:6.1f} us ({spread / med['greedy'] * 100:4.1f} %): "
+              f"{'inside' if abs(diff) <= spread else 'OUTSIDE'} the spread", flush=True)
+        # one selection launch by itself: 200 back-to-back launches between two events, after 20 warm-up launches
+        x = torch.randn(B, 32000, device=dev).mul_(3).to(torch.bfloat16)
+        us = {}
+        for name, fn in (("argmax_rows", lambda i: ops.argmax_rows(x)),
+                         ("sample_rows k=50 p=0.9", lambda i: ops.sample_rows(x, None, 1.0, 50, 0.9, 1, i)),
+                         ("sample_rows k=0 p=1", lambda i: ops.sample_rows(x, None, 1.0, 0, 1.0, 1, i))):
+            for i in range(20):
+                fn(i)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn(i)
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
+        print(f"B={B:2d}: one launch on [B, 32000] bf16 logits (back to back, incl. launch gaps): " +
+              ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if KV8:
     lcfg = model.llm.config
     NL, D, H = lcfg.num_hidden_layers, lcfg.hidden_size, lcfg.num_attention_heads
