@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -560,6 +561,21 @@ class LlamaLayerFn(torch.autograd.Function):
                 dwd, dln1 if need[14] else None, dln2 if need[15] else None, None, None, None)
 
 
+class LayerWeights(NamedTuple):
+    """the projection weights of one decoder layer, in llama_layer_cached's order (its two norm weights go between wd
+    and wqkv): the seven [out, in] matrices, and the fused q|k|v [3D, D] / gate|up [2 FF, D] buffers that wq, wk, wv /
+    wg, wu are row slices of where the storage is fused (else None)"""
+    wq: torch.Tensor
+    wk: torch.Tensor
+    wv: torch.Tensor
+    wo: torch.Tensor
+    wg: torch.Tensor
+    wu: torch.Tensor
+    wd: torch.Tensor
+    wqkv: Optional[torch.Tensor]
+    wgu: Optional[torch.Tensor]
+
+
 def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off):
     """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
     e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8"""
@@ -568,36 +584,24 @@ def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, s
     return ops.decode_step_attn(q, k, v, in_bs, cos, sin, kvc, t_dev, Tmax, B, H, hd, att, scale, **off)
 
 
-def _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, FF, wo, wd, ln1, ln2, wqkv, wgu, t_dev, w8,
-                          kv8=None):
-    """llama_layer_cached's five-launch decode step with the four linear launches on e4m3 weight copies.
-    Where the prepared token rows of a prologue form do not fit the kernel's LDS budget (M > 4 at K = 4096) the
-    separate RMSNorm / SwiGLU kernel runs first, as in the 16-bit step, and the PLAIN fp8 launch follows: every
-    batch size up to 32 streams e4m3 bytes."""
-    M, D = x2.shape
-    H, hd = n_heads, D // n_heads
-    q_qkv, q_o, q_gu, q_d = w8
-
-    def linear(x, W, q8, pro, w_ln=None, residual=None):
-        if q8 is not None and ops.decode_linear_fp8_ok(x, q8[0], pro):
-            return ops.decode_linear_fp8(x, q8[0], q8[1], pro, w_ln, eps, residual)
-        if q8 is None and ops.decode_linear_ok(x, W, pro):
-            return ops.decode_linear(x, W, pro, w_ln, eps, residual)
-        if pro == 1:
-            x = ops.rmsnorm_fwd(x, w_ln, eps)[1]
-        elif pro == 2:
-            x = ops.swiglu2d_fwd(x, FF)
-        if q8 is not None:
-            return ops.decode_linear_fp8(x, q8[0], q8[1], residual=residual)
-        return ops.linear_fwd(x, W, residual=residual)
-
-    qkv = linear(x2, wqkv, q_qkv, 1, ln1)
-    att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
-    _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att,
-               1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
-    h1 = linear(att, wo, q_o, 0, residual=x2)
-    gu = linear(h1, wgu, q_gu, 1, ln2)
-    return linear(gu, wd, q_d, 2, residual=h1)
+def _stream_linear(x, W, q8, pro, w_ln, eps, residual, FF):
+    """y = pro(x) W^T (+ residual) for the few token rows of a decode step, the weight streamed once: W 16-bit, or
+    q8 = its e4m3 copy (q uint8 [N, K], scales f32 [N]) where that is not None.  The prologue pro (1 = RMSNorm(x;
+    w_ln, eps), 2 = SwiGLU of x = [gate | up] [M, 2 FF], 0 = none) is folded into the weight stream where the
+    prepared token rows fit the kernel's LDS budget (ops.decode_linear_ok: not for M > 4 at K = 4096); otherwise the
+    separate RMSNorm / SwiGLU kernel runs first and the PLAIN launch follows, so every batch size up to 32 streams
+    the bytes it was given.  A 16-bit weight outside ops.decode_linear's domain goes through ops.linear_fwd."""
+    if q8 is not None and ops.decode_linear_fp8_ok(x, q8[0], pro):
+        return ops.decode_linear_fp8(x, q8[0], q8[1], pro, w_ln, eps, residual)
+    if q8 is None and ops.decode_linear_ok(x, W, pro):
+        return ops.decode_linear(x, W, pro, w_ln, eps, residual)
+    if pro == 1:
+        x = ops.rmsnorm_fwd(x, w_ln, eps)[1]
+    elif pro == 2:
+        x = ops.swiglu2d_fwd(x, FF)
+    if q8 is not None:
+        return ops.decode_linear_fp8(x, q8[0], q8[1], residual=residual)
+    return ops.linear_fwd(x, W, residual=residual)
 
 
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
@@ -631,82 +635,61 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
                          f"steps (t_dev), not {Sn} new positions at t0 = {t0}")
     if dyn and Sn != 1:
         raise ValueError("llama_layer_cached: t_dev is for single-position decode steps")
-    if w8 is not None:
-        if not (dyn and wqkv is not None and wgu is not None and ops.decode_linear_ok(x2, wqkv)):
-            raise ValueError("llama_layer_cached: w8 is for the five-launch decode step (t_dev, fused q|k|v and "
-                             "gate|up storage, at most 32 rows)")
-        return _llama_layer_step_fp8(x2, B, kvc, Tmax, cos, sin, n_heads, eps, wg.shape[0], wo, wd, ln1, ln2,
-                                     wqkv, wgu, t_dev, w8, kv8)
-    if dyn and wqkv is not None and wgu is not None and ops.decode_linear_ok(x2, wqkv):
-        # five launches: RMSNorm folded into the q|k|v and gate|up weight streams, SwiGLU into down's
-        # (each where the prepared token rows fit the kernel's LDS budget, else the separate kernel)
-        H, hd = n_heads, D // n_heads
-
-        def norm_linear(x, w_ln, W):
-            if ops.decode_linear_ok(x, W, 1):
-                return ops.decode_linear(x, W, 1, w_ln, eps)
-            return ops.linear_fwd(ops.rmsnorm_fwd(x, w_ln, eps)[1], W)
-
-        qkv = norm_linear(x2, ln1, wqkv)
-        att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
-        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att,
-                   1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
-        h1 = ops.decode_linear(att, wo, residual=x2)
-        gu = norm_linear(h1, ln2, wgu)
-        if ops.decode_linear_ok(gu, wd, 2):
-            return ops.decode_linear(gu, wd, 2, residual=h1)
-        return ops.linear_fwd(ops.swiglu2d_fwd(gu, wg.shape[0]), wd, residual=h1)
+    step = dyn and wqkv is not None and wgu is not None and ops.decode_linear_ok(x2, wqkv)
+    if w8 is not None and not step:
+        raise ValueError("llama_layer_cached: w8 is for the five-launch decode step (t_dev, fused q|k|v and "
+                         "gate|up storage, at most 32 rows)")
     H, hd = n_heads, D // n_heads
     FF = wg.shape[0]
-    _, y1, _ = ops.rmsnorm_fwd(x2, ln1, eps)
-    ldc = 2 * D
     att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
     scale = 1.0 / math.sqrt(hd)
-    if wqkv is not None:
+    if step:
+        # five launches: RMSNorm folded into the q|k|v and gate|up weight streams, SwiGLU into down's, each weight
+        # 16-bit or (w8) its e4m3 copy: _stream_linear.  o asks ops.decode_linear_ok like the other three, with or
+        # without w8; under the gate above that matters only for a non-contiguous wo, which takes ops.linear_fwd.
+        q_qkv, q_o, q_gu, q_d = w8 if w8 is not None else (None,) * 4
+        qkv = _stream_linear(x2, wqkv, q_qkv, 1, ln1, eps, None, FF)
+        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, k_off=D, v_off=2 * D)
+        h1 = _stream_linear(att, wo, q_o, 0, None, eps, x2, FF)
+        gu = _stream_linear(h1, wgu, q_gu, 1, ln2, eps, None, FF)
+        return _stream_linear(gu, wd, q_d, 2, None, eps, h1, FF)
+    _, y1, _ = ops.rmsnorm_fwd(x2, ln1, eps)
+    ldc = 2 * D
+    # the layout of the new q, k, v, decided once: what the step kernel reads, what RoPE rotates (tensor, heads) and
+    # what the cache append copies (source, columns, source offset, cache column)
+    if wqkv is not None:        # fused: column blocks of ONE [M, 3D] buffer, one RoPE launch, one copy of [k | v]
         qkv = ops.linear_fwd(y1, wqkv)
-        q = qkv[:, :D]
         ldq = 3 * D
-        if dyn:     # RoPE + cache append + attention of the new position: one launch
-            _step_attn(qkv, qkv, qkv, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale,
-                       k_off=D, v_off=2 * D)
-        else:
-            ops.rope_(qkv[:, :2 * D], cos, sin, pos, 2 * H, hd)
-            k, v = qkv[:, D:2 * D], qkv[:, 2 * D:]
-            if kv8 is None:
-                ops.copy2d(qkv, kvc, Sn, 2 * D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, src_off=D,
-                           dst_off=t0 * ldc)
+        q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
+        new, off = (qkv, qkv, qkv), {"k_off": D, "v_off": 2 * D}
+        ropes, appends = ((qkv[:, :2 * D], 2 * H),), ((qkv, 2 * D, D, 0),)
     else:
         q, k, v = ops.linear_fwd(y1, wq), ops.linear_fwd(y1, wk), ops.linear_fwd(y1, wv)
         ldq = D
-        if dyn:
-            _step_attn(q, k, v, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale)
-        else:
-            ops.rope_(q, cos, sin, pos, H, hd)
-            ops.rope_(k, cos, sin, pos, H, hd)
-            if kv8 is None:
-                # append the new keys / values to the cache rows [t0, t0 + Sn) of every sample
-                ops.copy2d(k, kvc, Sn, D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, dst_off=t0 * ldc)
-                ops.copy2d(v, kvc, Sn, D, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, dst_off=t0 * ldc + D)
-    kc, vc = kvc[:, :, :D], kvc[:, :, D:]
-    T = t0 + Sn
-    if dyn:
-        pass
-    elif kv8 is not None:
-        # e4m3 cache, prefill: causal attention over the prompt's own 16-bit q, k, v (read at the ldq pitch), then the
-        # quantising cache write
-        if flash_ok(x2.dtype, hd):
-            ops.flash_attn_fwd(q, k, v, att, B, H, Sn, Sn, hd, ldq, Sn * ldq, ldq, Sn * ldq, ldq, Sn * ldq,
-                               D, Sn * D, scale, causal=True)
-        else:
-            attention_fwd(TDesc(q, ldq, Sn * ldq), TDesc(k, ldq, Sn * ldq), TDesc(v, ldq, Sn * ldq),
-                          TDesc(att, D, Sn * D), B, H, Sn, Sn, hd, scale, causal=True)
-        ops.kv_quant_append(k, v, ldq, Sn * ldq, kvc, kv8, 0, Sn, Tmax, B, H, hd)
-    elif flash_ok(x2.dtype, hd):
-        ops.flash_attn_fwd(q, kc, vc, att, B, H, Sn, T, hd, ldq, Sn * ldq, ldc, Tmax * ldc, ldc, Tmax * ldc,
-                           D, Sn * D, scale, causal=True)
+        new, off = (q, k, v), {}
+        ropes, appends = ((q, H), (k, H)), ((k, D, 0, 0), (v, D, 0, D))
+    if dyn:     # RoPE + cache append + attention of the new position: one launch
+        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off)
     else:
-        attention_fwd(TDesc(q, ldq, Sn * ldq), TDesc(kvc, ldc, Tmax * ldc, 0), TDesc(kvc, ldc, Tmax * ldc, D),
-                      TDesc(att, D, Sn * D), B, H, Sn, T, hd, scale, causal=True)
+        for t, heads in ropes:
+            ops.rope_(t, cos, sin, pos, heads, hd)
+        if kv8 is None:
+            # append the new keys / values to the cache rows [t0, t0 + Sn) of every sample, attend over rows [0, t0 + Sn)
+            for src, cols, src_off, col in appends:
+                ops.copy2d(src, kvc, Sn, cols, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, src_off=src_off,
+                           dst_off=t0 * ldc + col)
+            kd, vd, Lk = TDesc(kvc, ldc, Tmax * ldc, 0), TDesc(kvc, ldc, Tmax * ldc, D), t0 + Sn
+        else:
+            # e4m3 cache, prefill: causal attention over the prompt's own 16-bit k, v (read at the ldq pitch), then the
+            # quantising cache write
+            kd, vd, Lk = TDesc(k, ldq, Sn * ldq), TDesc(v, ldq, Sn * ldq), Sn
+        if flash_ok(x2.dtype, hd):      # (takes views: the D columns at the operand's offset)
+            ops.flash_attn_fwd(q, kd.t[..., kd.off:kd.off + D], vd.t[..., vd.off:vd.off + D], att, B, H, Sn, Lk, hd,
+                               ldq, Sn * ldq, kd.ld, kd.bs, vd.ld, vd.bs, D, Sn * D, scale, causal=True)
+        else:
+            attention_fwd(TDesc(q, ldq, Sn * ldq), kd, vd, TDesc(att, D, Sn * D), B, H, Sn, Lk, hd, scale, causal=True)
+        if kv8 is not None:
+            ops.kv_quant_append(k, v, ldq, Sn * ldq, kvc, kv8, 0, Sn, Tmax, B, H, hd)
     h1 = ops.linear_fwd(att, wo, residual=x2)
     _, y2, _ = ops.rmsnorm_fwd(h1, ln2, eps)
     if wgu is not None:

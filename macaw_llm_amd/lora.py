@@ -239,8 +239,8 @@ def merged_weight(lin, s, out=None):
 
 @torch.no_grad()
 def merged_layer_weights(model, layer):
-    """(layer, (wq, wk, wv, wo, wg, wu, wd, wqkv, wgu)) with every adapted projection replaced by a merged COPY
-    (W + s B A); fused q|k|v / gate|up buffers are copied whole so that the one-GEMM decode path stays"""
+    """(layer, engine.LayerWeights) with every adapted projection replaced by a merged COPY (W + s B A); fused
+    q|k|v / gate|up buffers are copied whole so that the one-GEMM decode path stays"""
     s = model._lora.config.scaling
     a, m = layer.self_attn, layer.mlp
     lins = (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj)
@@ -264,7 +264,7 @@ def merged_layer_weights(model, layer):
     for i, lin in ad.items():
         if ws[i] is lin.weight:
             ws[i] = merged_weight(lin, s, lin.weight.detach().clone())
-    return layer, (*ws, wqkv, wgu)
+    return layer, eng.LayerWeights(*ws, wqkv, wgu)
 
 
 @torch.no_grad()

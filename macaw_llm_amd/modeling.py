@@ -626,13 +626,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         w8_head = None            # decode_weights="fp8": (q, scales) of the lm_head
 
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
-            if w8_head is not None and h_last.is_contiguous():
-                if ops.decode_linear_fp8_ok(h_last, w8_head[0], 1):
-                    return ops.decode_linear_fp8(h_last, *w8_head, 1, self.model.norm.weight, eps)
-                _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
-                return ops.decode_linear_fp8(y, *w8_head)
-            if h_last.is_contiguous() and ops.decode_linear_ok(h_last, self.lm_head.weight, 1):
-                return ops.decode_linear(h_last, self.lm_head.weight, 1, self.model.norm.weight, eps)
+            if h_last.is_contiguous():
+                return eng._stream_linear(h_last, self.lm_head.weight, w8_head, 1, self.model.norm.weight, eps, None, 0)
             _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
             return ops.linear_fwd(y, self.lm_head.weight)
 
@@ -685,6 +680,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         else:
             merged = {}
 
+        stored = []               # per layer its own parameters, as the engine's named weight set
+        for lyr in layers:
+            a, m = lyr.self_attn, lyr.mlp
+            stored.append(eng.LayerWeights(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight,
+                                           m.up_proj.weight, m.down_proj.weight, *lyr.fused_weights()))
+
         w8 = None                 # decode_weights="fp8": per layer the copies of q|k|v, o, gate|up, down
         if decode_weights == "fp8":
             probe = torch.empty((B, 0), dtype=dtype, device=dev)
@@ -695,31 +696,23 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 return ops.fp8_weight(W) if own is not None and own.data_ptr() == W.data_ptr() else ops.quantize_fp8_rows(W)
 
             w8 = []
-            for lyr in layers:
-                a, m = lyr.self_attn, lyr.mlp
-                own = (*lyr.fused_weights(), a.o_proj.weight, m.down_proj.weight)
-                if own[0] is None or own[1] is None:
+            for lyr, own in zip(layers, stored):
+                if own.wqkv is None or own.wgu is None:
                     raise ValueError("generate(decode_weights='fp8'): unfused q/k/v or gate/up storage (the fp8 "
                                      "decode step streams the fused q|k|v and gate|up weights: fuse_projections())")
-                ws = merged.get(lyr)
-                cur = (ws[7], ws[8], ws[3], ws[6]) if ws is not None else own
-                w8.append((q8(cur[0], own[0]), q8(cur[2], own[2]), q8(cur[1], own[1]), q8(cur[3], own[3])))
+                ws = merged.get(lyr, own)
+                w8.append((q8(ws.wqkv, own.wqkv), q8(ws.wo, own.wo), q8(ws.wgu, own.wgu), q8(ws.wd, own.wd)))
             w8_head = q8(self.lm_head.weight, self.lm_head.weight)
 
         def run(x2, Sn, t0, pos=None, t_dev=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
             for i, lyr in enumerate(layers):
-                a, m = lyr.self_attn, lyr.mlp
-                if lyr in merged:
-                    ws = merged[lyr]
-                else:
-                    ws = (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight,
-                          m.up_proj.weight, m.down_proj.weight, *lyr.fused_weights())
+                ws = merged.get(lyr, stored[i])
                 x2 = eng.llama_layer_cached(
-                    x2, B, Sn, t0, kvc[i], Tmax, pos, cos, sin, a.num_heads,
-                    lyr.input_layernorm.variance_epsilon, *ws[:7], lyr.input_layernorm.weight,
-                    lyr.post_attention_layernorm.weight, *ws[7:], t_dev=t_dev,
+                    x2, B, Sn, t0, kvc[i], Tmax, pos, cos, sin, lyr.self_attn.num_heads,
+                    lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
+                    lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
                     w8=w8[i] if w8 is not None and t_dev is not None else None,
                     kv8=kvs[i] if kvs is not None else None)
             return x2

@@ -580,9 +580,7 @@ def decode_linear_fp8(x, Wq, s, prologue=0, norm_w=None, eps=0.0, residual=None,
 def decode_linear_fp8_ok(x, Wq, prologue=0):
     """mk_decode_linear_fp8's domain (Wq: the e4m3 copy, or the [N, K] 16-bit weight it will be made from); with
     a prologue the prepared token rows must fit 40 KiB of LDS"""
-    M, K = x.shape[0], Wq.shape[1]
-    return (x.dtype in (torch.bfloat16, torch.float16) and M <= (16 if prologue else 32) and K % 64 == 0
-            and Wq.is_contiguous() and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
+    return decode_linear_ok(x, Wq, prologue)       # one kernel skeleton, one domain: only the weight bytes differ
 
 
 def decode_emit(logits, V, pad, eos, tok, done, out, state):
