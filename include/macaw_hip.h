@@ -77,7 +77,9 @@ typedef struct mk_gemm_desc {
                          arrival counters); NULL disables it. Must not be shared by GEMMs that
                          run concurrently on different streams.  Its first 4096 bytes (the
                          counters) must be ZERO before the first use; every launch leaves
-                         them zero again (the last arriver of a tile resets its counter). */
+                         them zero again (the last arriver of a tile resets its counter).  A
+                         workspace too small for a split (4096 + tail tiles x pieces x 64 KiB)
+                         runs the tail unsplit.  Pinned by tests/test_gemm_plans_gpu.py. */
   int64_t ws_bytes;
   const float* scale_a; /* optional DEVICE scalars multiplied into alpha in the epilogue (the     */
   const float* scale_b; /* per-tensor de-quantisation scales of fp8 operands; no host sync)       */
@@ -108,7 +110,8 @@ int mk_gemm_has_cfg(int cfg);
  * gradient reduce-scatter running beside the backward (train.sh:14, configs/deepspeed_config.json:22-41) -- is
  * lost to them: rounds of exactly 256 tiles then take two passes.  The step runtime sets this to
  * (CUs - collective channels) while collectives overlap the backward; round sizes, the spatial tail and the
- * kernel choice follow.  Returns the previous value. */
+ * kernel choice follow.  Values at or above the device's CU count mean all as well.  Returns the previous value.
+ * Pinned by tests/test_gemm_plans_gpu.py. */
 int mk_gemm_set_cus(int n_cus);
 /* Optional live timing of every mk_gemm launch with HIP events on the launch stream
  * (bench.py roofline): begin, run, then end() synchronises and returns the sums. */
