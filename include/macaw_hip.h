@@ -420,6 +420,35 @@ int mk_decode_step_attn_kv8(const void* q, const void* k_new, const void* v_new,
                             const void* sin_t, void* cache, float* scales, void* o, int64_t o_bs,
                             const int32_t* t_dev, int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale,
                             int32_t dtype, void* stream);
+/* Padded batches (generate(attention_mask=)): a ragged, compacted KV cache.  Sample b holds its n_b valid prompt
+ *   tokens in cache rows 0 ... n_b - 1 and its new token t in row n_b + t, while the step state keeps ONE device
+ *   counter *t_dev for the batch.
+ * mk_decode_step_attn_var / mk_decode_step_attn_kv8_var: mk_decode_step_attn / mk_decode_step_attn_kv8 at a position
+ *   per sample, p_b = clamp(*t_dev + t_off[b], 0, t_max - 1), t_off int32 [B] on the device: RoPE at table row p_b,
+ *   append at cache row p_b, attention over rows 0 ... p_b; no row past p_b is read.  The same kernel bodies and the
+ *   same kernel selection: a sample's output and appended row are bit-identical to the plain entry point's at
+ *   *t_dev = p_b over the same cache.  Domain of the plain entry points; t_off null is MK_ERR_BAD_ARG.
+ * mk_kv_append_rows / mk_kv_quant_append_rows: the prefill's compacting cache write.  k (already rotated) and v: Sn
+ *   rows [H * hd] per sample, bf16 or f16, row pitch ld and sample stride in_bs (elements; slices of a fused [M][3D]
+ *   buffer work).  Source row j of sample b goes to cache row slot[b * Sn + j] (int32, device); a row whose slot is
+ *   negative or >= t_max is skipped, and no other cache byte is touched.  mk_kv_append_rows: the 16-bit cache
+ *   [B][t_max][2 * H * hd] = [keys | values], a pure copy in 16-byte pieces.  mk_kv_quant_append_rows: the e4m3 cache
+ *   above, bytes and scales of a written row identical to mk_kv_quant_append's for that source row.  Two source rows
+ *   of a sample with the same slot: one of them wins.  Domain as mk_kv_quant_append. */
+int mk_decode_step_attn_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                            const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                            int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
+                            const int32_t* t_off, int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale,
+                            int32_t dtype, void* stream);
+int mk_decode_step_attn_kv8_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                                const void* cos_t, const void* sin_t, void* cache, float* scales, void* o,
+                                int64_t o_bs, const int32_t* t_dev, const int32_t* t_off, int32_t t_max, int32_t B,
+                                int32_t H, int32_t hd, float scale, int32_t dtype, void* stream);
+int mk_kv_append_rows(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, const int32_t* slot,
+                      int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd, int32_t dtype, void* stream);
+int mk_kv_quant_append_rows(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,
+                            const int32_t* slot, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd,
+                            int32_t dtype, void* stream);
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);

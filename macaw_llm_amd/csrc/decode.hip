@@ -8,6 +8,9 @@
 //   mk_decode_step_attn  RoPE(q, k_new) + append(k_new, v_new) + that attention in one launch
 //   mk_kv_quant_append / mk_decode_step_attn_kv8  the prefill's cache write and the step's attention block over an
 //                   e4m3 KV cache (bytes + one fp32 scale per head and position: decode_kv8_impl.inc)
+//   mk_decode_step_attn_var / mk_decode_step_attn_kv8_var  the same steps at a position PER SAMPLE, *t_dev + t_off[b]
+//   mk_kv_append_rows / mk_kv_quant_append_rows  the prefill's cache write of a padded batch: source row j of sample
+//                   b goes to cache row slot[b][j], masked rows (slot < 0) are not written (a compacted, ragged cache)
 //
 // The fused training / prefill attention (attention.hip) works on 128-row query tiles: at Lq = 1
 // it would spend 127 of 128 MFMA rows on padding and, more to the point here, takes its key count
@@ -25,6 +28,24 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const char* src, char* d
   dst += (long)blockIdx.y * s_dst + (long)t * ld_dst;
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 16; i < row_bytes; i += (long)gridDim.x * 256 * 16)
     *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<const uint4*>(src + i);
+}
+
+// cache[b][slot[b][j]] = [k[b][j] | v[b][j]] for slot in [0, t_max): one 16-byte piece per thread, pieces of a
+// destination row adjacent (the row is one contiguous 2 * d_bytes run); bytes only, any 16-bit element type.
+__global__ __launch_bounds__(256) void kv_append_rows_kernel(const char* k, const char* v, long ld_bytes,
+                                                             long in_bs_bytes, char* cache, const int32_t* slot,
+                                                             int Sn, int t_max, int d_pieces) {
+  const int b = blockIdx.y;
+  const long per_row = 2L * d_pieces;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)Sn * per_row) return;
+  const int j = (int)(idx / per_row), c = (int)(idx % per_row);
+  const int r = slot[(long)b * Sn + j];
+  if (r < 0 || r >= t_max) return;
+  const char* src = (c < d_pieces ? k + (long)c * 16 : v + (long)(c - d_pieces) * 16) + (long)b * in_bs_bytes +
+                    (long)j * ld_bytes;
+  char* dst = cache + ((long)b * t_max + r) * per_row * 16 + (long)c * 16;
+  *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
 }
 
 template <typename T>
@@ -109,6 +130,56 @@ extern "C" int mk_decode_step_attn(const void* q, const void* k_new, const void*
                                    int32_t hd, float scale, int32_t dtype, void* stream) {
   if (dtype == MK_F16) return e_f16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream);
   return e_bf16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream);
+}
+
+extern "C" int mk_decode_step_attn_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                                       const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                       int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs,
+                                       const int32_t* t_dev, const int32_t* t_off, int32_t t_max, int32_t B,
+                                       int32_t H, int32_t hd, float scale, int32_t dtype, void* stream) {
+  if (!t_off) return MK_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(t_off) & 3) return MK_ERR_UNSUPPORTED;
+  if (dtype == MK_F16) return e_f16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream, true, t_off);
+  return e_bf16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream, true, t_off);
+}
+
+extern "C" int mk_decode_step_attn_kv8_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                                           const void* cos_t, const void* sin_t, void* cache, float* scales, void* o,
+                                           int64_t o_bs, const int32_t* t_dev, const int32_t* t_off, int32_t t_max,
+                                           int32_t B, int32_t H, int32_t hd, float scale, int32_t dtype,
+                                           void* stream) {
+  if (!t_off) return MK_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(t_off) & 3) return MK_ERR_UNSUPPORTED;
+  if (dtype == MK_F16) return e_f16::decode_step_attn_kv8_impl(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream, true, t_off);
+  return e_bf16::decode_step_attn_kv8_impl(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream, true, t_off);
+}
+
+extern "C" int mk_kv_quant_append_rows(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache,
+                                       float* scales, const int32_t* slot, int32_t Sn, int32_t t_max, int32_t B,
+                                       int32_t H, int32_t hd, int32_t dtype, void* stream) {
+  if (!slot) return MK_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(slot) & 3) return MK_ERR_UNSUPPORTED;
+  if (dtype == MK_F16) return e_f16::kv_quant_append_impl(k, v, ld, in_bs, cache, scales, 0, Sn, t_max, B, H, hd, dtype, stream, true, slot);
+  return e_bf16::kv_quant_append_impl(k, v, ld, in_bs, cache, scales, 0, Sn, t_max, B, H, hd, dtype, stream, true, slot);
+}
+
+extern "C" int mk_kv_append_rows(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache,
+                                 const int32_t* slot, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd,
+                                 int32_t dtype, void* stream) {
+  if (!k || !v || !cache || !slot || B <= 0 || H <= 0 || Sn <= 0 || t_max <= 0) return MK_ERR_BAD_ARG;
+  if ((dtype != MK_BF16 && dtype != MK_F16) || (hd != 16 && hd != 32 && hd != 64 && hd != 128)) return MK_ERR_UNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+                       reinterpret_cast<uintptr_t>(cache);
+  const int64_t D = (int64_t)H * hd;
+  if ((al & 15) || (reinterpret_cast<uintptr_t>(slot) & 3) || (ld % 8) || (in_bs % 8) || ld < D ||
+      (B > 1 && in_bs < D))
+    return MK_ERR_UNSUPPORTED;
+  const int d_pieces = (int)(D / 8);                     // 16-byte pieces of a key (or value) row
+  const long n = (long)Sn * 2 * d_pieces;
+  dim3 grid((unsigned)mk_cdiv(n, 256), B), block(256);
+  MK_LAUNCH(kv_append_rows_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), (const char*)k,
+            (const char*)v, (long)ld * 2, (long)in_bs * 2, (char*)cache, slot, Sn, t_max, d_pieces);
+  return mk_check_launch();
 }
 
 extern "C" int mk_kv_quant_append(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,

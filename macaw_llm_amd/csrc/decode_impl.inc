@@ -115,18 +115,23 @@ struct DecodeStepArgs {
   const int32_t* t_dev;
   int t_max;
   float scale;
+  const int32_t* t_off;                                     // VAR kernels only: [B] per-sample offsets to *t_dev
 };
 
 MK_DEV float rnd_e16(float x) { return rnd<e16>(x); }
 
-template <int HD, int NWV>
+// VAR (mk_decode_step_attn_var): p = clamp(*t_dev + t_off[b]) per sample, a padded batch's ragged cache; everything
+// after p is the same code, so a sample's arithmetic is that of the plain kernel at *t_dev = p.
+template <int HD, int NWV, bool VAR = false>
 __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(DecodeStepArgs a) {
   constexpr int LPK = HD / 8, KPW = 64 / LPK, KPP = NWV * KPW;
   __shared__ float red[NWV][HD];
   __shared__ float redw[2 * NWV];
   const int h = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p = min(max(*a.t_dev, 0), a.t_max - 1);
+  int tp = *a.t_dev;
+  if constexpr (VAR) tp += a.t_off[b];
+  const int p = min(max(tp, 0), a.t_max - 1);
   const int T = p + 1;
   const int sub = lane % LPK, grp = lane / LPK;
   const int d0 = sub * 8;
@@ -262,7 +267,7 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(DecodeStepAr
 // (lanes 16 g ... 16 g + 15 <-> head 4 x + g), the eight waves take keys t = wave, wave + 8, ..., eight keys per
 // lane in flight (64 keys per trip), and the grid is B x H / 4 = 256 workgroups at B = 32: one per CU, one round.
 // Partial results meet in LDS per head (8 waves x 4 heads).  hd = 128 only.
-template <int NWV>
+template <int NWV, bool VAR = false>
 __global__ __launch_bounds__(NWV * 64) void decode_step_attn4_kernel(DecodeStepArgs a) {
   constexpr int HD = 128, LPK = 16, HG = 4;
   __shared__ float red[NWV][HG * HD];
@@ -271,7 +276,9 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn4_kernel(DecodeStepA
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = lane / LPK, sub = lane % LPK;
   const int h = blockIdx.x * HG + grp;
-  const int p = min(max(*a.t_dev, 0), a.t_max - 1);
+  int tp = *a.t_dev;
+  if constexpr (VAR) tp += a.t_off[b];
+  const int p = min(max(tp, 0), a.t_max - 1);
   const int T = p + 1;
   const int d0 = sub * 8;
   const bool first = d0 < HD / 2;
@@ -370,9 +377,10 @@ int decode_step_attn_impl(const void* q, const void* k_new, const void* v_new, i
                                    const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
                                    int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs,
                                    const int32_t* t_dev, int32_t t_max, int32_t B, int32_t H,
-                                   int32_t hd, float scale, int32_t dtype, void* stream) {
+                                   int32_t hd, float scale, int32_t dtype, void* stream,
+                                   bool var = false, const int32_t* t_off = nullptr) {
   if (!q || !k_new || !v_new || !cos_t || !sin_t || !k_cache || !v_cache || !o || !t_dev || B <= 0 ||
-      H <= 0 || t_max <= 0)
+      H <= 0 || t_max <= 0 || (var && !t_off))
     return MK_ERR_BAD_ARG;
   if (dtype != E16<e16>::dtype || (hd != 16 && hd != 32 && hd != 64 && hd != 128)) return MK_ERR_UNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_new) |
@@ -385,11 +393,20 @@ int decode_step_attn_impl(const void* q, const void* k_new, const void* v_new, i
   a.cos_t = (const e16*)cos_t; a.sin_t = (const e16*)sin_t;
   a.kc = (e16*)k_cache; a.vc = (e16*)v_cache; a.kv_ld = kv_ld; a.kv_bs = kv_bs;
   a.o = (e16*)o; a.o_bs = o_bs;
-  a.t_dev = t_dev; a.t_max = t_max; a.scale = scale;
+  a.t_dev = t_dev; a.t_max = t_max; a.scale = scale; a.t_off = t_off;
   dim3 grid(H, B), block(512);
   const size_t lds = 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   static const bool no4 = getenv("MK_DECODE_ATTN_NO4") != nullptr;
+  if (var) {          // the same selection, the per-sample-position instantiations
+    if (hd == 128 && (H % 4) == 0 && (long)B * H >= 512 && !no4)
+      MK_LAUNCH((decode_step_attn4_kernel<8, true>), dim3(H / 4, B), block, lds, st, a);
+    else if (hd == 128) MK_LAUNCH((decode_step_attn_kernel<128, 8, true>), grid, block, lds, st, a);
+    else if (hd == 64) MK_LAUNCH((decode_step_attn_kernel<64, 8, true>), grid, block, lds, st, a);
+    else if (hd == 32) MK_LAUNCH((decode_step_attn_kernel<32, 8, true>), grid, block, lds, st, a);
+    else MK_LAUNCH((decode_step_attn_kernel<16, 8, true>), grid, block, lds, st, a);
+    return mk_check_launch();
+  }
   if (hd == 128 && (H % 4) == 0 && (long)B * H >= 512 && !no4)
     MK_LAUNCH((decode_step_attn4_kernel<8>), dim3(H / 4, B), block, lds, st, a);
   else if (hd == 128) MK_LAUNCH((decode_step_attn_kernel<128, 8>), grid, block, lds, st, a);

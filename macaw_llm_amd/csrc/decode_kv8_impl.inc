@@ -14,6 +14,7 @@ struct Kv8AppendArgs {
   const e16* k; const e16* v; long ld, in_bs;     // Sn rows per sample at pitch ld, samples in_bs apart (elements)
   uint8_t* cache; float* scales;
   int t0, Sn, t_max, H;
+  const int32_t* slot;                            // ROWS kernels only: [B][Sn] destination rows, < 0 = skip
 };
 
 // amax over the LPK lanes that share a head, then the project's row quantisation (fp8_rowquant_kernel's
@@ -39,8 +40,9 @@ MK_DEV float kv8_quant(const float (&x)[NCH * 8], unsigned (&q)[NCH * 2]) {
 }
 
 // One lane group of HD / 8 lanes per (new row, head): 16 bytes of k and of v per lane in, 8 + 8 bytes out.
-// Writes cache rows [t0, t0 + Sn) of every sample and nothing else.
-template <int HD>
+// Writes cache rows [t0, t0 + Sn) of every sample and nothing else.  ROWS (mk_kv_quant_append_rows): source row s of
+// sample b goes to cache row slot[b][s] instead, a row whose slot is outside [0, t_max) is not written.
+template <int HD, bool ROWS = false>
 __global__ __launch_bounds__(256) void kv_quant_append_kernel(Kv8AppendArgs a) {
   constexpr int LPK = HD / 8;
   const int b = blockIdx.y;
@@ -62,7 +64,12 @@ __global__ __launch_bounds__(256) void kv_quant_append_kernel(Kv8AppendArgs a) {
   const float vs = kv8_quant<LPK, 1>(vf, vq);
   if (!live) return;
   const long D = (long)a.H * HD;
-  const long row = (long)b * a.t_max + a.t0 + s;
+  int dr = a.t0 + s;
+  if constexpr (ROWS) {
+    dr = a.slot[(long)b * a.Sn + s];
+    if (dr < 0 || dr >= a.t_max) return;
+  }
+  const long row = (long)b * a.t_max + dr;
   uint8_t* dst = a.cache + row * 2 * D + (long)h * HD + sub * 8;
   *reinterpret_cast<uint2*>(dst) = make_uint2(kq[0], kq[1]);
   *reinterpret_cast<uint2*>(dst + D) = make_uint2(vq[0], vq[1]);
@@ -80,6 +87,7 @@ struct DecodeStepKv8Args {
   const int32_t* t_dev;
   int t_max, H;
   float scale;
+  const int32_t* t_off;                                     // VAR kernels only: [B] per-sample offsets to *t_dev
 };
 
 // E e4m3 bytes (E / 4 dwords, element index ascending with the byte address) against E fp32 values
@@ -138,7 +146,8 @@ MK_DEV void kv8_store(uint8_t* p, const unsigned (&w)[E / 4]) {
 //                 wave instruction), and L2-served streaming reads of 8 bytes per lane run at 0.54 - 0.70 of the 16-byte
 //                 rate on this part, so the stream that decides this regime takes the 16-byte form.  Registers per lane in flight: 8 keys x (4 + 4 dwords + 2 scales), the same 64
 //                 dwords of payload as the 16-bit kernel's 8 keys x 2 x 16 bytes.
-template <int HD, int E, int HG, int NWV>
+// VAR (mk_decode_step_attn_kv8_var): p = clamp(*t_dev + t_off[b]) per sample, as in decode_step_attn_kernel.
+template <int HD, int E, int HG, int NWV, bool VAR = false>
 __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kv8_kernel(DecodeStepKv8Args a) {
   constexpr int LPK = HD / E, KPW = 64 / (LPK * HG), KPP = NWV * KPW, NCH = E / 8, NB = 8;
   static_assert(LPK >= 2 && KPW >= 1, "rotate-half partner in another lane; at least one key per wave");
@@ -148,7 +157,9 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kv8_kernel(DecodeSt
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sub = lane % LPK, hg = (lane / LPK) % HG, grp = lane / (LPK * HG);
   const int h = blockIdx.x * HG + hg;
-  const int p = min(max(*a.t_dev, 0), a.t_max - 1);
+  int tp = *a.t_dev;
+  if constexpr (VAR) tp += a.t_off[b];
+  const int p = min(max(tp, 0), a.t_max - 1);
   const int T = p + 1;
   const int d0 = sub * E;
   const bool first = d0 < HD / 2;
@@ -276,9 +287,9 @@ bool kv8_hd_ok(int hd) { return hd == 16 || hd == 32 || hd == 64 || hd == 128; }
 
 int kv_quant_append_impl(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,
                          int32_t t0, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd, int32_t dtype,
-                         void* stream) {
+                         void* stream, bool rows = false, const int32_t* slot = nullptr) {
   if (!k || !v || !cache || !scales || B <= 0 || H <= 0 || Sn <= 0 || t_max <= 0 || t0 < 0 ||
-      (int64_t)t0 + Sn > t_max)
+      (!rows && (int64_t)t0 + Sn > t_max) || (rows && !slot))
     return MK_ERR_BAD_ARG;
   if (dtype != E16<e16>::dtype || !kv8_hd_ok(hd)) return MK_ERR_UNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
@@ -288,10 +299,17 @@ int kv_quant_append_impl(const void* k, const void* v, int64_t ld, int64_t in_bs
   Kv8AppendArgs a;
   a.k = (const e16*)k; a.v = (const e16*)v; a.ld = ld; a.in_bs = in_bs;
   a.cache = (uint8_t*)cache; a.scales = scales;
-  a.t0 = t0; a.Sn = Sn; a.t_max = t_max; a.H = H;
+  a.t0 = t0; a.Sn = Sn; a.t_max = t_max; a.H = H; a.slot = slot;
   const long n = (long)Sn * H * (hd / 8);
   dim3 grid((unsigned)mk_cdiv(n, 256), B), block(256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (rows) {
+    if (hd == 128) MK_LAUNCH((kv_quant_append_kernel<128, true>), grid, block, 0, st, a);
+    else if (hd == 64) MK_LAUNCH((kv_quant_append_kernel<64, true>), grid, block, 0, st, a);
+    else if (hd == 32) MK_LAUNCH((kv_quant_append_kernel<32, true>), grid, block, 0, st, a);
+    else MK_LAUNCH((kv_quant_append_kernel<16, true>), grid, block, 0, st, a);
+    return mk_check_launch();
+  }
   if (hd == 128) MK_LAUNCH((kv_quant_append_kernel<128>), grid, block, 0, st, a);
   else if (hd == 64) MK_LAUNCH((kv_quant_append_kernel<64>), grid, block, 0, st, a);
   else if (hd == 32) MK_LAUNCH((kv_quant_append_kernel<32>), grid, block, 0, st, a);
@@ -302,9 +320,9 @@ int kv_quant_append_impl(const void* k, const void* v, int64_t ld, int64_t in_bs
 int decode_step_attn_kv8_impl(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
                               const void* sin_t, void* cache, float* scales, void* o, int64_t o_bs,
                               const int32_t* t_dev, int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale,
-                              int32_t dtype, void* stream) {
+                              int32_t dtype, void* stream, bool var = false, const int32_t* t_off = nullptr) {
   if (!q || !k_new || !v_new || !cos_t || !sin_t || !cache || !scales || !o || !t_dev || B <= 0 || H <= 0 ||
-      t_max <= 0)
+      t_max <= 0 || (var && !t_off))
     return MK_ERR_BAD_ARG;
   if (dtype != E16<e16>::dtype || !kv8_hd_ok(hd)) return MK_ERR_UNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_new) |
@@ -318,9 +336,18 @@ int decode_step_attn_kv8_impl(const void* q, const void* k_new, const void* v_ne
   a.cos_t = (const e16*)cos_t; a.sin_t = (const e16*)sin_t;
   a.cache = (uint8_t*)cache; a.scales = scales;
   a.o = (e16*)o; a.o_bs = o_bs;
-  a.t_dev = t_dev; a.t_max = t_max; a.H = H; a.scale = scale;
+  a.t_dev = t_dev; a.t_max = t_max; a.H = H; a.scale = scale; a.t_off = t_off;
   dim3 grid(H, B), block(512);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (var) {          // the same selection, the per-sample-position instantiations
+    if (hd == 128 && (H % 4) == 0 && (long)B * H >= 512)
+      MK_LAUNCH((decode_step_attn_kv8_kernel<128, 16, 4, 8, true>), dim3(H / 4, B), block, 0, st, a);
+    else if (hd == 128) MK_LAUNCH((decode_step_attn_kv8_kernel<128, 8, 1, 8, true>), grid, block, 0, st, a);
+    else if (hd == 64) MK_LAUNCH((decode_step_attn_kv8_kernel<64, 8, 1, 8, true>), grid, block, 0, st, a);
+    else if (hd == 32) MK_LAUNCH((decode_step_attn_kv8_kernel<32, 8, 1, 8, true>), grid, block, 0, st, a);
+    else MK_LAUNCH((decode_step_attn_kv8_kernel<16, 8, 1, 8, true>), grid, block, 0, st, a);
+    return mk_check_launch();
+  }
   // the dispatch of decode_step_attn_impl: four heads per workgroup where there are many (sample, head) pairs
   if (hd == 128 && (H % 4) == 0 && (long)B * H >= 512)
     MK_LAUNCH((decode_step_attn_kv8_kernel<128, 16, 4, 8>), dim3(H / 4, B), block, 0, st, a);

@@ -576,9 +576,48 @@ class LayerWeights(NamedTuple):
     wgu: Optional[torch.Tensor]
 
 
-def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off):
+class Ragged(NamedTuple):
+    """a padded batch for llama_layer_cached (ragged_from_mask): the prompt's key mask, where each prompt row goes in
+    the COMPACTED cache, and where each sample's decode steps run relative to the common step counter"""
+    kmask: torch.Tensor      # int32 [B, S0], non-zero = valid: the prefill attention's key mask
+    slot: torch.Tensor       # int32 [B, S0]: cache row of prompt row (b, j) = its position; -1 for a masked row
+    t_off: torch.Tensor      # int32 [B]: n_b - S0; the step of sample b runs at position / cache row *t_dev + t_off[b]
+
+
+def ragged_from_mask(mask, B, S0):
+    """The host side of generate(attention_mask=): mask [B, S0], any integer or bool dtype, non-zero = valid.
+    Returns None for a mask without a zero (the unpadded path), else (Ragged, pos, last):
+      pos  int32 [B * S0]  RoPE positions, max(cumsum(mask) - 1, 0) (the reference's prepare_inputs_for_generation rule)
+      last int64 [B]       flat row b * S0 + (last valid index of sample b): the hidden row that predicts token 0
+    ValueError for a shape other than (B, S0) and for a sample without a valid token."""
+    if mask.dim() != 2 or tuple(mask.shape) != (B, S0):
+        raise ValueError(f"attention_mask should be of size {(B, S0)}, but is {tuple(mask.shape)}")
+    valid = mask != 0
+    if bool(valid.all()):
+        return None
+    n = valid.sum(1)
+    if bool((n == 0).any()):
+        raise ValueError(f"attention_mask: sample(s) {torch.nonzero(n == 0).flatten().tolist()} have no valid token")
+    cs = valid.long().cumsum(1)
+    pos = (cs - 1).clamp_(min=0)
+    slot = torch.where(valid, pos, torch.full_like(pos, -1))
+    idx = torch.arange(S0, device=mask.device).expand(B, S0)
+    last = torch.where(valid, idx, torch.full_like(idx, -1)).max(1).values
+    last = last + torch.arange(B, device=mask.device) * S0
+    rg = Ragged(valid.to(torch.int32).contiguous(), slot.to(torch.int32).contiguous(),
+                (n - S0).to(torch.int32).contiguous())
+    return rg, pos.to(torch.int32).reshape(-1).contiguous(), last.contiguous()
+
+
+def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged=None, **off):
     """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
-    e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8"""
+    e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8; with ragged (a padded batch) their per-sample-position forms"""
+    if ragged is not None:
+        if kv8 is not None:
+            return ops.decode_step_attn_kv8_var(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, ragged.t_off, Tmax, B, H, hd,
+                                                att, scale, **off)
+        return ops.decode_step_attn_var(q, k, v, in_bs, cos, sin, kvc, t_dev, ragged.t_off, Tmax, B, H, hd, att, scale,
+                                        **off)
     if kv8 is not None:
         return ops.decode_step_attn_kv8(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off)
     return ops.decode_step_attn(q, k, v, in_bs, cos, sin, kvc, t_dev, Tmax, B, H, hd, att, scale, **off)
@@ -605,7 +644,7 @@ def _stream_linear(x, W, q8, pro, w_ln, eps, residual, FF):
 
 
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
-                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None):
+                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None, ragged=None):
     """No-grad decoder layer over `Sn` NEW positions per sample (rows of x2 are (b, s)) that
     start at position t0, with a preallocated KV cache kvc [B, Tmax, 2D] = [keys | values] per
     position (post-RoPE keys, modeling.py:183-195 semantics without the torch.cat per step).
@@ -627,9 +666,19 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     ops.kv8_cache): every decode step (t_dev) runs ops.decode_step_attn_kv8 in place of ops.decode_step_attn, with
     or without w8.  The prefill (t0 = 0) attends over the fresh 16-bit q, k, v of the prompt -- the data a 16-bit
     cache would have held -- and then writes the cache through ops.kv_quant_append; there is no quantised
-    attention over several new positions, so t0 > 0 without t_dev raises ValueError."""
+    attention over several new positions, so t0 > 0 without t_dev raises ValueError.
+
+    ragged (a Ragged: ragged_from_mask): a padded batch.  The prefill (t0 = 0, `pos` the caller's cumsum positions)
+    attends causally over the prompt's own fresh k, v with ragged.kmask and writes the cache COMPACTED through
+    ops.kv_append_rows / ops.kv_quant_append_rows: the valid token at position i of a sample goes to cache row i,
+    masked rows are not written.  Every decode step (t_dev) runs the per-sample-position step attention at
+    *t_dev + ragged.t_off[b] and never reads past that row, so the cache's unwritten tail may stay uninitialised.
+    There is no masked attention over a cache: anything else (t0 > 0 without t_dev) raises ValueError."""
     M, D = x2.shape
     dyn = t_dev is not None
+    if ragged is not None and not dyn and t0 != 0:
+        raise ValueError("llama_layer_cached: ragged takes a prefill from position 0 (t0 = 0) or single-position "
+                         f"decode steps (t_dev), not {Sn} new positions at t0 = {t0}")
     if kv8 is not None and not dyn and t0 != 0:
         raise ValueError("llama_layer_cached: kv8 takes a prefill from position 0 (t0 = 0) or single-position decode "
                          f"steps (t_dev), not {Sn} new positions at t0 = {t0}")
@@ -649,7 +698,8 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         # without w8; under the gate above that matters only for a non-contiguous wo, which takes ops.linear_fwd.
         q_qkv, q_o, q_gu, q_d = w8 if w8 is not None else (None,) * 4
         qkv = _stream_linear(x2, wqkv, q_qkv, 1, ln1, eps, None, FF)
-        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, k_off=D, v_off=2 * D)
+        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, k_off=D,
+                   v_off=2 * D)
         h1 = _stream_linear(att, wo, q_o, 0, None, eps, x2, FF)
         gu = _stream_linear(h1, wgu, q_gu, 1, ln2, eps, None, FF)
         return _stream_linear(gu, wd, q_d, 2, None, eps, h1, FF)
@@ -669,26 +719,32 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         new, off = (q, k, v), {}
         ropes, appends = ((q, H), (k, H)), ((k, D, 0, 0), (v, D, 0, D))
     if dyn:     # RoPE + cache append + attention of the new position: one launch
-        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, **off)
+        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, **off)
     else:
         for t, heads in ropes:
             ops.rope_(t, cos, sin, pos, heads, hd)
-        if kv8 is None:
+        kmask = ragged.kmask if ragged is not None else None
+        if kv8 is None and ragged is None:
             # append the new keys / values to the cache rows [t0, t0 + Sn) of every sample, attend over rows [0, t0 + Sn)
             for src, cols, src_off, col in appends:
                 ops.copy2d(src, kvc, Sn, cols, ldq, ldc, batch=B, s_src=Sn * ldq, s_dst=Tmax * ldc, src_off=src_off,
                            dst_off=t0 * ldc + col)
             kd, vd, Lk = TDesc(kvc, ldc, Tmax * ldc, 0), TDesc(kvc, ldc, Tmax * ldc, D), t0 + Sn
         else:
-            # e4m3 cache, prefill: causal attention over the prompt's own 16-bit k, v (read at the ldq pitch), then the
-            # quantising cache write
+            # e4m3 cache or padded batch, prefill: causal attention over the prompt's own 16-bit k, v (read at the ldq
+            # pitch), then the quantising / compacting cache write
             kd, vd, Lk = TDesc(k, ldq, Sn * ldq), TDesc(v, ldq, Sn * ldq), Sn
         if flash_ok(x2.dtype, hd):      # (takes views: the D columns at the operand's offset)
             ops.flash_attn_fwd(q, kd.t[..., kd.off:kd.off + D], vd.t[..., vd.off:vd.off + D], att, B, H, Sn, Lk, hd,
-                               ldq, Sn * ldq, kd.ld, kd.bs, vd.ld, vd.bs, D, Sn * D, scale, causal=True)
+                               ldq, Sn * ldq, kd.ld, kd.bs, vd.ld, vd.bs, D, Sn * D, scale, kmask=kmask, causal=True)
         else:
-            attention_fwd(TDesc(q, ldq, Sn * ldq), kd, vd, TDesc(att, D, Sn * D), B, H, Sn, Lk, hd, scale, causal=True)
-        if kv8 is not None:
+            attention_fwd(TDesc(q, ldq, Sn * ldq), kd, vd, TDesc(att, D, Sn * D), B, H, Sn, Lk, hd, scale, kmask=kmask,
+                          causal=True)
+        if ragged is not None and kv8 is not None:
+            ops.kv_quant_append_rows(k, v, ldq, Sn * ldq, kvc, kv8, ragged.slot, Sn, Tmax, B, H, hd)
+        elif ragged is not None:
+            ops.kv_append_rows(k, v, ldq, Sn * ldq, kvc, ragged.slot, Sn, Tmax, B, H, hd)
+        elif kv8 is not None:
             ops.kv_quant_append(k, v, ldq, Sn * ldq, kvc, kv8, 0, Sn, Tmax, B, H, hd)
     h1 = ops.linear_fwd(att, wo, residual=x2)
     _, y2, _ = ops.rmsnorm_fwd(h1, ln2, eps)

@@ -110,6 +110,12 @@ SIGNATURES = {
     "mk_kv_quant_append": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mk_decode_step_attn_kv8": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32,
                                 _i32, _vp],
+    "mk_decode_step_attn_var": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32,
+                                _i32, _i32, _f32, _i32, _vp],
+    "mk_decode_step_attn_kv8_var": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32,
+                                    _i32, _f32, _i32, _vp],
+    "mk_kv_append_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "mk_kv_quant_append_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mk_adamw_bias_correction": [_f32, _f32, _i32, _vp],
     "mk_adamw_multi_dev": [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _i32, _vp],
     "mk_set_dropout_seed_offset": [_vp],

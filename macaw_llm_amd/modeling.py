@@ -59,6 +59,8 @@ DECODE_WEIGHTS = [None]
 KV_CACHE = [None]
 # MM_LLMs.set_sampling: the sampling arguments MM_LLMs.forward hands to generate()
 SAMPLING = [dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None)]
+# MM_LLMs.set_generate_mask: whether MM_LLMs.forward hands its extended attention mask to generate()
+GENERATE_MASK = [False]
 
 
 def _sampling_check(where, temperature, top_k, top_p):
@@ -551,7 +553,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
-                 kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, **_):
+                 kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None,
+                 attention_mask=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -596,7 +599,23 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         given.  One difference to HF: top_k keeps EXACTLY k columns, ties at the k-th value going to the lower column
         (HF keeps the whole tie group), which makes top_k=1 greedy.  temperature <= 0, top_p outside (0, 1] and a
         negative top_k raise ValueError.  With do_sample=False (default) the four arguments are ignored and not one
-        launch differs.  Composes with decode_weights, kv_cache and LoRA (they only change where the logits come from)."""
+        launch differs.  Composes with decode_weights, kv_cache and LoRA (they only change where the logits come from).
+
+        attention_mask [B, S0] (any integer or bool dtype, non-zero = valid): a PADDED batch -- left padding, right
+        padding or holes.  Sample b generates what its n_b valid tokens would generate alone, in order and unpadded:
+        positions are max(cumsum(mask) - 1, 0) (the reference's LLaMA rule for such batches, modeling.py:624-652), masked
+        keys are excluded, and token 0 is predicted by each sample's LAST VALID row.  The prefill runs over the padded
+        rows with the key mask and writes the KV cache compacted (the valid token at position i in cache row i:
+        ops.kv_append_rows / ops.kv_quant_append_rows); new token t of sample b then lives at position and cache row
+        n_b + t, and the step kernels read their position per sample (ops.decode_step_attn_var / _kv8_var: the one
+        device counter plus a per-sample offset), so a short sample streams only its own keys and the host still
+        does nothing per token on the hipGraph path.  decode_graph=False, MACAW_NO_DECODE_GRAPH and max_new_tokens <= 2
+        run the same step launches kernel by kernel.  Composes with kv_cache, decode_weights, sampling and LoRA.  A
+        padded mask with use_cache=True needs those step kernels: fp32 parameters, or a head size / length outside
+        ops.decode_attn_ok, raise ValueError (there is no masked attention over a cache) -- use use_cache=False, which
+        recomputes the prefix with the growing mask and works for every dtype.  A sample without a valid token and a
+        mask of another shape raise ValueError.  None (default) or a mask without a zero: the unpadded path, not one
+        launch different."""
         if decode_weights not in (None, "fp8"):
             raise ValueError(f"generate: decode_weights must be None or 'fp8', got {decode_weights!r}")
         if kv_cache not in (None, "fp8"):
@@ -616,6 +635,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         pad = pad_token_id if pad_token_id is not None else (eos_token_id or 0)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         eps = self.model.norm.variance_epsilon
+        # a padded batch: engine.Ragged, the prefill's positions, the flat index of each sample's last valid row
+        ragged = rg_pos = rg_last = None
+        if attention_mask is not None:
+            padded = eng.ragged_from_mask(attention_mask.to(dev), B, S0)        # None for a mask without a zero
+            if padded is not None:
+                ragged, rg_pos, rg_last = padded
         V = self.lm_head.weight.shape[0]
         out = []
 
@@ -638,16 +663,24 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         if not use_cache:
             emb = inputs_embeds.contiguous()
+            mask = ragged.kmask if ragged is not None else None        # grows by a one per new token
             for t in range(max_new_tokens):
                 S = emb.shape[1]
                 self.model._defer_final_norm = True
                 try:
-                    h = self.model(inputs_embeds=emb)
+                    if mask is not None:
+                        h = self.model(inputs_embeds=emb, attention_mask=mask,
+                                       position_ids=(mask.cumsum(1) - 1).clamp_(min=0))
+                    else:
+                        h = self.model(inputs_embeds=emb)
                 finally:
                     self.model._defer_final_norm = False
-                last = torch.empty((B, D), dtype=dtype, device=dev)
-                ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=B, s_src=S * D, s_dst=D,
-                           src_off=(S - 1) * D)
+                if mask is not None and t == 0:         # token 0: predicted by each sample's last valid row
+                    last = ops.embedding_fwd(h.contiguous().view(B * S, D), rg_last)
+                else:
+                    last = torch.empty((B, D), dtype=dtype, device=dev)
+                    ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=B, s_src=S * D, s_dst=D,
+                               src_off=(S - 1) * D)
                 nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
                 out.append(nxt)
                 done = done | (nxt == eos_token_id)
@@ -658,10 +691,20 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ops.copy2d(ops.embedding_fwd(emb_w, nxt.contiguous()), nemb, 1, D, D, D, batch=B,
                            s_src=D, s_dst=(S + 1) * D, dst_off=S * D)
                 emb = nemb
+                if mask is not None:
+                    mask = torch.cat([mask, torch.ones((B, 1), dtype=mask.dtype, device=dev)], dim=1)
             return torch.stack(out, dim=1)
 
         Tmax = S0 + max_new_tokens
         layers = self.model.layers
+        if ragged is not None:
+            hd0 = D // layers[0].self_attn.num_heads
+            if not ops.decode_attn_ok(dtype, hd0, Tmax):
+                why = (f"fp32 parameters ({dtype})" if dtype not in (torch.bfloat16, torch.float16) else
+                       f"ops.decode_attn_ok is false for head size {hd0} and {Tmax} positions")
+                raise ValueError(f"generate(attention_mask=) with a padded mask and use_cache=True: {why}; the "
+                                 "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
+                                 "there is no masked attention over a cache: pass use_cache=False")
         rot = layers[0].self_attn.rotary_emb
         cos, sin = rot.tables(Tmax, dtype, dev)
         kvs = None                # kv_cache="fp8": per layer the f32 scales of the e4m3 cache (kvc: its bytes)
@@ -714,16 +757,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
                     lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
                     w8=w8[i] if w8 is not None and t_dev is not None else None,
-                    kv8=kvs[i] if kvs is not None else None)
+                    kv8=kvs[i] if kvs is not None else None, ragged=ragged)
             return x2
 
-        h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)                 # prefill
-        last = torch.empty((B, D), dtype=dtype, device=dev)
-        ops.copy2d(h, last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
+        if ragged is not None:    # prefill over the padded rows; token 0 comes from each sample's last valid row
+            h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0, pos=rg_pos)
+            last = ops.embedding_fwd(h.view(B * S0, D), rg_last)
+        else:
+            h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)             # prefill
+            last = torch.empty((B, D), dtype=dtype, device=dev)
+            ops.copy2d(h, last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
         hd = D // layers[0].self_attn.num_heads
         if (decode_graph and max_new_tokens > 2 and ops.decode_attn_ok(dtype, hd, Tmax)
                 and not os.environ.get("MACAW_NO_DECODE_GRAPH")):
             return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample)
+        t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
         for t in range(max_new_tokens):
             nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
             out.append(nxt)
@@ -731,7 +779,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if t + 1 == max_new_tokens or bool(done.all()):
                 break
             x = ops.embedding_fwd(emb_w, nxt.contiguous())                 # [B, D]
-            last = run(x, 1, S0 + t)                                       # decode step
+            if ragged is not None:                                         # the graph path's step launches, one by one
+                last = run(x, 1, 0, pos=t_dev, t_dev=t_dev)
+                t_dev += 1
+            else:
+                last = run(x, 1, S0 + t)                                   # decode step
         return torch.stack(out, dim=1)
 
 
@@ -902,7 +954,8 @@ class MM_LLMs(PreTrainedModel):
         if "inference" in inputs and inputs["inference"] is True:
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
-                                     decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0], **SAMPLING[0])
+                                     decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
+                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0])
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -934,6 +987,14 @@ class MM_LLMs(PreTrainedModel):
         if mode not in (None, "fp8"):
             raise ValueError(f"set_kv_cache: mode must be None or 'fp8', got {mode!r}")
         KV_CACHE[0] = mode
+
+    @staticmethod
+    def set_generate_mask(on=False):
+        """Whether `inputs["inference"] = True` passes the extended attention mask it builds (ones for the modal
+        prefix, then the text mask) to LlamaForCausalLM.generate (attention_mask=): a padded batch then decodes
+        every sample as it would decode alone.  Off by default -- the reference drops the mask at llm.generate
+        (modeling.py:959) and attends to the pad tokens.  Process-wide switch, like set_kv_cache."""
+        GENERATE_MASK[0] = bool(on)
 
     @staticmethod
     def set_sampling(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None):

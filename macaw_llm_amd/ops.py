@@ -659,6 +659,69 @@ def decode_step_attn_kv8(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, t_
     return out
 
 
+def _i32_check(op, name, t, n):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise MacawHipError(f"{op}: {name} {t.dtype} {tuple(t.shape)}; expected {n} contiguous int32")
+
+
+def decode_step_attn_var(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_off, t_max, B, H, hd, out, scale,
+                         q_off=0, k_off=0, v_off=0):
+    """decode_step_attn at a position per sample, p_b = *t_dev + t_off[b] (t_off int32 [B] on the device): RoPE at
+    table row p_b, append at cache row p_b, attention over rows 0 ... p_b of sample b's cache -- the step of a padded
+    batch over its compacted cache (kv_append_rows).  Bit-identical per sample to decode_step_attn at *t_dev = p_b"""
+    lib = _L.load()
+    es = q.element_size()
+    D = H * hd
+    _i32_check("decode_step_attn_var", "t_off", t_off, B)
+    if cache.dtype != q.dtype:
+        raise MacawHipError(f"decode_step_attn_var: cache {cache.dtype}, tokens {q.dtype}")
+    _L.check(lib.mk_decode_step_attn_var(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es,
+                                         in_bs, _p(cos_t), _p(sin_t), _p(cache), _p(cache) + D * es, 2 * D,
+                                         t_max * 2 * D, _p(out), D, _p(t_dev), _p(t_off), t_max, B, H, hd, scale,
+                                         dt(q), _st()), "mk_decode_step_attn_var")
+    return out
+
+
+def decode_step_attn_kv8_var(q, k_new, v_new, in_bs, cos_t, sin_t, cache, scales, t_dev, t_off, t_max, B, H, hd, out,
+                             scale, q_off=0, k_off=0, v_off=0):
+    """decode_step_attn_kv8 at a position per sample, p_b = *t_dev + t_off[b] (see decode_step_attn_var)"""
+    lib = _L.load()
+    es = q.element_size()
+    _kv8_check("decode_step_attn_kv8_var", cache, scales, t_max, B, H, hd)
+    _i32_check("decode_step_attn_kv8_var", "t_off", t_off, B)
+    _L.check(lib.mk_decode_step_attn_kv8_var(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es,
+                                             in_bs, _p(cos_t), _p(sin_t), _p(cache), _p(scales), _p(out), H * hd,
+                                             _p(t_dev), _p(t_off), t_max, B, H, hd, scale, dt(q), _st()),
+             "mk_decode_step_attn_kv8_var")
+    return out
+
+
+def kv_append_rows(k, v, ld, in_bs, cache, slot, Sn, t_max, B, H, hd):
+    """the compacting prefill write of a 16-bit KV cache [B, t_max, 2 * H * hd]: source row j of sample b of the
+    ROTATED keys k and of the values v (row pitch ld, sample stride in_bs in elements; k / v may be slices of one
+    fused [M, 3D] buffer) goes to cache row slot[b, j] (int32 [B, Sn]); slot < 0 skips the row, and no other cache
+    byte is touched"""
+    lib = _L.load()
+    if (cache.dtype != k.dtype or tuple(cache.shape) != (B, t_max, 2 * H * hd) or not cache.is_contiguous()):
+        raise MacawHipError(f"kv_append_rows: cache {cache.dtype} {tuple(cache.shape)}; expected {k.dtype} "
+                            f"{(B, t_max, 2 * H * hd)}, contiguous")
+    _i32_check("kv_append_rows", "slot", slot, B * Sn)
+    _L.check(lib.mk_kv_append_rows(_p(k), _p(v), ld, in_bs, _p(cache), _p(slot), Sn, t_max, B, H, hd, dt(k), _st()),
+             "mk_kv_append_rows")
+    return cache
+
+
+def kv_quant_append_rows(k, v, ld, in_bs, cache, scales, slot, Sn, t_max, B, H, hd):
+    """kv_append_rows into an e4m3 KV cache (kv8_cache) with kv_quant_append's quantisation: the bytes and scales of
+    a written row are what kv_quant_append writes for that source row"""
+    lib = _L.load()
+    _kv8_check("kv_quant_append_rows", cache, scales, t_max, B, H, hd)
+    _i32_check("kv_quant_append_rows", "slot", slot, B * Sn)
+    _L.check(lib.mk_kv_quant_append_rows(_p(k), _p(v), ld, in_bs, _p(cache), _p(scales), _p(slot), Sn, t_max, B, H,
+                                         hd, dt(k), _st()), "mk_kv_quant_append_rows")
+    return cache, scales
+
+
 def decode_attn_ok(dtype, hd, t_max):
     return dtype in (torch.bfloat16, torch.float16) and hd in (16, 32, 64, 128) and t_max * 4 <= 60 * 1024
 

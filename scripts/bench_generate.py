@@ -21,13 +21,19 @@ with torch.no_grad():
 #        bench_generate.py --sample-ab [--reps R] [B ...]: greedy against do_sample=True, top_k=50, top_p=0.9 (seed 1), alternated
 # the same way: ms per token of every run, the medians, their difference and the greedy run-to-run spread (the difference
 # counts only beyond it), then the stand-alone time of one ops.sample_rows launch against ops.argmax_rows on [B, 32000] logits
+#        bench_generate.py --ragged-ab [--prompt-tokens N] [--short-tokens M] [--reps R] [B ...]: a LEFT-PADDED batch (default
+# B = 32) whose text lengths fall linearly from N (default 1900) to M (default 150), once with attention_mask= (the compacted,
+# ragged KV cache: a step streams the sum of the real lengths) and once as today's call without a mask (every sample streams
+# all S0 rows and attends to its pad tokens), alternated the same way, with the KV bytes a step reads in each mode
 AB = "--fp8-ab" in sys.argv
+RAGGED = "--ragged-ab" in sys.argv
 SAMPLE = "--sample-ab" in sys.argv
 KV8 = "--kv8-ab" in sys.argv
-_VAL = ("--reps", "--prompt-tokens")
+_VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
-PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else 128
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--kv8-ab", "--sample-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
+SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
 if SAMPLE:
     from macaw_llm_amd import ops
     SKW = dict(do_sample=True, top_k=50, top_p=0.9, seed=1)
@@ -67,6 +73,39 @@ if SAMPLE:
             us[name] = e0.elapsed_time(e1) / 200 * 1e3
         print(f"B={B:2d}: one launch on [B, 32000] bf16 logits (back to back, incl. launch gaps): " +
               ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
+if RAGGED:
+    lcfg = model.llm.config
+    NL, D = lcfg.num_hidden_layers, lcfg.hidden_size
+    for B in [int(a) for a in _args] or [32]:
+        inp = synthetic_inputs(cfg, B, PROMPT, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {"mask": [], "none": []}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            S0 = emb.shape[1]
+            pads = [round((PROMPT - SHORT) * b / max(B - 1, 1)) for b in range(B)]      # sample b: pads[b] masked rows on the left
+            mask = torch.ones((B, S0), dtype=torch.long, device=dev)
+            for b, n in enumerate(pads):
+                mask[b, :n] = 0
+            real = [S0 - n for n in pads]
+            kvb = {"mask": NL * sum(n + 40 for n in real) * 2 * D * 2, "none": NL * B * (S0 + 40) * 2 * D * 2}
+            for mode in ("none", "mask"):       # untimed: each mode's first call (kernel attributes, allocator pools at this size)
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=-1, attention_mask=mask if mode == "mask" else None)
+            for rep in range(REPS):
+                for mode in ("none", "mask"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1,
+                                           attention_mask=mask if mode == "mask" else None)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} S0={S0} real {real[0]} ... {real[-1]} rep {rep} {mode:4s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = (max(ms["none"]) - min(ms["none"])) / med["none"]
+        print(f"B={B:2d} S0={S0}, real lengths {real[0]} ... {real[-1]} (sum {sum(real)} of {B * S0}): no mask {med['none']:6.3f} ms/token "
+              f"({kvb['none'] / 1e9:6.3f} GB of KV per token), attention_mask {med['mask']:6.3f} ms/token ({kvb['mask'] / 1e9:6.3f} GB), "
+              f"mask / none = {med['mask'] / med['none']:5.3f} (no-mask run-to-run spread {spread * 100:4.1f} %)", flush=True)
     sys.exit(0)
 if KV8:
     lcfg = model.llm.config
