@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 from golden_util import load_case  # noqa: E402
 from oracle import configs  # noqa: E402
+from softmax_ref import hash32  # noqa: E402
 from test_model_gpu import build_model, to_dev  # noqa: E402
 
 from macaw_llm_amd import ops  # noqa: E402
@@ -19,18 +20,6 @@ from macaw_llm_amd import modeling as Mo  # noqa: E402
 
 ALL7 = ["q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj"]
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-def hash32(seed, idx):
-    """numpy copy of mk_hash32 (csrc/common.h)"""
-    with np.errstate(over="ignore"):
-        z = idx.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(seed)
-        z ^= z >> np.uint64(30)
-        z *= np.uint64(0xBF58476D1CE4E5B9)
-        z ^= z >> np.uint64(27)
-        z *= np.uint64(0x94D049BB133111EB)
-        z ^= z >> np.uint64(31)
-    return (z >> np.uint64(16)).astype(np.uint32)
 
 
 def keep_mask(seed, tag, M, K, p, dev):
