@@ -352,6 +352,35 @@ int mk_decode_linear(const void* x, int64_t ldx, const void* W, int64_t ldw, voi
 int mk_decode_linear_fp8(const void* x, int64_t ldx, const void* Wq, int64_t ldw, const float* scale, void* y,
                          int64_t ldy, const void* residual, int64_t ldr, int32_t M, int32_t N, int32_t K,
                          int32_t prologue, const void* norm_w, float eps, int32_t dtype, void* stream);
+/* MXFP4 weight-only decode (generate(decode_weights="mxfp4")): the weight stream of a decode step at 4.25 bits per
+ *   element.  ONE format (OCP Microscaling v1.0, MXFP4), for a weight W [N][K], K % 128 == 0:
+ *     codes      uint8 [N][K / 2]   row pitch ldw BYTES; element 2 j of a row in the LOW nibble of byte j, element
+ *                                   2 j + 1 in the HIGH nibble.  A code is e2m1: a sign bit (bit 3) and 3 bits that
+ *                                   index {0, 0.5, 1, 1.5, 2, 3, 4, 6};
+ *     exponents  uint8 [N][K / 32]  row pitch lde; one E8M0 byte e per block of 32 elements along K, the scale is
+ *                                   2^(e - 127).  The NaN byte 0xFF is never written and not handled.
+ *   Quantiser (round to nearest, no calibration), per block: E = clamp(floor(log2(amax)) - 2, EMIN, 125), E = EMIN
+ *   for an all-zero block; element = x * 2^-E rounded to the nearest e2m1 value, ties to the even code (0.25 -> 0,
+ *   0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturated at +-6; stored byte E + 127.  EMIN is -125
+ *   for bf16 and -13 for f16, so every de-quantised value (code * 2^E) is zero or a NORMAL number of the token type:
+ *   the widening is exact and no result depends on a denormal mode.  A zero code is written without a sign.
+ * mk_mxfp4_quantize_rows: that quantiser for a row-major bf16 / f16 matrix x [rows][cols] at pitch ld (elements;
+ *   pitched rows allowed), one block of 32 per thread; deterministic.  cols % 32 == 0, ld % 8 == 0, ldq % 16 == 0,
+ *   pitches not below the row lengths, x and q 16-byte aligned, else MK_ERR_UNSUPPORTED.
+ * mk_decode_linear_mxfp4: y[M][N] = prologue(x) dequant(Wq, e)^T (+ residual), mk_decode_linear_fp8 with the weight
+ *   streamed in that format (W4A16).  A lane's 16-byte load is one MX block; v_cvt_scalef32_pk_{bf16,f16}_fp4 widens
+ *   two codes and applies the block scale (built as as_float(e << 23), a normal power of two) in one instruction,
+ *   the 16-bit MFMA accumulates in fp32; tokens are NOT quantised.  The residual is added in fp32 before the one
+ *   rounding to the output type.  Prologues and their rounding points as mk_decode_linear.  Domain, else
+ *   MK_ERR_UNSUPPORTED: bf16 / f16; M <= 16 with a prologue, M <= 32 plain; K % 128 == 0; ldw % 16 == 0, ldw >= K / 2;
+ *   lde % 4 == 0, lde >= K / 32; ldx % 8 == 0 (elements), ldx / ldy / ldr not below the row lengths; x, Wq (and
+ *   norm_w) 16-byte aligned, e 4-byte aligned; with a prologue M * (K + 8) * 2 bytes <= 40 KiB of LDS.
+ *   Deterministic: the cross-wave sum has a fixed order. */
+int mk_mxfp4_quantize_rows(const void* x, int32_t rows, int32_t cols, int64_t ld, int32_t dtype, void* q, int64_t ldq,
+                           void* e, int64_t lde, void* stream);
+int mk_decode_linear_mxfp4(const void* x, int64_t ldx, const void* Wq, int64_t ldw, const void* e, int64_t lde, void* y,
+                           int64_t ldy, const void* residual, int64_t ldr, int32_t M, int32_t N, int32_t K,
+                           int32_t prologue, const void* norm_w, float eps, int32_t dtype, void* stream);
 /* mk_decode_emit: greedy selection + bookkeeping of one decode step (modeling.py:959, HF greedy_search):
  *   for every sample b: nxt = done[b] ? pad : first argmax of logits[b][0:V]; out[b][state[1]] = nxt;
  *   done[b] |= (nxt == eos); tok[b] = nxt.  Then, once: state[0] += 1 (the position the other decode

@@ -629,17 +629,22 @@ def _stream_linear(x, W, q8, pro, w_ln, eps, residual, FF):
     w_ln, eps), 2 = SwiGLU of x = [gate | up] [M, 2 FF], 0 = none) is folded into the weight stream where the
     prepared token rows fit the kernel's LDS budget (ops.decode_linear_ok: not for M > 4 at K = 4096); otherwise the
     separate RMSNorm / SwiGLU kernel runs first and the PLAIN launch follows, so every batch size up to 32 streams
-    the bytes it was given.  A 16-bit weight outside ops.decode_linear's domain goes through ops.linear_fwd."""
-    if q8 is not None and ops.decode_linear_fp8_ok(x, q8[0], pro):
-        return ops.decode_linear_fp8(x, q8[0], q8[1], pro, w_ln, eps, residual)
-    if q8 is None and ops.decode_linear_ok(x, W, pro):
+    the bytes it was given.  A 16-bit weight outside ops.decode_linear's domain goes through ops.linear_fwd.
+    A copy whose second member is uint8 is an MXFP4 copy (codes uint8 [N, K / 2], block exponents uint8 [N, K / 32]:
+    ops.mxfp4_weight) and streams through ops.decode_linear_mxfp4 under the same rule."""
+    if q8 is not None:      # the kind of a copy, per entry: uint8 block exponents = MXFP4, f32 channel scales = e4m3
+        mx = q8[1].dtype == torch.uint8
+        lin, ok = (ops.decode_linear_mxfp4, ops.decode_linear_mxfp4_ok) if mx else (ops.decode_linear_fp8, ops.decode_linear_fp8_ok)
+        if ok(x, q8[0], pro):
+            return lin(x, q8[0], q8[1], pro, w_ln, eps, residual)
+    elif ops.decode_linear_ok(x, W, pro):
         return ops.decode_linear(x, W, pro, w_ln, eps, residual)
     if pro == 1:
         x = ops.rmsnorm_fwd(x, w_ln, eps)[1]
     elif pro == 2:
         x = ops.swiglu2d_fwd(x, FF)
     if q8 is not None:
-        return ops.decode_linear_fp8(x, q8[0], q8[1], residual=residual)
+        return lin(x, q8[0], q8[1], residual=residual)
     return ops.linear_fwd(x, W, residual=residual)
 
 
@@ -660,7 +665,9 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     w8 (with t_dev and fused storage only): the e4m3 copies (q uint8 [N, K], scales f32 [N]: ops.fp8_weight) of
     the four streamed weights, in the order fused q|k|v, o, fused gate|up, down.  The same five launches then
     stream e4m3 bytes (ops.decode_linear_fp8: W8A16, tokens / KV cache / accumulation unchanged).  An entry
-    may be None for a projection outside the plain fp8 domain: that one keeps its 16-bit launch.
+    may be None for a projection outside the plain fp8 domain: that one keeps its 16-bit launch.  Each entry may
+    instead be an MXFP4 copy (codes uint8 [N, K / 2], exponents uint8 [N, K / 32]: ops.mxfp4_weight), streamed by
+    ops.decode_linear_mxfp4 (W4A16); the kind is decided per entry (_stream_linear).
 
     kv8 (the f32 [B, Tmax, 2H] scales of an e4m3 KV cache; kvc then is its uint8 [B, Tmax, 2D] bytes:
     ops.kv8_cache): every decode step (t_dev) runs ops.decode_step_attn_kv8 in place of ops.decode_step_attn, with

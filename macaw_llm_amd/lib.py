@@ -101,6 +101,9 @@ SIGNATURES = {
     "mk_decode_linear": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _f32, _i32, _vp],
     "mk_decode_linear_fp8": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _f32, _i32,
                              _vp],
+    "mk_mxfp4_quantize_rows": [_vp, _i32, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
+    "mk_decode_linear_mxfp4": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _f32,
+                               _i32, _vp],
     "mk_decode_emit": [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp],
     "mk_sample_rows": [_vp, _i64, _i32, _i32, _f32, _i32, _f32, _u64, _i32, _vp, _i32, _vp],
     "mk_decode_emit_sample": [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _f32, _i32, _f32, _u64, _i32,

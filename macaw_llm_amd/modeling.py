@@ -53,7 +53,7 @@ def _dtype_check(dtype):
 # them separate storage), so a model built the reference's way -- MM_LLMs(config), .to(), Trainer --
 # runs the same fused GEMMs as factory.build_model.  MACAW_NO_AUTO_FUSE=1 disables it.
 AUTO_FUSE = os.environ.get("MACAW_NO_AUTO_FUSE") is None
-# MM_LLMs.set_decode_weights: the decode_weights MM_LLMs.forward hands to generate() (None or "fp8")
+# MM_LLMs.set_decode_weights: the decode_weights MM_LLMs.forward hands to generate() (None, "fp8" or "mxfp4")
 DECODE_WEIGHTS = [None]
 # MM_LLMs.set_kv_cache: the kv_cache MM_LLMs.forward hands to generate() (None or "fp8")
 KV_CACHE = [None]
@@ -524,10 +524,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
         return res.clone()
 
-    def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="decode_weights"):
+    def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="decode_weights",
+                          value="fp8"):
         """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
         what keeps a call off that path instead of decoding it in 16 bits.  The limit of 32 sequences belongs to the
-        weight-streaming step (switch="decode_weights"); the e4m3 cache takes any batch."""
+        weight-streaming step (switch="decode_weights", value "fp8" or "mxfp4"); the e4m3 cache takes any batch."""
         why = None
         a0 = self.model.layers[0].self_attn
         hd = self.config.hidden_size // a0.num_heads
@@ -548,7 +549,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             why = (f"ops.decode_attn_ok is false for head size {hd} and {S0 + max_new_tokens} positions: the eager "
                    "decode loop would run")
         if why is not None:
-            raise ValueError(f"generate({switch}='fp8'): {why}")
+            raise ValueError(f"generate({switch}='{value}'): {why}")
 
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
@@ -575,6 +576,15 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         parameters, unfused q/k/v or gate/up storage, use_cache=False, decode_graph=False or
         MACAW_NO_DECODE_GRAPH, max_new_tokens <= 2, more than 32 sequences, a head size / length outside
         ops.decode_attn_ok) instead of silently decoding in 16 bits.  None (default): the 16-bit path.
+
+        decode_weights="mxfp4": the same mode at 4.25 bits per weight (W4A16).  The four streamed projections of every
+        layer use OCP MXFP4 copies (e2m1 codes, one power-of-two scale per 32 elements along K: ops.mxfp4_weight, cached
+        and re-made like the e4m3 copies) through ops.decode_linear_mxfp4; a projection outside that kernel's domain
+        (K % 128 != 0) keeps its 16-bit launch.  The lm_head streams its E4M3 copy (ops.fp8_weight): 1 % of the bytes,
+        and the projection whose rounding decides the argmax.  Round-to-nearest quantisation WITHOUT calibration: the
+        format error is bounded by tests/test_decode_mxfp4_gpu.py, the quality on trained checkpoints is unmeasured.
+        Prefill, tokens, KV cache, accumulation, LoRA (merged copies quantised once per call) and every refusal as
+        for "fp8".  Also a LATENCY mode: the 16-bit masters stay resident and the copies add 0.27 of their size.
 
         kv_cache="fp8": the KV cache holds OCP e4m3 bytes with one fp32 scale per (sample, position, key or value,
         head) (amax / 448 over the head's elements; keys quantised after RoPE; the format of include/macaw_hip.h):
@@ -616,8 +626,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         recomputes the prefix with the growing mask and works for every dtype.  A sample without a valid token and a
         mask of another shape raise ValueError.  None (default) or a mask without a zero: the unpadded path, not one
         launch different."""
-        if decode_weights not in (None, "fp8"):
-            raise ValueError(f"generate: decode_weights must be None or 'fp8', got {decode_weights!r}")
+        if decode_weights not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"generate: decode_weights must be None, 'fp8' or 'mxfp4', got {decode_weights!r}")
         if kv_cache not in (None, "fp8"):
             raise ValueError(f"generate: kv_cache must be None or 'fp8', got {kv_cache!r}")
         sample = None
@@ -644,11 +654,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         V = self.lm_head.weight.shape[0]
         out = []
 
-        if decode_weights == "fp8":
-            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph)
+        if decode_weights is not None:
+            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, value=decode_weights)
         if kv_cache == "fp8":
             self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="kv_cache")
-        w8_head = None            # decode_weights="fp8": (q, scales) of the lm_head
+        w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
 
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
             if h_last.is_contiguous():
@@ -729,8 +739,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             stored.append(eng.LayerWeights(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight,
                                            m.up_proj.weight, m.down_proj.weight, *lyr.fused_weights()))
 
-        w8 = None                 # decode_weights="fp8": per layer the copies of q|k|v, o, gate|up, down
-        if decode_weights == "fp8":
+        w8 = None                 # decode_weights="fp8" / "mxfp4": per layer the copies of q|k|v, o, gate|up, down
+        if decode_weights is not None:
             probe = torch.empty((B, 0), dtype=dtype, device=dev)
 
             def q8(W, own):       # own: a stored parameter (version-keyed cache); else a merged copy of this call
@@ -738,13 +748,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     return None   # outside the plain fp8 domain: this projection keeps its 16-bit launch
                 return ops.fp8_weight(W) if own is not None and own.data_ptr() == W.data_ptr() else ops.quantize_fp8_rows(W)
 
+            def q4(W, own):       # the same rule for the MXFP4 copies (K % 128 == 0)
+                if W is None or not ops.decode_linear_mxfp4_ok(probe, W):
+                    return None
+                return ops.mxfp4_weight(W) if own is not None and own.data_ptr() == W.data_ptr() else ops.quantize_mxfp4_rows(W)
+
+            ql = q4 if decode_weights == "mxfp4" else q8     # the layers' projections; the lm_head is e4m3 in both modes
+
             w8 = []
             for lyr, own in zip(layers, stored):
                 if own.wqkv is None or own.wgu is None:
-                    raise ValueError("generate(decode_weights='fp8'): unfused q/k/v or gate/up storage (the fp8 "
-                                     "decode step streams the fused q|k|v and gate|up weights: fuse_projections())")
+                    raise ValueError(f"generate(decode_weights='{decode_weights}'): unfused q/k/v or gate/up storage (the "
+                                     f"{decode_weights} decode step streams the fused q|k|v and gate|up weights: "
+                                     "fuse_projections())")
                 ws = merged.get(lyr, own)
-                w8.append((q8(ws.wqkv, own.wqkv), q8(ws.wo, own.wo), q8(ws.wgu, own.wgu), q8(ws.wd, own.wd)))
+                w8.append((ql(ws.wqkv, own.wqkv), ql(ws.wo, own.wo), ql(ws.wgu, own.wgu), ql(ws.wd, own.wd)))
             w8_head = q8(self.lm_head.weight, self.lm_head.weight)
 
         def run(x2, Sn, t0, pos=None, t_dev=None):
@@ -974,9 +992,10 @@ class MM_LLMs(PreTrainedModel):
     def set_decode_weights(mode=None):
         """Weight format of the decode steps of `inputs["inference"] = True` (LlamaForCausalLM.generate's
         decode_weights): None = the 16-bit weights, "fp8" = weight-only e4m3 copies (W8A16: a latency mode, the
-        16-bit masters stay resident).  Process-wide switch, like set_fp8."""
-        if mode not in (None, "fp8"):
-            raise ValueError(f"set_decode_weights: mode must be None or 'fp8', got {mode!r}")
+        16-bit masters stay resident), "mxfp4" = weight-only MXFP4 copies of the layers' projections and the e4m3
+        lm_head (W4A16: likewise a latency mode).  Process-wide switch, like set_fp8."""
+        if mode not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"set_decode_weights: mode must be None, 'fp8' or 'mxfp4', got {mode!r}")
         DECODE_WEIGHTS[0] = mode
 
     @staticmethod

@@ -150,6 +150,7 @@ def quantize_fp8_cols_t(W):
 # (load_state_dict, manual .copy_) move the tensor's own version counter.
 WEIGHT_VERSION = [0]
 _W8 = {}
+_W4 = {}       # the MXFP4 copies (mxfp4_weight), keyed and versioned the same way
 
 
 def bump_weight_version():
@@ -170,6 +171,32 @@ def fp8_weight(W, transposed=False):
 
 def clear_fp8_cache():
     _W8.clear()
+    _W4.clear()
+
+
+def quantize_mxfp4_rows(x):
+    """OCP MXFP4 (round to nearest, the format of include/macaw_hip.h) of a row-major bf16 / fp16 matrix [rows, cols]
+    (pitched rows allowed, cols % 32 == 0): returns (q uint8 [rows, cols / 2], two e2m1 codes per byte, low nibble
+    first; e uint8 [rows, cols / 32], one E8M0 exponent per block of 32 along the row, scale 2^(e - 127))"""
+    lib = _L.load()
+    rows, cols = x.shape
+    q = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
+    e = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+    _L.check(lib.mk_mxfp4_quantize_rows(_p(x), rows, cols, _rowmajor(x), dt(x), _p(q), max(cols // 2, 1), _p(e),
+                                        max(cols // 32, 1), _st()), "mk_mxfp4_quantize_rows")
+    return q, e
+
+
+def mxfp4_weight(W):
+    """cached MXFP4 copy (q [N, K / 2], e [N, K / 32]: quantize_mxfp4_rows) of weight W [N, K] for y = x W^T; made
+    once, re-made when the weight version moves (the rule of fp8_weight)"""
+    key = (W.data_ptr(), tuple(W.shape), W.stride(0))
+    ver = (WEIGHT_VERSION[0], W._version)
+    ent = _W4.get(key)
+    if ent is None or ent[0] != ver:
+        q, e = quantize_mxfp4_rows(W)
+        ent = _W4[key] = (ver, q, e)
+    return ent[1], ent[2]
 
 
 def linear_fp8(xq, sx, wq, sw, bias=None, act=0, residual=None, out=None, accumulate=False):
@@ -581,6 +608,32 @@ def decode_linear_fp8_ok(x, Wq, prologue=0):
     """mk_decode_linear_fp8's domain (Wq: the e4m3 copy, or the [N, K] 16-bit weight it will be made from); with
     a prologue the prepared token rows must fit 40 KiB of LDS"""
     return decode_linear_ok(x, Wq, prologue)       # one kernel skeleton, one domain: only the weight bytes differ
+
+
+def decode_linear_mxfp4(x, Wq, e, prologue=0, norm_w=None, eps=0.0, residual=None, out=None):
+    """decode_linear with the weight streamed as MXFP4 (W4A16): y[M <= 16, N] = prologue(x) dequant(Wq, e)^T
+    (+ residual); Wq uint8 [N, K / 2] row-major, e uint8 [N, K / 32] (the pair mxfp4_weight(W) returns); x, residual,
+    y bf16 or fp16, tokens not quantised, fp32 accumulation, the block scales applied while widening (exact)"""
+    lib = _L.load()
+    M = x.shape[0]
+    N, K = Wq.shape[0], 2 * Wq.shape[1]
+    if Wq.dtype != torch.uint8 or e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32):
+        raise MacawHipError(f"decode_linear_mxfp4: codes {Wq.dtype} {tuple(Wq.shape)}, exponents {e.dtype} {tuple(e.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _L.check(lib.mk_decode_linear_mxfp4(_p(x), _rowmajor(x), _p(Wq), _rowmajor(Wq), _p(e), _rowmajor(e), _p(out),
+                                        _rowmajor(out), _p(residual),
+                                        _rowmajor(residual) if residual is not None else 0, M, N, K, prologue,
+                                        _p(norm_w), eps, dt(x), _st()), "mk_decode_linear_mxfp4")
+    return out
+
+
+def decode_linear_mxfp4_ok(x, W, prologue=0):
+    """mk_decode_linear_mxfp4's domain (W: the uint8 codes [N, K / 2], or the [N, K] 16-bit weight they will be made
+    from): decode_linear_ok's rule with K % 128 == 0 (a K-block is four MX blocks and one dword of exponents)"""
+    M, K = x.shape[0], (2 * W.shape[1] if W.dtype == torch.uint8 else W.shape[1])
+    return (x.dtype in (torch.bfloat16, torch.float16) and M <= (16 if prologue else 32) and K % 128 == 0 and W.is_contiguous()
+            and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
 
 
 def decode_emit(logits, V, pad, eos, tok, done, out, state):

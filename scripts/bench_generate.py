@@ -25,15 +25,20 @@ with torch.no_grad():
 # B = 32) whose text lengths fall linearly from N (default 1900) to M (default 150), once with attention_mask= (the compacted,
 # ragged KV cache: a step streams the sum of the real lengths) and once as today's call without a mask (every sample streams
 # all S0 rows and attends to its pad tokens), alternated the same way, with the KV bytes a step reads in each mode
+#        bench_generate.py --mxfp4-ab [--reps R] [B ...]: the --fp8-ab alternation over THREE modes, bf16 / fp8 / mxfp4 (default
+# B = 1 8 16 32, R = 5): the bytes each mode streams per token (mxfp4: codes + E8M0 exponents of the layers' projections, the
+# e4m3 lm_head with its f32 scales), ms per token of every run, the medians, the implied bandwidth, the ratios and the
+# run-to-run spread of every mode (a difference counts only beyond the spreads)
 AB = "--fp8-ab" in sys.argv
+MX4 = "--mxfp4-ab" in sys.argv
 RAGGED = "--ragged-ab" in sys.argv
 SAMPLE = "--sample-ab" in sys.argv
 KV8 = "--kv8-ab" in sys.argv
 _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
-REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
+REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
 if SAMPLE:
     from macaw_llm_amd import ops
     SKW = dict(do_sample=True, top_k=50, top_p=0.9, seed=1)
@@ -132,6 +137,44 @@ if KV8:
         print(f"B={B:2d} S0={S0}: kv bf16 {med[None]:6.3f} ms/token ({kvb[None] / 1e9:6.3f} GB of KV per token), kv fp8 "
               f"{med['fp8']:6.3f} ms/token ({kvb['fp8'] / 1e9:6.3f} GB), fp8 / bf16 = {med['fp8'] / med[None]:5.3f} "
               f"(bf16 run-to-run spread {spread * 100:4.1f} %)", flush=True)
+    sys.exit(0)
+if MX4:
+    proj = [lyr.fused_weights() + (lyr.self_attn.o_proj.weight, lyr.mlp.down_proj.weight) for lyr in model.llm.model.layers]
+    proj = [w for ws in proj for w in ws]
+    head = model.llm.lm_head.weight
+    MODES = (None, "fp8", "mxfp4")
+    BYTES = {None: sum(2 * w.numel() for w in proj + [head]), "fp8": sum(w.numel() + 4 * w.shape[0] for w in proj + [head]),
+             "mxfp4": sum(w.numel() // 2 + w.numel() // 32 for w in proj) + head.numel() + 4 * head.shape[0]}
+    print("streamed per token: " + ", ".join(f"{m or 'bf16'} {BYTES[m] / 1e9:.3f} GB" for m in MODES) +
+          " (mxfp4: e2m1 codes + E8M0 exponents of the layers' projections, e4m3 lm_head)", flush=True)
+    with torch.no_grad():       # the quantised copies are made here, outside the timed calls
+        for mode in MODES[1:]:
+            model.llm.generate(inputs_embeds=model.prepare_inputs_for_generation(_w)[0], max_new_tokens=4, eos_token_id=-1,
+                               decode_weights=mode)
+    for B in [int(a) for a in _args] or [1, 8, 16, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {m: [] for m in MODES}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for mode in MODES:  # untimed: each mode's first call at this batch size (kernel attributes, allocator pools)
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=-1, decode_weights=mode)
+            for rep in range(REPS):
+                for mode in MODES:
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, decode_weights=mode)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {mode or 'bf16':5s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = {m: (max(v) - min(v)) / med[m] for m, v in ms.items()}
+        print(f"B={B:2d}: " + ", ".join(f"{m or 'bf16'} {med[m]:6.3f} ms/token ({BYTES[m] / med[m] / 1e9:4.2f} TB/s, spread "
+                                        f"{spread[m] * 100:4.1f} %)" for m in MODES) +
+              f"; fp8 / bf16 = {med['fp8'] / med[None]:5.3f}, mxfp4 / bf16 = {med['mxfp4'] / med[None]:5.3f}, "
+              f"mxfp4 / fp8 = {med['mxfp4'] / med['fp8']:5.3f}: mxfp4 is "
+              f"{'OUTSIDE' if med['fp8'] - med['mxfp4'] > max(spread['fp8'] * med['fp8'], spread['mxfp4'] * med['mxfp4']) else 'inside'}"
+              " the fp8 / mxfp4 spreads", flush=True)
     sys.exit(0)
 if AB:
     streamed = [lyr.fused_weights() + (lyr.self_attn.o_proj.weight, lyr.mlp.down_proj.weight) for lyr in model.llm.model.layers]

@@ -1,4 +1,4 @@
-"""one generate() call (B from argv, 40 new tokens; second argument fp8 = decode_weights="fp8") for profiling the decode step"""
+"""one generate() call (B from argv, 40 new tokens; second argument fp8 / mxfp4 = decode_weights="fp8" / "mxfp4") for profiling the decode step"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from macaw_llm_amd.factory import baseline_config, build_model, synthetic_inputs
