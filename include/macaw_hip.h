@@ -36,7 +36,7 @@ extern "C" {
 #define MK_FP8 3 /* OCP e4m3fn bytes: mk_gemm operands / mk_fp8_quantize output only */
 
 /* library identification: returns MK_ABI_VERSION */
-#define MK_ABI_VERSION 9
+#define MK_ABI_VERSION 10
 int mk_abi_version(void);
 
 /* ------------------------------------------------------------------ GEMM --
@@ -113,6 +113,32 @@ int mk_gemm_has_cfg(int cfg);
  * kernel choice follow.  Values at or above the device's CU count mean all as well.  Returns the previous value.
  * Pinned by tests/test_gemm_plans_gpu.py. */
 int mk_gemm_set_cus(int n_cus);
+/* Grouped launch on the 256 x 256 v9 loop: ONE launch of one persistent workgroup per planned CU (mk_gemm_set_cus is
+ * honoured) that runs whole tiles of several GEMMs -- an optional `main` problem, a grad-input GEMM (layout (0,1)), and
+ * `n_fill` grad-weight GEMMs (layout (1,1)) whose tiles fill the CUs that the main problem's partial last round leaves
+ * idle.  A filler may be consumed over several launches: tiles [0, first_tile) of its tile order are done already, and
+ * on return `taken` says how many more this launch ran (they start at first_tile).  drain = 0 takes only what balances
+ * the launch and leaves the rest queued; drain = 1 takes everything.  main may be NULL (a plain grouped grad-weight
+ * launch: whole rounds of the queue, everything with drain).  Every tile is computed exactly as mk_gemm's
+ * configuration 15 computes a whole tile, so results do not depend on how the tiles were grouped.
+ * The members of one launch run concurrently and in no defined order, so they must be independent: no member's A or B
+ * may overlap another member's C (a filler cannot consume the main's output of the same launch), and no two C regions
+ * may overlap.  The library does not check this.
+ * Every member must be bf16 or f16 (one type for all), unbatched, M % 256 == N % 256 == 0, K % 64 == 0, K >= 128,
+ * alpha only (no bias / activation / R / accumulate / scales / flags), operands as configuration 15 needs them
+ * (16-byte aligned, pitches % 8 == 0) and C 8-byte aligned with ldc % 4 == 0; at most MK_GROUP_MAX_FILL fillers with
+ * fewer than 65536 remaining tiles in all.  Otherwise MK_NOT_GROUPED is returned, nothing is launched or written and
+ * the caller runs the members through mk_gemm.  In the profiler a grouped launch is one kind-0 launch with
+ * configuration id 16, the main's shape (the first filler's without one) and the FLOPs of the tiles it ran.
+ * Replaces cuBLAS behind the backward of nn.Linear (modeling.py:134-140,159-162). */
+#define MK_NOT_GROUPED 1
+#define MK_GROUP_MAX_FILL 8
+typedef struct mk_gemm_group_fill {
+  mk_gemm_desc d;
+  int32_t first_tile; /* in: tiles already done */
+  int32_t taken;      /* out: tiles this launch ran */
+} mk_gemm_group_fill;
+int mk_gemm_grouped(const mk_gemm_desc* main, mk_gemm_group_fill* fill, int32_t n_fill, int32_t drain, void* stream);
 /* Optional live timing of every mk_gemm launch with HIP events on the launch stream
  * (bench.py roofline): begin, run, then end() synchronises and returns the sums. */
 int mk_prof_begin(void);

@@ -56,7 +56,7 @@ def _digest(paths) -> str:
 
 def build(force: bool = False, verbose: bool = True) -> Path:
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / "common.h", CSRC / "gemm_common.h", PKG.parent / "include" / "macaw_hip.h",
+    deps = srcs + [CSRC / "common.h", CSRC / "gemm_common.h", CSRC / "gemm_group_plan.h", PKG.parent / "include" / "macaw_hip.h",
                    *sorted(CSRC.glob("*.inc"))]
     stamp = OBJ / "stamp.txt"
     dig = _digest(deps)

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "../../include/macaw_hip.h"
 #include "gemm_common.h"
+#include "gemm_group_plan.h"
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -300,6 +301,7 @@ int launch_v8(const GemmArgs& g, bool a_red, bool b_red, dim3 grid, hipStream_t 
 #endif
 int launch_v9(const GemmArgs& g, bool a_red, bool b_red, dim3 grid, hipStream_t st, bool f16);            // gemm_v9.hip
 int v9_mfma16_layouts();                                                                                        // gemm_v9.hip
+int launch_grp(const GrpArgs& g, bool has_main, int n_wg, hipStream_t st, bool f16);                            // gemm_v9.hip
 }
 
 // y[M <= 16, N] = prologue(x) W^T (+ residual): the linear layers of one decode position per sample
@@ -671,6 +673,78 @@ extern "C" int mk_gemm(const mk_gemm_desc* d_in, void* stream) {
   }
   mkp::end(prof, st);
   return mk_check_launch();
+}
+
+// One launch of whole v9 tiles of several problems: a grad-input GEMM and the grad-weight GEMMs queued behind it
+// (include/macaw_hip.h; kernel in gemm_v9_impl.inc, work plan in gemm_group_plan.h).
+extern "C" int mk_gemm_grouped(const mk_gemm_desc* main, mk_gemm_group_fill* fill, int32_t n_fill, int32_t drain,
+                               void* stream) {
+  static_assert(mkgp::MAX_FILL == GRP_MAX_FILL && mkgp::MAX_WG == GRP_MAX_WG && MK_GROUP_MAX_FILL == GRP_MAX_FILL, "one limit");
+  if (n_fill < 0 || (n_fill > 0 && !fill)) return MK_ERR_BAD_ARG;
+  for (int i = 0; i < n_fill; ++i) fill[i].taken = 0;
+  if (!main && n_fill == 0) return MK_OK;
+  if (n_fill > GRP_MAX_FILL || mkg::v9_mfma16_layouts() != 15) return MK_NOT_GROUPED;
+  const int dtype = main ? main->dtype : fill[0].d.dtype;
+  if (dtype != MK_BF16 && dtype != MK_F16) return MK_NOT_GROUPED;
+  const auto member = [&](const mk_gemm_desc& d, int a_red) {
+    if (!d.A || !d.B || !d.C || d.M <= 0 || d.N <= 0 || d.K <= 0) return MK_ERR_BAD_ARG;
+    const auto span = [&](bool red, long ld) { return red ? (long)d.K * ld * 2 : (256L * ld + d.K) * 2; };
+    const bool ok = d.dtype == dtype && d.a_red_major == a_red && d.b_red_major == 1 && d.nb1 == 1 && d.nb2 == 1 &&
+                    d.M % 256 == 0 && d.N % 256 == 0 && d.K % 64 == 0 && d.K >= 128 && d.bias_mode == 0 && !d.bias && d.act == 0 &&
+                    !d.R && !d.accumulate && !d.scale_a && !d.scale_b && d.flags == 0 && aligned16(d.A) && aligned16(d.B) &&
+                    d.lda % 8 == 0 && d.ldb % 8 == 0 && (reinterpret_cast<uintptr_t>(d.C) & 7) == 0 && d.ldc % 4 == 0 &&
+                    d.lda >= (a_red ? d.M : d.K) && d.ldb >= d.N && d.ldc >= d.N &&
+                    span(a_red != 0, d.lda) < 0x7fffffffL && span(true, d.ldb) < 0x7fffffffL;
+    return ok ? MK_OK : MK_NOT_GROUPED;
+  };
+  if (main) if (const int rc = member(*main, 0)) return rc;
+  int rem[GRP_MAX_FILL], nk[GRP_MAX_FILL];
+  for (int i = 0; i < n_fill; ++i) {
+    if (const int rc = member(fill[i].d, 1)) return rc;
+    const int tiles = (fill[i].d.M / 256) * (fill[i].d.N / 256);
+    if (fill[i].first_tile < 0 || fill[i].first_tile > tiles) return MK_ERR_BAD_ARG;
+    rem[i] = tiles - fill[i].first_tile;
+    nk[i] = fill[i].d.K / 64;
+  }
+  static const int dev_cus = [] {
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+  }();
+  const int n_wg = (g_plan_cus > 0 && g_plan_cus < dev_cus) ? g_plan_cus : dev_cus;
+  const int main_tiles = main ? (main->M / 256) * (main->N / 256) : 0;
+  mkgp::Plan plan;
+  if (!mkgp::plan(n_wg, main_tiles, main ? main->K / 64 : 0, n_fill, rem, nk, drain != 0, plan)) return MK_NOT_GROUPED;
+  GrpArgs g{};
+  const auto put = [](GrpProb& p, const mk_gemm_desc& d, int first, int count) {
+    p.A = d.A; p.B = d.B; p.C = d.C;
+    p.lda = d.lda; p.ldb = d.ldb; p.ldc = d.ldc;
+    p.M = d.M; p.N = d.N; p.K = d.K;
+    p.tiles_m = d.M / 256; p.tiles_n = d.N / 256;
+    p.first = first; p.count = count;
+    p.alpha = d.alpha;
+  };
+  double flops = 0;
+  if (main) { put(g.p[0], *main, 0, main_tiles); flops += 2.0 * main->M * main->N * main->K; }
+  long taken = 0;
+  for (int i = 0; i < n_fill; ++i) {
+    put(g.p[1 + i], fill[i].d, fill[i].first_tile, plan.taken[i]);
+    flops += 2.0 * 256 * 256 * fill[i].d.K * plan.taken[i];
+    taken += plan.taken[i];
+  }
+  if (main_tiles == 0 && taken == 0) return MK_OK;     // (nothing to run: fewer queued tiles than one whole round)
+  g.n_fill = n_fill;
+  g.main_tiles = main_tiles;
+  for (int r = 0; r <= GRP_MAX_WG; ++r) g.start[r] = plan.start[r];
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const mk_gemm_desc& shape = main ? *main : fill[0].d;
+  const int prof = mkp::begin(st, 0, flops, shape.M, shape.N, shape.K, 1, shape.a_red_major * 2 + shape.b_red_major, 16);
+  const int rc = mkg::launch_grp(g, main != nullptr, n_wg, st, dtype == MK_F16);
+  mkp::end(prof, st);
+  if (rc != MK_OK) return rc;
+  for (int i = 0; i < n_fill; ++i) fill[i].taken = plan.taken[i];
+  return MK_OK;
 }
 
 extern "C" int mk_transpose(const void* in, void* out, int32_t rows, int32_t cols, int64_t ld_in,

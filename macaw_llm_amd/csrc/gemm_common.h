@@ -33,6 +33,27 @@ struct GemmArgs {
   int* counters;   // arrival counter per tail tile (zeroed by the launcher)
 };
 
+// Grouped launch on the v9 loop (mk_gemm_grouped; kernel in gemm_v9_impl.inc, plan in gemm_group_plan.h): one optional
+// main problem p[0] (grad-input, K-major x reduction-major) and up to GRP_MAX_FILL fillers p[1 ...] (grad-weight, both
+// operands reduction-major), whole 256 x 256 tiles and alpha only.  The whole plan travels in the kernel arguments, so a
+// captured graph replays it without reading host or device memory.
+constexpr int GRP_MAX_FILL = 8, GRP_MAX_WG = 320;
+struct GrpProb {
+  const void* A; const void* B; void* C;
+  long lda, ldb, ldc;
+  int M, N, K;
+  int tiles_m, tiles_n;
+  int first, count;      // this launch computes tiles [first, first + count) of the problem's tile order (main: all of them)
+  float alpha;
+};
+struct GrpArgs {
+  GrpProb p[1 + GRP_MAX_FILL];
+  int n_fill;
+  int main_tiles;        // 0: no main problem
+  // the workgroup of rank r (gemm_group_plan.h wg_rank) runs start[r + 1] - start[r] filler tiles; which ones: wg_tile there
+  unsigned short start[GRP_MAX_WG + 1];
+};
+
 MK_DEV float apply_act(float v, int act) {
   if (act == 1) return 0.5f * v * (1.0f + mk_erf(v * 0.70710678118654752440f));
   if (act == 2) return v / (1.0f + __expf(-1.702f * v));

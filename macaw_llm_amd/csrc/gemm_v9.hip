@@ -39,8 +39,10 @@
 #define MK_E16_NS e_f16
 #define MK_V9_SFX "f16"
 #define gemm_bf16_v9_kernel gemm_f16_v9_kernel
+#define gemm_bf16_grp_kernel gemm_f16_grp_kernel
 #include "gemm_v9_impl.inc"
 #undef gemm_bf16_v9_kernel
+#undef gemm_bf16_grp_kernel
 #undef MK_E16_T
 #undef MK_E16_NS
 #undef MK_V9_SFX
@@ -66,5 +68,9 @@ int launch_v9(const GemmArgs& g, bool a_red, bool b_red, dim3 grid, hipStream_t 
   if (!a_red && b_red) return e_bf16::launch_v9<false, true>(g, grid, st);
   if (a_red && !b_red) return e_bf16::launch_v9<true, false>(g, grid, st);
   return e_bf16::launch_v9<true, true>(g, grid, st);
+}
+// the grouped launch (mk_gemm_grouped in gemm.hip): n_wg persistent workgroups over g's work lists
+int launch_grp(const GrpArgs& g, bool has_main, int n_wg, hipStream_t st, bool f16) {
+  return f16 ? e_f16::launch_grp(g, has_main, n_wg, st) : e_bf16::launch_grp(g, has_main, n_wg, st);
 }
 }  // namespace mkg

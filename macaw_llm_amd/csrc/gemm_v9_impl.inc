@@ -349,6 +349,202 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
   }
 }
 
+#if V9_MFMA16 == 15
+// ---- grouped launch (mk_gemm_grouped): one persistent workgroup per planned CU runs whole tiles of SEVERAL problems:
+// its tiles b, b + n, ... of the main problem g.p[0] (grad-input: A K-major, B reduction-major), then its run of filler
+// tiles (grad-weight: both reduction-major; GrpArgs in gemm_common.h, the plan in gemm_group_plan.h).  Per tile it is
+// gemm_bf16_v9_kernel's protocol with the problem looked up per tile: set-up, the first LDS-DMA requests, the generated
+// loop of the tile's layout, and the next tile's set-up and requests behind the barrier before this tile's epilogue --
+// also when the next tile has the other layout (the ring's slots and the wait protocol do not depend on the layout).
+// Every tile is computed by the instruction stream that gemm_bf16_v9_kernel runs on it.
+// gemm_bf16_v9_kernel itself stays as it is (its symbols, register budget and disassembly are pinned by tests), so two
+// pieces exist TWICE and must be kept in step by hand, since the bit-identity of the two paths rests on them:
+// grp_tile_setup restates v9_tile_setup (descriptor bounds, voffsets) for a GrpProb, and GRP_F16P restates V9_F16P
+// (alpha-only register epilogue, plain 8-byte stores: the MK_V9_NT_STORE experiment build does not reach this kernel).
+// v9_tile_request, v9_voffset, v9_read_offset16, the generated loops and the V9_ACC16_READ macros are shared.
+// tests/test_gemm_grouped_gpu.py compares the two paths bit for bit.
+template <bool A_RED>
+MK_DEV void grp_tile_setup(const GrpProb& p, int lin, int w, int l, V9Tile& t) {
+  int tm, tn;
+  tile_from_index(lin, p.tiles_m, p.tiles_n, tm, tn, 8);
+  const e16* A = reinterpret_cast<const e16*>(p.A);
+  const e16* B = reinterpret_cast<const e16*>(p.B);
+  t.C = reinterpret_cast<e16*>(p.C);
+  t.Rp = nullptr;
+  const int m0 = tm * BM9, n0 = tn * BN9;
+  t.m0 = m0; t.n0 = n0;
+  const e16* abase = uniform_ptr(A_RED ? A + m0 : A + (long)m0 * p.lda);
+  const e16* bbase = uniform_ptr(B + n0);
+  const long a_bytes = A_RED ? ((long)(p.K - 1) * p.lda + ((p.M - m0 + 1) & ~1)) * 2
+                             : ((long)(BM9 - 1) * p.lda + ((p.K + 1) & ~1)) * 2;
+  const long b_bytes = ((long)(p.K - 1) * p.ldb + ((p.N - n0 + 1) & ~1)) * 2;
+  const int a_rec = __builtin_amdgcn_readfirstlane((int)min(a_bytes, 0x7fffffffL));
+  const int b_rec = __builtin_amdgcn_readfirstlane((int)min(b_bytes, 0x7fffffffL));
+  t.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, a_rec, 0x00020000);
+  t.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)bbase, 0, b_rec, 0x00020000);
+  const uint64_t pa = reinterpret_cast<uint64_t>(abase), pb = reinterpret_cast<uint64_t>(bbase);
+  t.dA[0] = __builtin_amdgcn_readfirstlane((uint32_t)pa);
+  t.dA[1] = __builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32) & 0xffffu);
+  t.dA[2] = (uint32_t)a_rec;
+  t.dA[3] = 0x00020000u;
+  t.dB[0] = __builtin_amdgcn_readfirstlane((uint32_t)pb);
+  t.dB[1] = __builtin_amdgcn_readfirstlane((uint32_t)(pb >> 32) & 0xffffu);
+  t.dB[2] = (uint32_t)b_rec;
+  t.dB[3] = 0x00020000u;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      t.voA[h][i] = v9_voffset<A_RED, true>(m0, p.M, p.lda, h, w + 4 * i, l);
+      t.voB[h][i] = v9_voffset<true, true>(n0, p.N, p.ldb, h, w + 4 * i, l);
+    }
+}
+
+// The workgroup's work list (wave-uniform throughout): its main tiles b, b + n, ..., then its filler tiles.  Fillers are
+// dealt ROUND by round inside a group of workgroups (gemm_group_plan.h: the workgroups of one XCD): the group owns the
+// indices [start[g0], start[g1]) of the taken filler tiles laid end to end, and in round j the workgroups that still
+// have a j-th tile (count > j) take the next indices in rank order.  Lane i holds the count of the group's i-th member.
+struct GrpCursor {
+  int mt, stride;          // next main tile and the stride n
+  int j, cnt, base;        // filler round, this workgroup's count, first index of round j
+  int cl;                  // per lane: count of the group's member `lane`
+  uint64_t below;          // lanes of the members before this workgroup
+};
+template <bool HAS_MAIN>
+MK_DEV bool grp_next(const GrpArgs& g, GrpCursor& c, int& pi, int& lin) {
+  if (HAS_MAIN && c.mt < g.main_tiles) {
+    pi = 0;
+    lin = xcd_remap(c.mt, g.main_tiles);
+    c.mt += c.stride;
+    return true;
+  }
+  if (c.j >= c.cnt) return false;
+  const uint64_t act = __builtin_amdgcn_ballot_w64(c.cl > c.j);
+  int at = c.base + __builtin_popcountll(act & c.below), f = 1;
+  c.base += __builtin_popcountll(act);
+  ++c.j;
+  while (f < g.n_fill && at >= g.p[f].count) at -= g.p[f++].count;
+  pi = f;
+  lin = g.p[f].first + at;
+  return true;
+}
+
+template <bool HAS_MAIN>
+__global__ __launch_bounds__(256, 1) void gemm_bf16_grp_kernel(GrpArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int l = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr = w >> 1, wc = w & 1;
+  const int wm0 = wr * 128, wn0 = wc * 128;
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(size_t)((__attribute__((address_space(3))) char*)smem));
+  const uint32_t wv = lds0 + (uint32_t)w * 1024u;
+  const uint32_t adA_k = lds0 + wr * HALF_BYTES + v9_read_offset16<false>(l);
+  const uint32_t adA_r = lds0 + wr * HALF_BYTES + v9_read_offset16<true>(l);
+  const uint32_t adB = lds0 + B_BASE9 + wc * HALF_BYTES + v9_read_offset16<true>(l);
+  const int n = (int)gridDim.x, b = (int)blockIdx.x;
+  const int rank = (n & 7) == 0 ? (b & 7) * (n >> 3) + (b >> 3) : b;      // gemm_group_plan.h wg_rank
+  const int gw = (n & 7) == 0 ? n >> 3 : 64;                             // gemm_group_plan.h group_width
+  const int g0 = rank / gw * gw, gsz = min(gw, n - g0);
+  GrpCursor cur;
+  cur.mt = b; cur.stride = n;
+  cur.j = 0; cur.cnt = (int)g.start[rank + 1] - (int)g.start[rank]; cur.base = g.start[g0];
+  cur.cl = l < gsz ? (int)g.start[g0 + l + 1] - (int)g.start[g0 + l] : 0;
+  cur.below = (1ull << (rank - g0)) - 1;
+  int pi, lin;
+  if (!grp_next<HAS_MAIN>(g, cur, pi, lin)) return;      // (a workgroup without work is legal)
+  V9Tile t;
+  bool a_red;
+  int nk, stepA, stepB, iA, iB;
+  uint32_t adA;
+  // set-up of one tile: the descriptor words and offsets in t, the loop's scalars beside it
+#define GRP_SETUP()                                                                               \
+  do {                                                                                            \
+    pi = __builtin_amdgcn_readfirstlane(pi);                                                      \
+    const GrpProb& p_ = g.p[pi];                                                                  \
+    a_red = !HAS_MAIN || pi != 0;                                                                 \
+    if (a_red) grp_tile_setup<true>(p_, lin, w, l, t);                                            \
+    else grp_tile_setup<false>(p_, lin, w, l, t);                                                 \
+    nk = __builtin_amdgcn_readfirstlane(p_.K / BK7);                                              \
+    stepA = __builtin_amdgcn_readfirstlane(a_red ? (int)(BK7 * p_.lda * 2) : BK7 * 2);            \
+    stepB = __builtin_amdgcn_readfirstlane((int)(BK7 * p_.ldb * 2));                              \
+    iA = __builtin_amdgcn_readfirstlane((int)((a_red ? 16 : 32) * p_.lda * 2));                   \
+    iB = __builtin_amdgcn_readfirstlane((int)(16 * p_.ldb * 2));                                  \
+    adA = a_red ? adA_r : adA_k;                                                                  \
+  } while (0)
+  GRP_SETUP();
+  v9_tile_request(t, smem, w, stepA, stepB);
+  bool first = true;
+  for (;;) {
+    __builtin_amdgcn_sched_barrier(0);
+#define GRP_LOOP(TEXT)                                                                            \
+  asm volatile(TEXT                                                                               \
+               :                                                                                  \
+               : [voA] "v"(t.voA[0][0]), [voB] "v"(t.voB[0][0]), [adA] "v"(adA), [adB] "v"(adB),   \
+                 [rsA] "s"(t.dA), [rsB] "s"(t.dB), [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA),   \
+                 [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)                                      \
+               : V9_LOOP16_CLOBBERS)
+    if (HAS_MAIN && !a_red) {
+      if (first) GRP_LOOP(V9_LOOP16_TEXT_01);
+      else GRP_LOOP(V9_LOOP16_TEXT_01_W);
+    } else {
+      if (first) GRP_LOOP(V9_LOOP16_TEXT_11);
+      else GRP_LOOP(V9_LOOP16_TEXT_11_W);
+    }
+#undef GRP_LOOP
+    __builtin_amdgcn_sched_barrier(0);
+    // this tile's output position, then the next tile: its requests go out BEFORE the epilogue
+    const int m0 = t.m0, n0 = t.n0;
+    e16* C = t.C;
+    const long ldc = g.p[pi].ldc;
+    const float alpha = g.p[pi].alpha;
+    const bool more = grp_next<HAS_MAIN>(g, cur, pi, lin);
+    if (more) {
+      GRP_SETUP();
+      __builtin_amdgcn_s_barrier();            // every wave has read its last fragments: the ring may be refilled
+      v9_tile_request(t, smem, w, stepA, stepB);
+    }
+    // the register epilogue of the 16 x 16 fragments, alpha only (as gemm_bf16_v9_kernel's V9_F16P)
+    e16* crow = C + (long)(m0 + wm0 + (l & 15)) * ldc + n0 + wn0 + 4 * (l >> 4);
+#define GRP_F16P(I, J)                                                                            \
+  do {                                                                                            \
+    float t_[4];                                                                                  \
+    V9_ACC16_READ_##I##_##J(t_);                                                                  \
+    e16x4 o_;                                                                                     \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * alpha);             \
+    *reinterpret_cast<e16x4*>(crow + (long)(16 * (I)) * ldc + 16 * (J)) = o_;                     \
+  } while (0)
+#define GRP_R16(I)                                                                                \
+  do {                                                                                            \
+    GRP_F16P(I, 0); GRP_F16P(I, 1); GRP_F16P(I, 2); GRP_F16P(I, 3);                               \
+    GRP_F16P(I, 4); GRP_F16P(I, 5); GRP_F16P(I, 6); GRP_F16P(I, 7);                               \
+    __builtin_amdgcn_sched_barrier(0);                                                            \
+  } while (0)
+    GRP_R16(0); GRP_R16(1); GRP_R16(2); GRP_R16(3); GRP_R16(4); GRP_R16(5); GRP_R16(6); GRP_R16(7);
+#undef GRP_R16
+#undef GRP_F16P
+    if (!more) break;
+    first = false;
+  }
+#undef GRP_SETUP
+}
+
+int launch_grp(const GrpArgs& g, bool has_main, int n_wg, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_grp_kernel<true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS9) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_grp_kernel<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS9) != hipSuccess)
+      return MK_ERR_LAUNCH;
+    attr_done = true;
+  }
+  if (has_main) MK_LAUNCH((gemm_bf16_grp_kernel<true>), dim3(n_wg), dim3(256), LDS9, st, g);
+  else MK_LAUNCH((gemm_bf16_grp_kernel<false>), dim3(n_wg), dim3(256), LDS9, st, g);
+  return mk_check_launch();
+}
+#endif  // V9_MFMA16 == 15
+
 template <bool A_RED, bool B_RED>
 int launch_v9(const GemmArgs& g, dim3 grid, hipStream_t st) {
   static bool attr_done = false;

@@ -195,6 +195,12 @@ class _DwSide:
         DW_SIDE["launches"] = DW_SIDE.get("launches", 0) + 1      # (for the tests: did anything go through the side stream?)
         return out
 
+    def pair(self, dy, W, x, name, want_dw, fp8=False, drain=False):
+        """(dx = dy W, dW = dy^T x or None) of one projection: the grad-input launch first, its partner beside it"""
+        ev = self.fork()
+        dx = _fp8_dx(dy, W) if fp8 else ops.linear_dx(dy, W)
+        return dx, (self.dw(ev, dy, x, W, name) if want_dw else None)
+
     def join(self):
         if self.side is not None and self.used:
             # More than one rank (the stream is then on only if FORCED): a HOST wait in front of the stream-ordered one.  With the
@@ -206,6 +212,52 @@ class _DwSide:
                              and torch.distributed.get_world_size() > 1):
                 self.side.synchronize()
             self.main.wait_stream(self.side)
+
+
+# Grad-weight tiles inside the grad-input launches of a decoder layer (ops.DwQueue / mk_gemm_grouped): the layer's four
+# grad-input GEMMs run whole 256 x 256 tiles only, and the CUs that a partial last round leaves idle compute tiles of the
+# layer's grad-weight GEMMs in the same launch -- dW(down) queued before dx(down), dW(gate|up) before dx(gate|up), dW(o)
+# before dx(o), dW(q|k|v) before dx(q|k|v), whose launch drains the queue.  One stream, no events: every gradient of the
+# layer is complete on the compute stream when its backward returns, under graph capture and planned CU counts alike.
+# Every tile is computed as mk_gemm computes a whole tile, so results are bit-identical.  A layer takes this path only
+# when all four projections are groupable (16-bit, fused q|k|v and gate|up storage, whole tiles, no fp8 grad-input, no
+# LoRA, every weight gradient wanted); other layers keep _DwSide.  Both are the projection backend of the ONE backward body.
+# MACAW_DW_FILL = 0 | 1 | auto; DW_FILL["on"] at run time.  Measured: profiles/dw_fill_cfg3.txt.
+DW_FILL = {"on": {"0": False, "1": True}.get(os.environ.get("MACAW_DW_FILL", "auto"), "auto"), "layers": 0}
+DW_FILL_AUTO = True        # what "auto" means
+
+
+def _dw_fill_ok(M, D, FF, x2, need, lo, gu, wqkv, wgu, fp8_any) -> bool:
+    """may this layer's backward run its grad-weight GEMMs as fillers of its grad-input launches?"""
+    on = DW_FILL["on"]
+    if on == "auto":
+        on = DW_FILL_AUTO
+    if not on or lo is not None or gu is None or wqkv is None or wgu is None or fp8_any or not x2.is_cuda:
+        return False
+    if x2.dtype not in (torch.bfloat16, torch.float16) or not all(need[7:14]):
+        return False
+    # whole 256 x 256 x 64 tiles in all eight products (M is an output extent of dx and the reduction of dW)
+    return M % 256 == 0 and D % 256 == 0 and FF % 256 == 0
+
+
+class _DwFill:
+    """the projections' backward of a groupable layer (DW_FILL): _DwSide's interface over an ops.DwQueue"""
+
+    def __init__(self):
+        DW_FILL["layers"] += 1
+        self.q = ops.DwQueue()
+
+    def pair(self, dy, W, x, name, want_dw, fp8=False, drain=False):
+        """dW is queued BEFORE the grad-input launch, which takes its tiles as fillers (all that is queued with drain);
+        its destination is the weight's gradient-bucket slot, else a fresh tensor"""
+        out = ops.grad_dst(W)
+        if out is None:
+            out = torch.empty((dy.shape[1], x.shape[1]), dtype=dy.dtype, device=dy.device)
+        dw = self.q.push(dy, x, out)
+        return self.q.dx(dy, W, drain=drain), dw
+
+    def join(self):
+        self.q.flush()           # (nothing is left behind a draining launch)
 
 
 def _fp8_ok(x, W) -> bool:
@@ -472,25 +524,26 @@ class LlamaLayerFn(torch.autograd.Function):
             lg = {}
         need = ctx.needs_input_grad
         dout2 = _c2(dout, M, D)
-        sd = _DwSide(x2.device, M, D)
         # ---- MLP
         fp8_mlp = FP8["mlp"] and gu is not None and _fp8_dx_ok(dout2, wd) and _fp8_ok(y2, wgu)
-        ev = sd.fork()
-        da = _fp8_dx(dout2, wd) if fp8_mlp else ops.linear_dx(dout2, wd)
-        dwd = sd.dw(ev, dout2, a, wd, "down") if need[13] else None
+        # the projections' backward: grad-weight tiles inside the grad-input launches (DW_FILL), else launch by launch
+        # with the grad-weight GEMMs on a second stream where that pays (DW_SIDE)
+        if _dw_fill_ok(M, D, FF, x2, need, lo, gu, wqkv, wgu, fp8_mlp or FP8["qkv"]):
+            sd = _DwFill()
+        else:
+            sd = _DwSide(x2.device, M, D)
+        da, dwd = sd.pair(dout2, wd, a, "down", need[13], fp8=fp8_mlp)
         if "down" in lg:
             _lora_bwd(lora, lg["down"], a, lut["down"], [dout2], da, grads)
         dwg = dwu = None
         if gu is not None:
             dgu = ops.swiglu2d_bwd(gu, da, FF)
             del da
-            ev = sd.fork()
-            dy2 = _fp8_dx(dgu, wgu) if (fp8_mlp and _fp8_dx_ok(dgu, wgu)) else ops.linear_dx(dgu, wgu)
+            dy2, dwgu = sd.pair(dgu, wgu, y2, "gu", need[11] or need[12], fp8=fp8_mlp and _fp8_dx_ok(dgu, wgu))   # [2FF, D]
             if "gu" in lg:
                 _lora_bwd(lora, lg["gu"], y2, lut["gu"], [(dgu[:, :FF], dgu[:, FF:])[m - 4] for m, _, _ in lg["gu"]],
                           dy2, grads)
-            if need[11] or need[12]:
-                dwgu = sd.dw(ev, dgu, y2, wgu, "gu")             # [2FF, D]
+            if dwgu is not None:
                 dwg, dwu = dwgu[:FF], dwgu[FF:]
             del dgu
         else:
@@ -505,9 +558,7 @@ class LlamaLayerFn(torch.autograd.Function):
             del dg, du
         dh1, dln2 = ops.rmsnorm_bwd(dy2, h1, ln2, rstd2, dres=dout2, dw_out=ops.grad_dst(ln2) if need[15] else None)
         # ---- attention
-        ev = sd.fork()
-        datt = ops.linear_dx(dh1, wo)
-        dwo = sd.dw(ev, dh1, att, wo, "o") if need[10] else None
+        datt, dwo = sd.pair(dh1, wo, att, "o", need[10])
         if "o" in lg:
             _lora_bwd(lora, lg["o"], att, lut["o"], [dh1], datt, grads)
         ldq = q.stride(0)
@@ -536,15 +587,12 @@ class LlamaLayerFn(torch.autograd.Function):
         dwq = dwk = dwv = None
         lora_qkv = lg.get("qkv")
         if wqkv is not None:
-            ev = sd.fork()
-            if FP8["qkv"] and _fp8_dx_ok(dqkv, wqkv) and _fp8_ok(y1, wqkv):
-                dy1 = _fp8_dx(dqkv, wqkv)                      # e4m3 dy x e4m3 W^T (cfg 5)
-            else:
-                dy1 = ops.linear_dx(dqkv, wqkv)
+            # (fp8: e4m3 dy x e4m3 W^T, cfg 5)    the layer's last projection: a fill queue is drained here
+            dy1, dwqkv = sd.pair(dqkv, wqkv, y1, "qkv", need[7] or need[8] or need[9],
+                                 fp8=FP8["qkv"] and _fp8_dx_ok(dqkv, wqkv) and _fp8_ok(y1, wqkv), drain=True)   # [3D, D]
             if lora_qkv:
                 _lora_bwd(lora, lora_qkv, y1, lut["qkv"], [(dq, dk, dv)[m] for m, _, _ in lora_qkv], dy1, grads)
-            if need[7] or need[8] or need[9]:
-                dwqkv = sd.dw(ev, dqkv, y1, wqkv, "qkv")          # [3D, D]
+            if dwqkv is not None:
                 dwq, dwk, dwv = dwqkv[:D], dwqkv[D:2 * D], dwqkv[2 * D:]
         else:
             dy1 = ops.linear_dx(dq, wq)

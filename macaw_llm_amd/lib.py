@@ -19,7 +19,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "libmacaw_hip.so"
 
 MK_F32, MK_BF16, MK_F16, MK_FP8 = 0, 1, 2, 3
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _ERR = {-1: "MK_ERR_BAD_ARG", -2: "MK_ERR_UNSUPPORTED", -3: "MK_ERR_LAUNCH"}
 
@@ -47,12 +47,21 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GroupFill(C.Structure):
+    """mk_gemm_group_fill: a queued grad-weight GEMM of mk_gemm_grouped"""
+    _fields_ = [("d", GemmDesc), ("first_tile", C.c_int32), ("taken", C.c_int32)]
+
+
+NOT_GROUPED = 1          # mk_gemm_grouped: a member is outside its domain, nothing was launched
+GROUP_MAX_FILL = 8
+
 _vp, _i32, _i64, _f32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
 # name -> argtypes; every symbol declared in include/macaw_hip.h
 SIGNATURES = {
     "mk_abi_version": [],
     "mk_gemm": [C.POINTER(GemmDesc), _vp],
+    "mk_gemm_grouped": [C.POINTER(GemmDesc), C.POINTER(GroupFill), _i32, _i32, _vp],
     "mk_gemm_set_cfg": [_i32],
     "mk_gemm_has_cfg": [_i32],
     "mk_gemm_set_cus": [_i32],

@@ -74,7 +74,18 @@ def gemm_raw(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_red=False, b_red=False, R=No
              flags=0):
     """Direct struct fill. *_off are element offsets added to the base pointers.
     flags: MK_GEMM_A_KPAD_ZERO (1) / MK_GEMM_B_KPAD_ZERO (2), see include/macaw_hip.h."""
-    lib = _L.load()
+    d = gemm_desc(A, B, Cc, M, N, K, lda, ldb, ldc, a_red=a_red, b_red=b_red, R=R, ldr=ldr, bias=bias, bias_mode=bias_mode,
+                  act=act, accumulate=accumulate, alpha=alpha, nb1=nb1, nb2=nb2, sA=sA, sB=sB, sC=sC, sR=sR, a_off=a_off,
+                  b_off=b_off, c_off=c_off, r_off=r_off, flags=flags)
+    _L.check(_L.load().mk_gemm(C.byref(d), _st()), "mk_gemm")
+    return Cc
+
+
+def gemm_desc(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_red=False, b_red=False, R=None, ldr=0,
+              bias=None, bias_mode=0, act=0, accumulate=False, alpha=1.0, nb1=1, nb2=1,
+              sA=(0, 0), sB=(0, 0), sC=(0, 0), sR=(0, 0), a_off=0, b_off=0, c_off=0, r_off=0,
+              flags=0):
+    """the mk_gemm_desc of gemm_raw's arguments (the caller keeps the tensors alive until the launch)"""
     es = A.element_size()
     d = GemmDesc()
     d.A = _p(A) + a_off * es
@@ -100,8 +111,70 @@ def gemm_raw(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_red=False, b_red=False, R=No
     d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
     if B.dtype != A.dtype or Cc.dtype != A.dtype:
         raise MacawHipError("gemm: mixed dtypes")
-    _L.check(lib.mk_gemm(C.byref(d), _st()), "mk_gemm")
-    return Cc
+    return d
+
+
+class DwQueue:
+    """Grad-weight GEMMs waiting to fill the idle CUs of grad-input launches (mk_gemm_grouped, include/macaw_hip.h).
+
+    push() queues dW = dy^T x; dx() launches a grad-input GEMM together with as many queued tiles as balance it (all of
+    them with drain).  dy, x and the destination of a queued product stay referenced until its last tile has been
+    launched; everything runs on the current stream.  A member that the grouped kernel cannot take makes the launch fall
+    back to mk_gemm for the whole queue and the grad-input GEMM (same results: every tile is computed the same way)."""
+
+    def __init__(self):
+        self.items = []          # [desc, tiles done, tiles, (dy, x, out)]
+        self.grouped = 0         # launches that went through mk_gemm_grouped
+
+    def push(self, dy, x, out):
+        M, N = dy.shape
+        K = x.shape[1]
+        d = gemm_desc(dy, x, out, N, K, M, _rowmajor(dy), _rowmajor(x), _rowmajor(out), a_red=True, b_red=True)
+        self.items.append([d, 0, ((N + 255) // 256) * ((K + 255) // 256), (dy, x, out)])
+        return out
+
+    def _launch(self, main, drain, limit=_L.GROUP_MAX_FILL):
+        lib = _L.load()
+        live = self.items[:limit]
+        arr = (_L.GroupFill * max(len(live), 1))()
+        for f, it in zip(arr, live):
+            f.d, f.first_tile = it[0], it[1]
+        rc = lib.mk_gemm_grouped(C.byref(main) if main is not None else None, arr, len(live), int(drain), _st())
+        if rc == _L.NOT_GROUPED:
+            return False
+        _L.check(rc, "mk_gemm_grouped")
+        for f, it in zip(arr, live):
+            it[1] += f.taken
+        self.items = [it for it in self.items if it[1] < it[2]]
+        self.grouped += 1
+        return True
+
+    def flush(self):
+        """run everything that is queued.  One grouped launch if it is accepted; else problem by problem, so that a partly
+        computed (hence legal) one still finishes grouped and only a problem outside the grouped domain goes to mk_gemm"""
+        while self.items and self._launch(None, True):
+            pass
+        while self.items:
+            head = self.items[0]
+            if self._launch(None, True, limit=1):
+                continue
+            if head[1]:      # (cannot happen: the launch that computed its first tiles accepted this descriptor)
+                raise MacawHipError("mk_gemm_grouped refused a partly computed grad-weight GEMM")
+            _L.check(_L.load().mk_gemm(C.byref(head[0]), _st()), "mk_gemm")
+            self.items.pop(0)
+
+    def dx(self, dy, W, drain=False):
+        """dx[M, K] = dy[M, N] @ W[N, K] (linear_dx) with queued grad-weight tiles in the same launch"""
+        M, N = dy.shape
+        K = W.shape[1]
+        out = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
+        d = gemm_desc(dy, W, out, M, K, N, _rowmajor(dy), _rowmajor(W), _rowmajor(out), b_red=True)
+        if not self._launch(d, drain or len(self.items) >= _L.GROUP_MAX_FILL):
+            self.flush()
+            _L.check(_L.load().mk_gemm(C.byref(d), _st()), "mk_gemm")
+        elif drain:
+            self.flush()         # (only if more problems were queued than one launch takes)
+        return out
 
 
 # --------------------------------------------------------------------- fp8 --
