@@ -64,24 +64,20 @@ MK_DEV int v9_read_offset16(int l) {
   }
 }
 
-template <bool A_RED, bool B_RED>
-MK_DEV void v9_tile_setup(const GemmArgs& g, int tile, int w, int l, V9Tile& t) {
+// The operand part of a tile's set-up, for gemm_bf16_v9_kernel and gemm_bf16_grp_kernel alike: descriptors of the A and B
+// panels of the tile at (m0, n0) (the compiler's form and four scalar words each for the asm block) and the lane's LDS-DMA
+// voffsets.  P: the problem (GemmArgs or GrpProb: M, N, K, lda, ldb); A, B: its operands.  CLAMP: a K-major panel's record
+// ends at the matrix edge when fewer than 256 rows are left (a launch of whole tiles needs no clamp).
+template <bool A_RED, bool B_RED, bool CLAMP, typename P>
+MK_DEV void v9_operand_setup(const P& g, const e16* A, const e16* B, int m0, int n0, int w, int l, V9Tile& t) {
   constexpr bool M16 = ((V9_MFMA16 >> (2 * (A_RED ? 1 : 0) + (B_RED ? 1 : 0))) & 1) != 0;
-  int tm, tn;
-  tile_from_index(xcd_remap(tile, g.dp_tiles), g.tiles_m, g.tiles_n, tm, tn, 8);
-  const int z = blockIdx.z, z1 = z / g.nb2, z2 = z - z1 * g.nb2;
-  const e16* A = reinterpret_cast<const e16*>(g.A) + z1 * g.sA1 + z2 * g.sA2;
-  const e16* B = reinterpret_cast<const e16*>(g.B) + z1 * g.sB1 + z2 * g.sB2;
-  t.C = reinterpret_cast<e16*>(g.C) + z1 * g.sC1 + z2 * g.sC2;
-  t.Rp = g.R ? reinterpret_cast<const e16*>(g.R) + z1 * g.sR1 + z2 * g.sR2 : nullptr;
-  const int m0 = tm * BM9, n0 = tn * BN9;
   t.m0 = m0; t.n0 = n0;
   const e16* abase = uniform_ptr(A_RED ? A + m0 : A + (long)m0 * g.lda);
   const e16* bbase = uniform_ptr(B_RED ? B + n0 : B + (long)n0 * g.ldb);
   const long a_bytes = A_RED ? ((long)(g.K - 1) * g.lda + ((g.M - m0 + 1) & ~1)) * 2
-                             : ((long)(min(g.M - m0, BM9) - 1) * g.lda + ((g.K + 1) & ~1)) * 2;
+                             : ((long)((CLAMP ? min(g.M - m0, BM9) : BM9) - 1) * g.lda + ((g.K + 1) & ~1)) * 2;
   const long b_bytes = B_RED ? ((long)(g.K - 1) * g.ldb + ((g.N - n0 + 1) & ~1)) * 2
-                             : ((long)(min(g.N - n0, BN9) - 1) * g.ldb + ((g.K + 1) & ~1)) * 2;
+                             : ((long)((CLAMP ? min(g.N - n0, BN9) : BN9) - 1) * g.ldb + ((g.K + 1) & ~1)) * 2;
   const int a_rec = __builtin_amdgcn_readfirstlane((int)min(a_bytes, 0x7fffffffL));
   const int b_rec = __builtin_amdgcn_readfirstlane((int)min(b_bytes, 0x7fffffffL));
   t.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, a_rec, 0x00020000);
@@ -103,6 +99,26 @@ MK_DEV void v9_tile_setup(const GemmArgs& g, int tile, int w, int l, V9Tile& t) 
       t.voA[h][i] = v9_voffset<A_RED, M16>(m0, g.M, g.lda, h, w + 4 * i, l);
       t.voB[h][i] = v9_voffset<B_RED, M16>(n0, g.N, g.ldb, h, w + 4 * i, l);
     }
+}
+
+// element (z1, z2) of a batched operand.  (A function on purpose: as a call it stays beside the tile index until the
+// inliner has run, and hipcc then orders the set-up as it did before v9_operand_setup was split off:
+// profiles/v9_shared_tile_isa.txt)
+template <typename T>
+MK_DEV T* v9_batch_elem(T* p, long z1, long s1, long z2, long s2) {
+  return p + z1 * s1 + z2 * s2;
+}
+// mk_gemm's tile: the XCD-aware tile order, the batch element of blockIdx.z, the residual
+template <bool A_RED, bool B_RED>
+MK_DEV void v9_tile_setup(const GemmArgs& g, int tile, int w, int l, V9Tile& t) {
+  int tm, tn;
+  tile_from_index(xcd_remap(tile, g.dp_tiles), g.tiles_m, g.tiles_n, tm, tn, 8);
+  const int z = blockIdx.z, z1 = z / g.nb2, z2 = z - z1 * g.nb2;
+  const e16* A = v9_batch_elem(reinterpret_cast<const e16*>(g.A), z1, g.sA1, z2, g.sA2);
+  const e16* B = v9_batch_elem(reinterpret_cast<const e16*>(g.B), z1, g.sB1, z2, g.sB2);
+  t.C = v9_batch_elem(reinterpret_cast<e16*>(g.C), z1, g.sC1, z2, g.sC2);
+  t.Rp = g.R ? v9_batch_elem(reinterpret_cast<const e16*>(g.R), z1, g.sR1, z2, g.sR2) : nullptr;
+  v9_operand_setup<A_RED, B_RED, true>(g, A, B, tm * BM9, tn * BN9, w, l, t);
 }
 
 // the first LDS-DMA requests of a tile (as gemm_v8): tile 0 (A, B piece by piece), A(1), half 0 of B(1) -- 28 pieces
@@ -129,6 +145,51 @@ MK_DEV void v9_tile_request(const V9Tile& t, char* smem, int w, int stepA, int s
 #undef V9_DMA_A
 #undef V9_DMA_B
 }
+
+// ---- shared by gemm_bf16_v9_kernel and gemm_bf16_grp_kernel (#undef'd at the end of this file).
+// The K loop (it names the kernel's locals t, adA, adB, iA, iB, stepA, stepB, nk, wv): ONE asm statement around a generated text (scripts/gen_v9_loop.py: register map, placement rule and the
+// slot / wait protocol there) with that text's clobber list.
+#define V9_ASM(TEXT, CLOBBERS)                                                                    \
+  asm volatile(TEXT                                                                               \
+               :                                                                                  \
+               : [voA] "v"(t.voA[0][0]), [voB] "v"(t.voB[0][0]), [adA] "v"(adA), [adB] "v"(adB),   \
+                 [rsA] "s"(t.dA), [rsB] "s"(t.dB), [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA),   \
+                 [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)                                      \
+               : CLOBBERS)
+#if V9_MFMA16
+// Register epilogue of the 16 x 16 fragments: D[n = 4 (l >> 4) + e][m = l & 15] of fragment (i, j) -> a lane owns 4
+// consecutive columns of ONE row: row m0 + wm0 + 16 i + (l & 15), columns n0 + wn0 + 16 j + 4 (l >> 4) .. + 3 = one
+// 8-byte access per lane and fragment; CROW points at the lane's four columns of fragment (0, 0).
+// (MK_V9_NT_STORE: experiment build -- the C stores with the non-temporal hint, so that a round's 4 MiB of output per
+// XCD do not displace the operand panels from its L2; measured in profiles/r06_gemm_v9_nt_store.txt)
+#ifdef MK_V9_NT_STORE
+typedef unsigned int v9_u32x2 __attribute__((ext_vector_type(2)));
+#define V9_ST8(PTR, VAL) __builtin_nontemporal_store(__builtin_bit_cast(v9_u32x2, VAL), reinterpret_cast<v9_u32x2*>(PTR))
+#else
+#define V9_ST8(PTR, VAL) (*reinterpret_cast<e16x4*>(PTR) = (VAL))
+#endif
+#define V9_F16P(I, J, CROW, LDC, ALPHA)   /* alpha only */                                        \
+  do {                                                                                            \
+    float t_[4];                                                                                  \
+    V9_ACC16_READ_##I##_##J(t_);                                                                  \
+    e16x4 o_;                                                                                     \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * (ALPHA));           \
+    V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
+  } while (0)
+// (a scheduling fence per fragment row: without it hipcc hoists all 256 accumulator reads and spills)
+#define V9_R16(F, I, CROW, LDC, ALPHA)                                                            \
+  do {                                                                                            \
+    F(I, 0, CROW, LDC, ALPHA); F(I, 1, CROW, LDC, ALPHA); F(I, 2, CROW, LDC, ALPHA); F(I, 3, CROW, LDC, ALPHA); \
+    F(I, 4, CROW, LDC, ALPHA); F(I, 5, CROW, LDC, ALPHA); F(I, 6, CROW, LDC, ALPHA); F(I, 7, CROW, LDC, ALPHA); \
+    __builtin_amdgcn_sched_barrier(0);                                                            \
+  } while (0)
+#define V9_EPI16(F, CROW, LDC, ALPHA)                                                             \
+  do {                                                                                            \
+    V9_R16(F, 0, CROW, LDC, ALPHA); V9_R16(F, 1, CROW, LDC, ALPHA); V9_R16(F, 2, CROW, LDC, ALPHA); \
+    V9_R16(F, 3, CROW, LDC, ALPHA); V9_R16(F, 4, CROW, LDC, ALPHA); V9_R16(F, 5, CROW, LDC, ALPHA); \
+    V9_R16(F, 6, CROW, LDC, ALPHA); V9_R16(F, 7, CROW, LDC, ALPHA);                               \
+  } while (0)
+#endif
 
 // Whole tiles only (M % 256 == N % 256 == K % 64 == 0, K >= 128: the launcher checks): the asm derives every LDS-DMA
 // voffset from piece 0's by adding strides, which is the C++ formula without its edge clamp.
@@ -171,35 +232,21 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
   bool first = true;
   for (;;) {
     __builtin_amdgcn_sched_barrier(0);
-    // ---- the K loop: scripts/gen_v9_loop.py (register map, placement rule and the slot / wait protocol there)
-#define V9_LOOP(TEXT)                                                                             \
-  asm volatile(TEXT                                                                               \
-               :                                                                                  \
-               : [voA] "v"(t.voA[0][0]), [voB] "v"(t.voB[0][0]), [adA] "v"(adA), [adB] "v"(adB),   \
-                 [rsA] "s"(t.dA), [rsB] "s"(t.dB), [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA),   \
-                 [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)                                      \
-               : V9_LOOP_CLOBBERS)
+    // ---- the K loop
 #define V9_LOOPS(W)                                                                               \
   do {                                                                                            \
-    if constexpr (!A_RED && !B_RED) V9_LOOP(V9_LOOP_TEXT_00##W);                                  \
-    else if constexpr (!A_RED && B_RED) V9_LOOP(V9_LOOP_TEXT_01##W);                              \
-    else if constexpr (A_RED && !B_RED) V9_LOOP(V9_LOOP_TEXT_10##W);                              \
-    else V9_LOOP(V9_LOOP_TEXT_11##W);                                                             \
+    if constexpr (!A_RED && !B_RED) V9_ASM(V9_LOOP_TEXT_00##W, V9_LOOP_CLOBBERS);                 \
+    else if constexpr (!A_RED && B_RED) V9_ASM(V9_LOOP_TEXT_01##W, V9_LOOP_CLOBBERS);             \
+    else if constexpr (A_RED && !B_RED) V9_ASM(V9_LOOP_TEXT_10##W, V9_LOOP_CLOBBERS);             \
+    else V9_ASM(V9_LOOP_TEXT_11##W, V9_LOOP_CLOBBERS);                                            \
   } while (0)
 #if V9_MFMA16
-#define V9_LOOP16(TEXT)                                                                           \
-  asm volatile(TEXT                                                                               \
-               :                                                                                  \
-               : [voA] "v"(t.voA[0][0]), [voB] "v"(t.voB[0][0]), [adA] "v"(adA), [adB] "v"(adB),   \
-                 [rsA] "s"(t.dA), [rsB] "s"(t.dB), [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA),   \
-                 [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)                                      \
-               : V9_LOOP16_CLOBBERS)
 #define V9_LOOPS16(W)                                                                             \
   do {                                                                                            \
-    if constexpr (!A_RED && !B_RED) V9_LOOP16(V9_LOOP16_TEXT_00##W);                              \
-    else if constexpr (!A_RED && B_RED) V9_LOOP16(V9_LOOP16_TEXT_01##W);                          \
-    else if constexpr (A_RED && !B_RED) V9_LOOP16(V9_LOOP16_TEXT_10##W);                          \
-    else V9_LOOP16(V9_LOOP16_TEXT_11##W);                                                         \
+    if constexpr (!A_RED && !B_RED) V9_ASM(V9_LOOP16_TEXT_00##W, V9_LOOP16_CLOBBERS);             \
+    else if constexpr (!A_RED && B_RED) V9_ASM(V9_LOOP16_TEXT_01##W, V9_LOOP16_CLOBBERS);         \
+    else if constexpr (A_RED && !B_RED) V9_ASM(V9_LOOP16_TEXT_10##W, V9_LOOP16_CLOBBERS);         \
+    else V9_ASM(V9_LOOP16_TEXT_11##W, V9_LOOP16_CLOBBERS);                                        \
   } while (0)
     if constexpr (M16) {
       if (first) V9_LOOPS16();
@@ -211,7 +258,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
       else V9_LOOPS(_W);
     }
 #undef V9_LOOPS
-#undef V9_LOOP
+#undef V9_LOOPS16
     __builtin_amdgcn_sched_barrier(0);
 #ifdef MK_V9_NOEPI      // timing-only experiment builds (scripts/probe/build_v9_variants.sh): no epilogue
     return;
@@ -229,48 +276,23 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
     }
 #if V9_MFMA16
     if constexpr (M16) {
-      // register epilogue of the 16 x 16 fragments: D[n = 4 (l >> 4) + e][m = l & 15] of fragment (i, j) -> a lane owns 4
-      // consecutive columns of ONE row: row m0 + wm0 + 16 i + (l & 15), columns n0 + wn0 + 16 j + 4 (l >> 4) .. + 3 =
-      // one 8-byte access per lane and fragment.  Two forms: alpha only, and alpha + residual (o_proj / down_proj forward);
+      // the register epilogue (V9_EPI16 above) in two forms: alpha only, and alpha + residual (o_proj / down_proj forward);
       // bias / activation / accumulate never reach this kernel (pick_cfg).  (A form with run-time switches per fragment
       // made hipcc keep 64-bit addresses per fragment live: 270 spilled registers.)
       const float alpha = g.alpha;
       const int mrow = m0 + wm0 + (l & 15), ncol = n0 + wn0 + 4 * (l >> 4);
       e16* crow = C + (long)mrow * g.ldc + ncol;
       const e16* rrow = Rp ? Rp + (long)mrow * g.ldr + ncol : nullptr;
-      // (MK_V9_NT_STORE: experiment build -- the C stores with the non-temporal hint, so that a round's 4 MiB of output per
-      // XCD do not displace the operand panels from its L2; measured in profiles/r06_gemm_v9_nt_store.txt)
-#ifdef MK_V9_NT_STORE
-      typedef unsigned int v9_u32x2 __attribute__((ext_vector_type(2)));
-#define V9_ST8(PTR, VAL) __builtin_nontemporal_store(__builtin_bit_cast(v9_u32x2, VAL), reinterpret_cast<v9_u32x2*>(PTR))
-#else
-#define V9_ST8(PTR, VAL) (*reinterpret_cast<e16x4*>(PTR) = (VAL))
-#endif
-#define V9_F16P(I, J)   /* alpha only */                                                         \
+#define V9_F16R(I, J, CROW, LDC, ALPHA)   /* + residual (requested for the whole tile up front: rv_) */ \
   do {                                                                                            \
     float t_[4];                                                                                  \
     V9_ACC16_READ_##I##_##J(t_);                                                                  \
     e16x4 o_;                                                                                     \
-    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * alpha);             \
-    V9_ST8(crow + (long)(16 * (I)) * g.ldc + 16 * (J), o_);                                       \
-  } while (0)
-#define V9_F16R(I, J)   /* + residual (requested for the whole tile up front: rv_) */                   \
-  do {                                                                                            \
-    float t_[4];                                                                                  \
-    V9_ACC16_READ_##I##_##J(t_);                                                                  \
-    e16x4 o_;                                                                                     \
-    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * alpha + (float)rv_[I][J][e_]); \
-    V9_ST8(crow + (long)(16 * (I)) * g.ldc + 16 * (J), o_);                                       \
-  } while (0)
-      // (a scheduling fence per fragment row: without it hipcc hoists all 256 accumulator reads and spills)
-#define V9_R16(F, I)                                                                              \
-  do {                                                                                            \
-    F(I, 0); F(I, 1); F(I, 2); F(I, 3); F(I, 4); F(I, 5); F(I, 6); F(I, 7);                       \
-    __builtin_amdgcn_sched_barrier(0);                                                            \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * (ALPHA) + (float)rv_[I][J][e_]); \
+    V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
   } while (0)
       if (rrow == nullptr) {
-        V9_R16(V9_F16P, 0); V9_R16(V9_F16P, 1); V9_R16(V9_F16P, 2); V9_R16(V9_F16P, 3);
-        V9_R16(V9_F16P, 4); V9_R16(V9_F16P, 5); V9_R16(V9_F16P, 6); V9_R16(V9_F16P, 7);
+        V9_EPI16(V9_F16P, crow, g.ldc, alpha);
       } else {
         // all 64 residual fragments of the lane are requested before the first accumulator is read (128 registers: the
         // K loop's fragment registers are free now) -- one HBM round trip for the tile instead of one per fragment row
@@ -282,13 +304,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
           for (int j_ = 0; j_ < 8; ++j_)
             rv_[i_][j_] = *reinterpret_cast<const e16x4*>(rrow + (long)(16 * i_) * g.ldr + 16 * j_);
         __builtin_amdgcn_sched_barrier(0);
-        V9_R16(V9_F16R, 0); V9_R16(V9_F16R, 1); V9_R16(V9_F16R, 2); V9_R16(V9_F16R, 3);
-        V9_R16(V9_F16R, 4); V9_R16(V9_F16R, 5); V9_R16(V9_F16R, 6); V9_R16(V9_F16R, 7);
+        V9_EPI16(V9_F16R, crow, g.ldc, alpha);
       }
-#undef V9_R16
-#undef V9_F16P
 #undef V9_F16R
-#undef V9_ST8
     } else
 #endif
     if (plain) {
@@ -356,48 +374,24 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
 // gemm_bf16_v9_kernel's protocol with the problem looked up per tile: set-up, the first LDS-DMA requests, the generated
 // loop of the tile's layout, and the next tile's set-up and requests behind the barrier before this tile's epilogue --
 // also when the next tile has the other layout (the ring's slots and the wait protocol do not depend on the layout).
-// Every tile is computed by the instruction stream that gemm_bf16_v9_kernel runs on it.
-// gemm_bf16_v9_kernel itself stays as it is (its symbols, register budget and disassembly are pinned by tests), so two
-// pieces exist TWICE and must be kept in step by hand, since the bit-identity of the two paths rests on them:
-// grp_tile_setup restates v9_tile_setup (descriptor bounds, voffsets) for a GrpProb, and GRP_F16P restates V9_F16P
-// (alpha-only register epilogue, plain 8-byte stores: the MK_V9_NT_STORE experiment build does not reach this kernel).
-// v9_tile_request, v9_voffset, v9_read_offset16, the generated loops and the V9_ACC16_READ macros are shared.
-// tests/test_gemm_grouped_gpu.py compares the two paths bit for bit.
+// Every tile is computed by the instruction stream that gemm_bf16_v9_kernel runs on it, and by the same source: the
+// two kernels share v9_operand_setup (descriptor bounds and words, voffsets), v9_tile_request, v9_voffset,
+// v9_read_offset16, the generated loops inside V9_ASM and the alpha-only register epilogue V9_EPI16(V9_F16P) with its
+// V9_ACC16_READ macros and V9_ST8 (so the MK_V9_NT_STORE experiment build reaches this kernel as well).  Per kernel
+// remain: which tile comes next and whose it is (v9_tile_setup / grp_next + grp_tile_setup), the wave preamble, the
+// loop's scalars (here per tile: GRP_SETUP) and the choice of loop text.
+// tests/test_gemm_grouped_gpu.py compares the two paths bit for bit; scripts/kernel_isa_diff.py compares builds.
+//
+// a grouped tile: tile `lin` of problem p in plain order (grp_next has applied the XCD remap of the main problem); B is
+// reduction-major in both layouts, whole tiles by mk_gemm_grouped's domain check (no record clamp), no residual
 template <bool A_RED>
 MK_DEV void grp_tile_setup(const GrpProb& p, int lin, int w, int l, V9Tile& t) {
   int tm, tn;
   tile_from_index(lin, p.tiles_m, p.tiles_n, tm, tn, 8);
-  const e16* A = reinterpret_cast<const e16*>(p.A);
-  const e16* B = reinterpret_cast<const e16*>(p.B);
   t.C = reinterpret_cast<e16*>(p.C);
   t.Rp = nullptr;
-  const int m0 = tm * BM9, n0 = tn * BN9;
-  t.m0 = m0; t.n0 = n0;
-  const e16* abase = uniform_ptr(A_RED ? A + m0 : A + (long)m0 * p.lda);
-  const e16* bbase = uniform_ptr(B + n0);
-  const long a_bytes = A_RED ? ((long)(p.K - 1) * p.lda + ((p.M - m0 + 1) & ~1)) * 2
-                             : ((long)(BM9 - 1) * p.lda + ((p.K + 1) & ~1)) * 2;
-  const long b_bytes = ((long)(p.K - 1) * p.ldb + ((p.N - n0 + 1) & ~1)) * 2;
-  const int a_rec = __builtin_amdgcn_readfirstlane((int)min(a_bytes, 0x7fffffffL));
-  const int b_rec = __builtin_amdgcn_readfirstlane((int)min(b_bytes, 0x7fffffffL));
-  t.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, a_rec, 0x00020000);
-  t.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)bbase, 0, b_rec, 0x00020000);
-  const uint64_t pa = reinterpret_cast<uint64_t>(abase), pb = reinterpret_cast<uint64_t>(bbase);
-  t.dA[0] = __builtin_amdgcn_readfirstlane((uint32_t)pa);
-  t.dA[1] = __builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32) & 0xffffu);
-  t.dA[2] = (uint32_t)a_rec;
-  t.dA[3] = 0x00020000u;
-  t.dB[0] = __builtin_amdgcn_readfirstlane((uint32_t)pb);
-  t.dB[1] = __builtin_amdgcn_readfirstlane((uint32_t)(pb >> 32) & 0xffffu);
-  t.dB[2] = (uint32_t)b_rec;
-  t.dB[3] = 0x00020000u;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      t.voA[h][i] = v9_voffset<A_RED, true>(m0, p.M, p.lda, h, w + 4 * i, l);
-      t.voB[h][i] = v9_voffset<true, true>(n0, p.N, p.ldb, h, w + 4 * i, l);
-    }
+  v9_operand_setup<A_RED, true, false>(p, reinterpret_cast<const e16*>(p.A), reinterpret_cast<const e16*>(p.B), tm * BM9,
+                                       tn * BN9, w, l, t);
 }
 
 // The workgroup's work list (wave-uniform throughout): its main tiles b, b + n, ..., then its filler tiles.  Fillers are
@@ -477,21 +471,13 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_grp_kernel(GrpArgs g) {
   bool first = true;
   for (;;) {
     __builtin_amdgcn_sched_barrier(0);
-#define GRP_LOOP(TEXT)                                                                            \
-  asm volatile(TEXT                                                                               \
-               :                                                                                  \
-               : [voA] "v"(t.voA[0][0]), [voB] "v"(t.voB[0][0]), [adA] "v"(adA), [adB] "v"(adB),   \
-                 [rsA] "s"(t.dA), [rsB] "s"(t.dB), [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA),   \
-                 [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)                                      \
-               : V9_LOOP16_CLOBBERS)
     if (HAS_MAIN && !a_red) {
-      if (first) GRP_LOOP(V9_LOOP16_TEXT_01);
-      else GRP_LOOP(V9_LOOP16_TEXT_01_W);
+      if (first) V9_ASM(V9_LOOP16_TEXT_01, V9_LOOP16_CLOBBERS);
+      else V9_ASM(V9_LOOP16_TEXT_01_W, V9_LOOP16_CLOBBERS);
     } else {
-      if (first) GRP_LOOP(V9_LOOP16_TEXT_11);
-      else GRP_LOOP(V9_LOOP16_TEXT_11_W);
+      if (first) V9_ASM(V9_LOOP16_TEXT_11, V9_LOOP16_CLOBBERS);
+      else V9_ASM(V9_LOOP16_TEXT_11_W, V9_LOOP16_CLOBBERS);
     }
-#undef GRP_LOOP
     __builtin_amdgcn_sched_barrier(0);
     // this tile's output position, then the next tile: its requests go out BEFORE the epilogue
     const int m0 = t.m0, n0 = t.n0;
@@ -504,25 +490,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_grp_kernel(GrpArgs g) {
       __builtin_amdgcn_s_barrier();            // every wave has read its last fragments: the ring may be refilled
       v9_tile_request(t, smem, w, stepA, stepB);
     }
-    // the register epilogue of the 16 x 16 fragments, alpha only (as gemm_bf16_v9_kernel's V9_F16P)
+    // the register epilogue, alpha only
     e16* crow = C + (long)(m0 + wm0 + (l & 15)) * ldc + n0 + wn0 + 4 * (l >> 4);
-#define GRP_F16P(I, J)                                                                            \
-  do {                                                                                            \
-    float t_[4];                                                                                  \
-    V9_ACC16_READ_##I##_##J(t_);                                                                  \
-    e16x4 o_;                                                                                     \
-    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * alpha);             \
-    *reinterpret_cast<e16x4*>(crow + (long)(16 * (I)) * ldc + 16 * (J)) = o_;                     \
-  } while (0)
-#define GRP_R16(I)                                                                                \
-  do {                                                                                            \
-    GRP_F16P(I, 0); GRP_F16P(I, 1); GRP_F16P(I, 2); GRP_F16P(I, 3);                               \
-    GRP_F16P(I, 4); GRP_F16P(I, 5); GRP_F16P(I, 6); GRP_F16P(I, 7);                               \
-    __builtin_amdgcn_sched_barrier(0);                                                            \
-  } while (0)
-    GRP_R16(0); GRP_R16(1); GRP_R16(2); GRP_R16(3); GRP_R16(4); GRP_R16(5); GRP_R16(6); GRP_R16(7);
-#undef GRP_R16
-#undef GRP_F16P
+    V9_EPI16(V9_F16P, crow, ldc, alpha);
     if (!more) break;
     first = false;
   }
@@ -559,3 +529,10 @@ int launch_v9(const GemmArgs& g, dim3 grid, hipStream_t st) {
 }
 }  // namespace MK_E16_NS
 }  // namespace
+#undef V9_ASM
+#if V9_MFMA16
+#undef V9_EPI16
+#undef V9_R16
+#undef V9_F16P
+#undef V9_ST8
+#endif

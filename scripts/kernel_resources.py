@@ -7,6 +7,7 @@ bundles, each holding one code object per target; its AMDGPU metadata note lists
 tests/test_kernel_resources_cpu.py pins the occupancy-relevant budgets with this (a run-time branch
 added to the GEMM epilogue in round 3 cost every 128x128 kernel its fourth wave per SIMD -- 125 -> 136
 VGPRs, -12 ... -24 % on the shapes that use it -- and nothing but a profile showed it)."""
+import collections
 import os
 import re
 import struct
@@ -89,6 +90,28 @@ def disassemble(substr, lib=LIB):
                 elif cur and line.strip():
                     out[cur].append(line.split("//")[0].strip())
     return out
+
+
+def agpr_uses(sym, lines, mfma):
+    """(opcode counter, reads per AGPR) over the instructions of one disassembled kernel that name an AGPR.  A hand-placed
+    GEMM keeps its accumulators in a0..a255 ACROSS asm statements, declared only as clobbers, so nothing the compiler emits
+    may touch them: asserts that `v_accvgpr_write_b32` only zeroes (never a value from a VGPR), that `v_accvgpr_read_b32`
+    is the only reader, and that every other instruction with an AGPR operand is an MFMA whose mnemonic starts with one
+    of `mfma` (no ds_read / buffer_load / v_mov into an AGPR)."""
+    areg = re.compile(r"\ba(\d+)\b|\ba\[(\d+):(\d+)\]")
+    ops, reads = collections.Counter(), collections.Counter()
+    for ins in lines:
+        if not areg.search(ins):
+            continue
+        op = ins.split()[0]
+        ops[op] += 1
+        if op == "v_accvgpr_write_b32":
+            assert re.search(r"\ba\d+, 0$", ins), (sym, ins)
+        elif op == "v_accvgpr_read_b32":
+            reads[int(areg.search(ins).group(1))] += 1
+        else:
+            assert op.startswith(tuple(mfma)), (sym, ins)
+    return ops, reads
 
 
 if __name__ == "__main__":

@@ -2,9 +2,7 @@
 tests/test_kernel_resources_cpu.py does for gemm_v9: the generated K loop owns a[0:255] across asm statements, so the kernel
 must keep all 256 AGPRs, spill nothing, use no scratch, run one wave per SIMD (workgroup size 256) -- and no compiler-made
 instruction may touch an AGPR between the loop and the epilogue's reads."""
-import collections
 import os
-import re
 import sys
 
 import pytest
@@ -41,20 +39,8 @@ def test_256_agprs_no_spill_no_scratch_one_wave_per_simd(ks):
 def test_only_mfmas_zeroing_writes_and_the_epilogue_reads_touch_an_agpr():
     dis = kr.disassemble("grp_kernel")
     assert len(dis) == 4
-    areg = re.compile(r"\ba(\d+)\b|\ba\[(\d+):(\d+)\]")
     for sym, lines in dis.items():
         loops = 4 if "Lb1E" in sym else 2          # <true>: the first / walking loop of both layouts; <false>: of one
-        ops, reads = collections.Counter(), collections.Counter()
-        for ins in lines:
-            if not areg.search(ins):
-                continue
-            op = ins.split()[0]
-            ops[op] += 1
-            if op == "v_accvgpr_write_b32":
-                assert re.search(r"\ba\d+, 0$", ins), (sym, ins)          # zeroing only, never a value from a VGPR
-            elif op == "v_accvgpr_read_b32":
-                reads[int(areg.search(ins).group(1))] += 1
-            else:
-                assert op.startswith("v_mfma_f32_16x16x32_"), (sym, ins)  # no ds_read / buffer_load / v_mov into an AGPR
+        ops, reads = kr.agpr_uses(sym, lines, ("v_mfma_f32_16x16x32_",))
         assert ops["v_accvgpr_write_b32"] == 256 * loops, (sym, dict(ops))
         assert sorted(reads) == list(range(256)) and set(reads.values()) == {1}, sym      # ONE epilogue form
