@@ -36,7 +36,7 @@ extern "C" {
 #define MK_FP8 3 /* OCP e4m3fn bytes: mk_gemm operands / mk_fp8_quantize output only */
 
 /* library identification: returns MK_ABI_VERSION */
-#define MK_ABI_VERSION 10
+#define MK_ABI_VERSION 11
 int mk_abi_version(void);
 
 /* ------------------------------------------------------------------ GEMM --
@@ -504,6 +504,72 @@ int mk_kv_append_rows(const void* k, const void* v, int64_t ld, int64_t in_bs, v
 int mk_kv_quant_append_rows(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,
                             const int32_t* slot, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd,
                             int32_t dtype, void* stream);
+/* Beam search (generate(num_beams=K)): classic HF BeamSearchScorer semantics, written down here; restated in pure
+ *   numpy in tests/beam_ref.py, to which the kernels are pinned.
+ *
+ * Per-sample state: K running beams with scores s_k (fp32 sums of log-probabilities), a pool of at most K finished
+ *   hypotheses, and a done flag.  The length L used for the penalty counts generated tokens only, the eos included.
+ *
+ * One step, for a sample that is not done.  K_in rows of logits: 1 for the first token (from the prefill), K afterwards.
+ *   L is the output column + 1.
+ *   1. cand(k, c) = s_k + (x_kc - lse_k) in fp32.  A NaN or -inf logit gives cand = -inf and is never selected.
+ *   2. Take the 2K best candidates by value descending.  Ties go to the lower flat index k * V + c.  The selection is
+ *      exact (the radix select of mk_sample_rows).
+ *   3. Walk them in rank order r = 0, 1, ...
+ *        column == eos and r < K:  insert into the pool with score cand / L^length_penalty.
+ *        column == eos and r >= K: skip.
+ *        any other column: it becomes the next running beam j = 0, 1, ... with parent k, token c and s_j = cand.
+ *      Stop when K running beams are filled.  A beam that cannot be filled because no finite candidate is left gets
+ *      s = -inf, token pad and parent 0.
+ *   4. Pool insert: append while fewer than K entries; otherwise replace the worst entry if the new score is strictly
+ *      greater; among equal worst scores, replace the latest inserted.
+ *   5. Done.  early_stopping != 0: the pool holds K.  early_stopping == 0: the pool holds K and
+ *      s_0 / L^length_penalty <= worst pool score, s_0 the best running beam after this step.
+ *   6. A sample that was already done changes nothing in its books.  Its rows are fed pad.
+ *   7. eos < 0 never matches (eos_token_id=None).
+ * After the last step (on the host): for every sample not done, each running beam with a finite score enters the pool
+ *   in beam order with s_k / L^length_penalty.
+ * Result: per sample, the pool sorted by score descending, ties to the earlier insertion, first num_return_sequences
+ *   entries.  Sequences are recovered by backtracking the per-step (token, parent) history, which is kept on the device
+ *   and never overwritten; a pool entry needs only (score, step, parent beam).
+ *
+ * State layout (all on the device; B samples, K beams, n_max = the most output columns):
+ *   tok        int64 [B * K]             the token each (sample, beam) row is fed next
+ *   scores     f32   [B * K]             s_k; before the first step s_0 = 0 (rows k >= K_in are not read)
+ *   hist       int32 [n_max][B][K][2]    (token, parent beam) of beam j at output column i
+ *   ind        int32 [B * K][n_max]      the indirection table: the cache slot of sample b that holds the key of
+ *                                        position S0 + i for row (b, k).  Zero it before the first step.
+ *   pool_score f32   [B][K]              scores of the finished hypotheses
+ *   pool_info  int32 [B][K + 1][4]       per entry (output column of its eos, parent beam, insertion number, 0);
+ *                                        row K = (entries, next insertion number, 0, 0).  Zero it before the first step.
+ *   done       one byte per sample;  state: int32 [>= 3] = (position, output column, arrival counter) as mk_decode_emit.
+ *
+ * mk_beam_emit: that step for every sample, one workgroup per sample, at output column col = state[1]: writes tok,
+ *   scores, hist[col], the pool and done; updates ind IN PLACE -- new row j = old row parent[j] over columns 0 ... col - 1
+ *   (each column permuted by one thread that reads its K entries before it writes any: columns are independent, so no
+ *   second table and no step parity), plus ind[j][col] = j for the token about to be fed.  A done sample writes tok =
+ *   pad, hist[col] = (pad, j) and ind[j][col] = j only.  The last workgroup to arrive advances state[0] and state[1]
+ *   and leaves state[2] zero, exactly as mk_decode_emit.  A column outside [0, n_max) writes neither hist nor ind.
+ *   Logits bf16 / f16 / f32 [B * K_in][V] at pitch ld >= V, sample b's rows b * K_in ... b * K_in + K_in - 1.
+ *   MK_ERR_BAD_ARG: null pointers, B <= 0, K outside [1, 16], K_in not in {1, K}, V < 2K, ld < V, n_max <= 0.
+ *   V <= 2^23, else MK_ERR_UNSUPPORTED.
+ * mk_decode_step_attn_beam: mk_decode_step_attn for row (b, k) of a [B][K][t_max][2D] cache (kv_bs = the stride of one
+ *   SLOT; row r = b * K + k of q / k_new / v_new / o).  RoPE, append, attention and rounding points are unchanged.  Key
+ *   t < S0 is read from slot 0 of sample b (the prompt is stored once per sample and the prefill runs at batch B);
+ *   key S0 <= t < p from slot ind[r][t - S0] (clamped into [0, K)); key p comes from the registers and is appended to
+ *   row p of the row's own slot k.  No cache row is ever copied.  Everything after the address of a key is
+ *   mk_decode_step_attn's code: a row's output is bit-identical to the plain entry point's on a physically gathered
+ *   cache with B * K samples (the same kernel selection on B * K * H).  Domain of mk_decode_step_attn; MK_ERR_BAD_ARG
+ *   also for ind null, K outside [1, 16], S0 outside [0, t_max], n_ind < max(t_max - S0, 1). */
+int mk_beam_emit(const void* logits, int64_t ld, int32_t V, int32_t B, int32_t K, int32_t K_in, int64_t pad,
+                 int64_t eos, float length_penalty, int32_t early_stopping, int64_t* tok, float* scores,
+                 int32_t* hist, int32_t* ind, int32_t n_max, float* pool_score, int32_t* pool_info, void* done,
+                 int32_t* state, int32_t dtype, void* stream);
+int mk_decode_step_attn_beam(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                             const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                             int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
+                             const int32_t* ind, int32_t n_ind, int32_t S0, int32_t t_max, int32_t B, int32_t K,
+                             int32_t H, int32_t hd, float scale, int32_t dtype, void* stream);
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);

@@ -9,6 +9,8 @@
 //   mk_kv_quant_append / mk_decode_step_attn_kv8  the prefill's cache write and the step's attention block over an
 //                   e4m3 KV cache (bytes + one fp32 scale per head and position: decode_kv8_impl.inc)
 //   mk_decode_step_attn_var / mk_decode_step_attn_kv8_var  the same steps at a position PER SAMPLE, *t_dev + t_off[b]
+//   mk_decode_step_attn_beam  the 16-bit step for (sample, beam) rows over a [B][K][t_max][2D] cache read through a beam
+//                   indirection table: the prompt's keys once per sample, no cache row ever copied (beam.hip: the emit)
 //   mk_kv_append_rows / mk_kv_quant_append_rows  the prefill's cache write of a padded batch: source row j of sample
 //                   b goes to cache row slot[b][j], masked rows (slot < 0) are not written (a compacted, ragged cache)
 //
@@ -141,6 +143,15 @@ extern "C" int mk_decode_step_attn_var(const void* q, const void* k_new, const v
   if (reinterpret_cast<uintptr_t>(t_off) & 3) return MK_ERR_UNSUPPORTED;
   if (dtype == MK_F16) return e_f16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream, true, t_off);
   return e_bf16::decode_step_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, t_max, B, H, hd, scale, dtype, stream, true, t_off);
+}
+
+extern "C" int mk_decode_step_attn_beam(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                                        const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                        int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
+                                        const int32_t* ind, int32_t n_ind, int32_t S0, int32_t t_max, int32_t B,
+                                        int32_t K, int32_t H, int32_t hd, float scale, int32_t dtype, void* stream) {
+  if (dtype == MK_F16) return e_f16::decode_step_attn_beam_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, ind, n_ind, S0, t_max, B, K, H, hd, scale, dtype, stream);
+  return e_bf16::decode_step_attn_beam_impl(q, k_new, v_new, in_bs, cos_t, sin_t, k_cache, v_cache, kv_ld, kv_bs, o, o_bs, t_dev, ind, n_ind, S0, t_max, B, K, H, hd, scale, dtype, stream);
 }
 
 extern "C" int mk_decode_step_attn_kv8_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,

@@ -118,12 +118,35 @@ struct DecodeStepArgs {
   const int32_t* t_off;                                     // VAR kernels only: [B] per-sample offsets to *t_dev
 };
 
+// BEAM kernels only (mk_decode_step_attn_beam): the launch's rows are (sample, beam) pairs of a [B][K][t_max][2D] cache
+struct DecodeStepBeamArgs : DecodeStepArgs {
+  const int32_t* ind;                                       // [B * K][n_ind]: slot that holds key S0 + i of a row
+  int K, S0, n_ind;
+};
+template <bool BEAM> struct StepArgsOf { typedef DecodeStepArgs type; };
+template <> struct StepArgsOf<true> { typedef DecodeStepBeamArgs type; };
+
 MK_DEV float rnd_e16(float x) { return rnd<e16>(x); }
+
+// BEAM: the element offset from a row's OWN cache slot to the slot that holds its key t -- slot 0 of the sample for the
+// shared prompt (t < S0), slot ind[row][t - S0] behind it (clamped into [0, K): an address, whatever the table holds).
+// Everything after the address of a key is the plain kernel's code, so a row's arithmetic is that of the plain kernel
+// on a physically gathered cache.
+template <bool BEAM, typename A>
+MK_DEV long beam_slot_off(const A& a, int row, int t) {
+  if constexpr (BEAM) {
+    int s = 0;
+    if (t >= a.S0) s = min(max(a.ind[(long)row * a.n_ind + (t - a.S0)], 0), a.K - 1);
+    return (long)(s - row % a.K) * a.kv_bs;
+  } else {
+    return 0;
+  }
+}
 
 // VAR (mk_decode_step_attn_var): p = clamp(*t_dev + t_off[b]) per sample, a padded batch's ragged cache; everything
 // after p is the same code, so a sample's arithmetic is that of the plain kernel at *t_dev = p.
-template <int HD, int NWV, bool VAR = false>
-__global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(DecodeStepArgs a) {
+template <int HD, int NWV, bool VAR = false, bool BEAM = false>
+__global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(typename StepArgsOf<BEAM>::type a) {
   constexpr int LPK = HD / 8, KPW = 64 / LPK, KPP = NWV * KPW;
   __shared__ float red[NWV][HD];
   __shared__ float redw[2 * NWV];
@@ -179,8 +202,9 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(DecodeStepAr
     for (int j = 0; j < NB; ++j) {
       const int t = t0 + j * KPP;
       if (t < p) {
-        kv[j] = *reinterpret_cast<const e16x8*>(K + (long)t * a.kv_ld);
-        vv[j] = *reinterpret_cast<const e16x8*>(V + (long)t * a.kv_ld);
+        const long so = beam_slot_off<BEAM>(a, b, t);
+        kv[j] = *reinterpret_cast<const e16x8*>(K + so + (long)t * a.kv_ld);
+        vv[j] = *reinterpret_cast<const e16x8*>(V + so + (long)t * a.kv_ld);
       } else {
         vv[j] = vnew;
       }
@@ -267,8 +291,8 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(DecodeStepAr
 // (lanes 16 g ... 16 g + 15 <-> head 4 x + g), the eight waves take keys t = wave, wave + 8, ..., eight keys per
 // lane in flight (64 keys per trip), and the grid is B x H / 4 = 256 workgroups at B = 32: one per CU, one round.
 // Partial results meet in LDS per head (8 waves x 4 heads).  hd = 128 only.
-template <int NWV, bool VAR = false>
-__global__ __launch_bounds__(NWV * 64) void decode_step_attn4_kernel(DecodeStepArgs a) {
+template <int NWV, bool VAR = false, bool BEAM = false>
+__global__ __launch_bounds__(NWV * 64) void decode_step_attn4_kernel(typename StepArgsOf<BEAM>::type a) {
   constexpr int HD = 128, LPK = 16, HG = 4;
   __shared__ float red[NWV][HG * HD];
   __shared__ float redm[NWV][HG], reds[NWV][HG];
@@ -320,8 +344,9 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn4_kernel(DecodeStepA
 #pragma unroll
     for (int j = 0; j < NB; ++j) {       // unconditional loads from a clamped row (no branch around a load)
       const int tc = min(t0 + j * NWV, max(p - 1, 0));
-      kv[j] = *reinterpret_cast<const e16x8*>(K + (long)tc * a.kv_ld);
-      vv[j] = *reinterpret_cast<const e16x8*>(V + (long)tc * a.kv_ld);
+      const long so = beam_slot_off<BEAM>(a, b, tc);
+      kv[j] = *reinterpret_cast<const e16x8*>(K + so + (long)tc * a.kv_ld);
+      vv[j] = *reinterpret_cast<const e16x8*>(V + so + (long)tc * a.kv_ld);
     }
     float sj[NB], mt = m_run;
 #pragma unroll
@@ -413,6 +438,42 @@ int decode_step_attn_impl(const void* q, const void* k_new, const void* v_new, i
   else if (hd == 64) MK_LAUNCH((decode_step_attn_kernel<64, 8>), grid, block, lds, st, a);
   else if (hd == 32) MK_LAUNCH((decode_step_attn_kernel<32, 8>), grid, block, lds, st, a);
   else MK_LAUNCH((decode_step_attn_kernel<16, 8>), grid, block, lds, st, a);
+  return mk_check_launch();
+}
+
+// mk_decode_step_attn_beam: the plain entry point's checks and kernel selection over B * K rows, plus the table
+int decode_step_attn_beam_impl(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                               const void* sin_t, void* k_cache, void* v_cache, int64_t kv_ld, int64_t kv_bs, void* o,
+                               int64_t o_bs, const int32_t* t_dev, const int32_t* ind, int32_t n_ind, int32_t S0,
+                               int32_t t_max, int32_t B, int32_t K, int32_t H, int32_t hd, float scale, int32_t dtype,
+                               void* stream) {
+  if (!q || !k_new || !v_new || !cos_t || !sin_t || !k_cache || !v_cache || !o || !t_dev || !ind || B <= 0 || H <= 0 ||
+      t_max <= 0 || K < 1 || K > 16 || S0 < 0 || S0 > t_max || n_ind < 1 || n_ind < t_max - S0)
+    return MK_ERR_BAD_ARG;
+  if (dtype != E16<e16>::dtype || (hd != 16 && hd != 32 && hd != 64 && hd != 128)) return MK_ERR_UNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_new) |
+                       reinterpret_cast<uintptr_t>(v_new) | reinterpret_cast<uintptr_t>(cos_t) |
+                       reinterpret_cast<uintptr_t>(sin_t) | reinterpret_cast<uintptr_t>(k_cache) |
+                       reinterpret_cast<uintptr_t>(v_cache);
+  if ((al & 15) || (reinterpret_cast<uintptr_t>(ind) & 3) || (in_bs % 8) || (kv_ld % 8) || (kv_bs % 8))
+    return MK_ERR_UNSUPPORTED;
+  DecodeStepBeamArgs a;
+  a.q = (const e16*)q; a.kn = (const e16*)k_new; a.vn = (const e16*)v_new; a.in_bs = in_bs;
+  a.cos_t = (const e16*)cos_t; a.sin_t = (const e16*)sin_t;
+  a.kc = (e16*)k_cache; a.vc = (e16*)v_cache; a.kv_ld = kv_ld; a.kv_bs = kv_bs;
+  a.o = (e16*)o; a.o_bs = o_bs;
+  a.t_dev = t_dev; a.t_max = t_max; a.scale = scale; a.t_off = nullptr;
+  a.ind = ind; a.K = K; a.S0 = S0; a.n_ind = n_ind;
+  const int R = B * K;
+  dim3 grid(H, R), block(512);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  static const bool no4 = getenv("MK_DECODE_ATTN_NO4") != nullptr;
+  if (hd == 128 && (H % 4) == 0 && (long)R * H >= 512 && !no4)
+    MK_LAUNCH((decode_step_attn4_kernel<8, false, true>), dim3(H / 4, R), block, 0, st, a);
+  else if (hd == 128) MK_LAUNCH((decode_step_attn_kernel<128, 8, false, true>), grid, block, 0, st, a);
+  else if (hd == 64) MK_LAUNCH((decode_step_attn_kernel<64, 8, false, true>), grid, block, 0, st, a);
+  else if (hd == 32) MK_LAUNCH((decode_step_attn_kernel<32, 8, false, true>), grid, block, 0, st, a);
+  else MK_LAUNCH((decode_step_attn_kernel<16, 8, false, true>), grid, block, 0, st, a);
   return mk_check_launch();
 }
 

@@ -632,6 +632,14 @@ class Ragged(NamedTuple):
     t_off: torch.Tensor      # int32 [B]: n_b - S0; the step of sample b runs at position / cache row *t_dev + t_off[b]
 
 
+class Beam(NamedTuple):
+    """a beam step for llama_layer_cached (generate(num_beams=K)): the rows are (sample, beam) pairs and the cache is
+    [B, K, Tmax, 2D], read through the indirection table that ops.beam_emit keeps"""
+    ind: torch.Tensor        # int32 [B * K, n]: the slot of sample b that holds the key of position S0 + i for row (b, k)
+    K: int                   # beams per sample
+    S0: int                  # prompt length: keys below it are read from slot 0 of the sample
+
+
 def ragged_from_mask(mask, B, S0):
     """The host side of generate(attention_mask=): mask [B, S0], any integer or bool dtype, non-zero = valid.
     Returns None for a mask without a zero (the unpadded path), else (Ragged, pos, last):
@@ -657,9 +665,13 @@ def ragged_from_mask(mask, B, S0):
     return rg, pos.to(torch.int32).reshape(-1).contiguous(), last.contiguous()
 
 
-def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged=None, **off):
+def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged=None, beam=None, **off):
     """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
-    e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8; with ragged (a padded batch) their per-sample-position forms"""
+    e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8; with ragged (a padded batch) their per-sample-position forms;
+    with beam (a Beam; B samples of beam.K rows each) ops.decode_step_attn_beam over the [B, K, Tmax, 2D] cache"""
+    if beam is not None:
+        return ops.decode_step_attn_beam(q, k, v, in_bs, cos, sin, kvc, t_dev, beam.ind, beam.S0, Tmax, B, beam.K, H, hd,
+                                         att, scale, **off)
     if ragged is not None:
         if kv8 is not None:
             return ops.decode_step_attn_kv8_var(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, ragged.t_off, Tmax, B, H, hd,
@@ -697,7 +709,7 @@ def _stream_linear(x, W, q8, pro, w_ln, eps, residual, FF):
 
 
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
-                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None, ragged=None):
+                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None, ragged=None, beam=None):
     """No-grad decoder layer over `Sn` NEW positions per sample (rows of x2 are (b, s)) that
     start at position t0, with a preallocated KV cache kvc [B, Tmax, 2D] = [keys | values] per
     position (post-RoPE keys, modeling.py:183-195 semantics without the torch.cat per step).
@@ -728,9 +740,18 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     ops.kv_append_rows / ops.kv_quant_append_rows: the valid token at position i of a sample goes to cache row i,
     masked rows are not written.  Every decode step (t_dev) runs the per-sample-position step attention at
     *t_dev + ragged.t_off[b] and never reads past that row, so the cache's unwritten tail may stay uninitialised.
-    There is no masked attention over a cache: anything else (t0 > 0 without t_dev) raises ValueError."""
+    There is no masked attention over a cache: anything else (t0 > 0 without t_dev) raises ValueError.
+
+    beam (a Beam; decode steps with t_dev only): a beam-search step.  B stays the number of SAMPLES, x2 holds the
+    B * beam.K (sample, beam) rows and kvc is [B, K, Tmax, 2D]; the step attention reads it through beam.ind
+    (ops.decode_step_attn_beam), every other launch sees B * K token rows and is unchanged.  The prefill of such a
+    cache is a plain call at B rows on kvc.view(B, K * Tmax, 2D) with Tmax = K * Tmax: it writes slot 0 of every
+    sample.  Not with kv8 or ragged."""
     M, D = x2.shape
     dyn = t_dev is not None
+    if beam is not None and (not dyn or kv8 is not None or ragged is not None or M != B * beam.K):
+        raise ValueError("llama_layer_cached: beam takes single-position decode steps (t_dev) of B * K rows on the 16-bit "
+                         "unpadded cache, not kv8 or ragged")
     if ragged is not None and not dyn and t0 != 0:
         raise ValueError("llama_layer_cached: ragged takes a prefill from position 0 (t0 = 0) or single-position "
                          f"decode steps (t_dev), not {Sn} new positions at t0 = {t0}")
@@ -753,7 +774,7 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         # without w8; under the gate above that matters only for a non-contiguous wo, which takes ops.linear_fwd.
         q_qkv, q_o, q_gu, q_d = w8 if w8 is not None else (None,) * 4
         qkv = _stream_linear(x2, wqkv, q_qkv, 1, ln1, eps, None, FF)
-        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, k_off=D,
+        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, k_off=D,
                    v_off=2 * D)
         h1 = _stream_linear(att, wo, q_o, 0, None, eps, x2, FF)
         gu = _stream_linear(h1, wgu, q_gu, 1, ln2, eps, None, FF)
@@ -774,7 +795,7 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         new, off = (q, k, v), {}
         ropes, appends = ((q, H), (k, H)), ((k, D, 0, 0), (v, D, 0, D))
     if dyn:     # RoPE + cache append + attention of the new position: one launch
-        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, **off)
+        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, **off)
     else:
         for t, heads in ropes:
             ops.rope_(t, cos, sin, pos, heads, hd)

@@ -19,7 +19,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "libmacaw_hip.so"
 
 MK_F32, MK_BF16, MK_F16, MK_FP8 = 0, 1, 2, 3
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _ERR = {-1: "MK_ERR_BAD_ARG", -2: "MK_ERR_UNSUPPORTED", -3: "MK_ERR_LAUNCH"}
 
@@ -126,6 +126,10 @@ SIGNATURES = {
                                 _i32, _i32, _f32, _i32, _vp],
     "mk_decode_step_attn_kv8_var": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32,
                                     _i32, _f32, _i32, _vp],
+    "mk_beam_emit": [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                     _vp, _i32, _vp],
+    "mk_decode_step_attn_beam": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32,
+                                 _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "mk_kv_append_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mk_kv_quant_append_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mk_adamw_bias_correction": [_f32, _f32, _i32, _vp],

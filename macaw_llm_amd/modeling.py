@@ -59,8 +59,13 @@ DECODE_WEIGHTS = [None]
 KV_CACHE = [None]
 # MM_LLMs.set_sampling: the sampling arguments MM_LLMs.forward hands to generate()
 SAMPLING = [dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None)]
+# MM_LLMs.set_beam_search: the beam arguments MM_LLMs.forward hands to generate()
+BEAM_SEARCH = [dict(num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1)]
 # MM_LLMs.set_generate_mask: whether MM_LLMs.forward hands its extended attention mask to generate()
 GENERATE_MASK = [False]
+
+
+from .beam import beam_check, beam_result  # noqa: E402
 
 
 def _sampling_check(where, temperature, top_k, top_p):
@@ -524,8 +529,52 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
         return res.clone()
 
+    @torch.no_grad()
+    def _generate_beam(self, run, logits, last, emb_w, B, K, S0, max_new_tokens, eos, pad, dev, length_penalty,
+                       early_stopping, graph):
+        """The beam-search decode loop (_generate_graph's, with ops.beam_emit in place of ops.decode_emit and the step's
+        B * K rows attending through the indirection table): token 0 from the prefill's B rows (K_in = 1), then one step
+        per token -- embedding of the K tokens per sample, the layers with engine.Beam, the lm_head, the emit.  graph:
+        the step is captured once after one eager step and replayed, the host looking at the done flags every 8 tokens;
+        otherwise the same launches run kernel by kernel and the host looks after every token.  Returns the device
+        books and the step state for generate's beam_out."""
+        state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
+        t_dev = state[:1]
+        bs = ops.BeamState(B, K, max_new_tokens, pad, dev)
+        beam = eng.Beam(bs.ind, K, S0)
+        V = self.lm_head.weight.shape[0]
+
+        def emit(h_last, K_in):
+            ops.beam_emit(logits(h_last), V, K_in, pad, eos, length_penalty, early_stopping, bs, state)
+
+        def step():
+            emit(run(ops.embedding_fwd(emb_w, bs.tok), 1, 0, pos=t_dev, t_dev=t_dev, beam=beam), K)
+
+        emit(last, 1)                    # token 0 (from the prefill) ...
+        state[0] = S0                    # ... is the one fed at position S0
+        emitted = 1
+        if not graph or max_new_tokens <= 2:     # no decode step would be captured
+            while emitted < max_new_tokens and not bool(bs.done.all()):
+                step()
+                emitted += 1
+            return bs, state
+        if not bool(bs.done.all()):
+            step()                       # token 1: eager (kernel attributes, allocator pools, workspace)
+            emitted += 1
+        remaining = max_new_tokens - emitted
+        if remaining > 0 and not bool(bs.done.all()):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                step()
+            for i in range(remaining):
+                g.replay()
+                if (i & 7) == 7 and bool(bs.done.all()):
+                    break
+            del g
+        return bs, state
+
     def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="decode_weights",
-                          value="fp8"):
+                          value="fp8", beams=1):
         """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
         what keeps a call off that path instead of decoding it in 16 bits.  The limit of 32 sequences belongs to the
         weight-streaming step (switch="decode_weights", value "fp8" or "mxfp4"); the e4m3 cache takes any batch."""
@@ -543,6 +592,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             why = "MACAW_NO_DECODE_GRAPH selects the eager decode loop"
         elif max_new_tokens <= 2:
             why = f"max_new_tokens={max_new_tokens} <= 2: no decode step is captured"
+        elif B * beams > 32 and switch == "decode_weights" and beams > 1:
+            why = (f"B x num_beams = {B} x {beams} = {B * beams} rows: the weight-streaming decode step takes at most 32 "
+                   "(B * K <= 32)")
         elif B > 32 and switch == "decode_weights":
             why = f"{B} sequences: the weight-streaming decode step takes at most 32"
         elif not ops.decode_attn_ok(dtype, hd, S0 + max_new_tokens):
@@ -555,7 +607,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
                  kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None,
-                 attention_mask=None, **_):
+                 attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
+                 return_beam_scores=False, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -625,7 +678,27 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         ops.decode_attn_ok, raise ValueError (there is no masked attention over a cache) -- use use_cache=False, which
         recomputes the prefix with the growing mask and works for every dtype.  A sample without a valid token and a
         mask of another shape raise ValueError.  None (default) or a mask without a zero: the unpadded path, not one
-        launch different."""
+        launch different.
+
+        num_beams=K > 1: beam search with classic HF BeamSearchScorer semantics (the rule is written down in
+        include/macaw_hip.h and restated in tests/beam_ref.py): K running beams per sample scored by their summed
+        log-probabilities, a pool of K finished hypotheses scored sum / L ** length_penalty (L = generated tokens, the
+        eos included), early_stopping=True finishing a sample once the pool holds K and False once no running beam can
+        still beat its worst entry.  Returns the ids of the best num_return_sequences <= K hypotheses per sample,
+        [B * num_return_sequences, longest returned hypothesis], pad_token_id behind each eos; with
+        return_beam_scores=True the pair (ids, scores f32 [B * num_return_sequences]).  Every step is on the device:
+        ops.beam_emit does log-softmax, the exact top-2K selection, eos, pool and done flags in one launch, and the KV
+        cache [B, K, T_max, 2D] is read through a beam indirection table (ops.decode_step_attn_beam) that the emit
+        updates in place -- no cache row is ever copied, the prompt's keys are stored once per sample and the prefill
+        runs at batch B.  One hipGraph replay per token as for greedy; decode_graph=False, MACAW_NO_DECODE_GRAPH and
+        max_new_tokens <= 2 run the same launches kernel by kernel; use_cache=False recomputes the B * K prefixes with
+        the same ops.beam_emit (any dtype; test reference).  The host backtracks the (token, parent) history once,
+        after the loop.  Composes with decode_weights (their limit becomes B * K <= 32) and LoRA.  ValueError naming the
+        condition for num_beams outside [1, 16], num_return_sequences > num_beams, a vocabulary below 2 * num_beams,
+        do_sample=True, kv_cache="fp8" and a padded attention_mask (the last two are not built), and for use_cache=True
+        with fp32 parameters or a shape outside ops.decode_attn_ok (use use_cache=False).  num_beams=1 (default): today's
+        path whatever the other beam arguments say, not one launch different."""
+        K = beam_check("generate", num_beams)
         if decode_weights not in (None, "fp8", "mxfp4"):
             raise ValueError(f"generate: decode_weights must be None, 'fp8' or 'mxfp4', got {decode_weights!r}")
         if kv_cache not in (None, "fp8"):
@@ -653,9 +726,17 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ragged, rg_pos, rg_last = padded
         V = self.lm_head.weight.shape[0]
         out = []
+        if K > 1:
+            beam_check("generate", K, num_return_sequences, V, do_sample, kv_cache, ragged is not None, length_penalty)
+            hd0 = D // self.model.layers[0].self_attn.num_heads
+            if use_cache and not ops.decode_attn_ok(dtype, hd0, S0 + max_new_tokens):
+                why = (f"fp32 parameters ({dtype})" if dtype not in (torch.bfloat16, torch.float16) else
+                       f"ops.decode_attn_ok is false for head size {hd0} and {S0 + max_new_tokens} positions")
+                raise ValueError(f"generate(num_beams={K}) with use_cache=True: {why}; the beam step attention takes bf16 / "
+                                 "fp16 inside ops.decode_attn_ok: pass use_cache=False")
 
         if decode_weights is not None:
-            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, value=decode_weights)
+            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, value=decode_weights, beams=K)
         if kv_cache == "fp8":
             self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="kv_cache")
         w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
@@ -670,6 +751,39 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if sample is not None:
                 return ops.sample_rows(logits(h_last), V, *sample, step=t)
             return ops.argmax_rows(logits(h_last), V)
+
+        def beam_out(bs, state):      # the books after the loop -> what generate returns
+            n_cols = int(state[1])
+            ids, sc = beam_result(bs.hist.cpu(), bs.scores.cpu(), bs.pool_score.cpu(), bs.pool_info.cpu(), bs.done.cpu(),
+                                  n_cols, length_penalty, num_return_sequences, pad,
+                                  -1 if eos_token_id is None else eos_token_id)
+            return (ids.to(dev), sc.to(dev)) if return_beam_scores else ids.to(dev)
+
+        if not use_cache and K > 1:   # the B * K prefixes recomputed per step, the same ops.beam_emit
+            state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)
+            bs = ops.BeamState(B, K, max_new_tokens, pad, dev)
+            emb = inputs_embeds.contiguous()
+            base = torch.arange(B, device=dev).repeat_interleave(K) * K
+            for t in range(max_new_tokens):
+                R, S = emb.shape[0], emb.shape[1]
+                self.model._defer_final_norm = True
+                try:
+                    h = self.model(inputs_embeds=emb)
+                finally:
+                    self.model._defer_final_norm = False
+                last = torch.empty((R, D), dtype=dtype, device=dev)
+                ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=R, s_src=S * D, s_dst=D, src_off=(S - 1) * D)
+                ops.beam_emit(logits(last), V, 1 if t == 0 else K, pad, eos_token_id, length_penalty, early_stopping, bs, state)
+                if t + 1 == max_new_tokens or bool(bs.done.all()):
+                    break
+                # row (b, j) continues the prefix of its parent (b, parent[j]) with its new token
+                src = (base + bs.hist[t, :, :, 1].reshape(-1).long()) if t > 0 else torch.arange(B, device=dev).repeat_interleave(K)
+                nemb = torch.empty((B * K, S + 1, D), dtype=dtype, device=dev)
+                nemb[:, :S] = emb.index_select(0, src)
+                ops.copy2d(ops.embedding_fwd(emb_w, bs.tok), nemb, 1, D, D, D, batch=B * K, s_src=D, s_dst=(S + 1) * D,
+                           dst_off=S * D)
+                emb = nemb
+            return beam_out(bs, state)
 
         if not use_cache:
             emb = inputs_embeds.contiguous()
@@ -721,6 +835,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if kv_cache == "fp8":
             H0 = layers[0].self_attn.num_heads
             kvc, kvs = zip(*(ops.kv8_cache(B, Tmax, H0, D // H0, dev) for _ in layers))
+        elif K > 1:               # one slot per beam; the prompt lives in slot 0 of its sample only
+            kvc = [torch.empty((B, K, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]
         else:
             kvc = [torch.empty((B, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]   # [keys | values]
 
@@ -741,7 +857,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         w8 = None                 # decode_weights="fp8" / "mxfp4": per layer the copies of q|k|v, o, gate|up, down
         if decode_weights is not None:
-            probe = torch.empty((B, 0), dtype=dtype, device=dev)
+            probe = torch.empty((B * K, 0), dtype=dtype, device=dev)     # the token rows of a step
 
             def q8(W, own):       # own: a stored parameter (version-keyed cache); else a merged copy of this call
                 if W is None or not ops.decode_linear_fp8_ok(probe, W):
@@ -765,17 +881,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 w8.append((ql(ws.wqkv, own.wqkv), ql(ws.wo, own.wo), ql(ws.wgu, own.wgu), ql(ws.wd, own.wd)))
             w8_head = q8(self.lm_head.weight, self.lm_head.weight)
 
-        def run(x2, Sn, t0, pos=None, t_dev=None):
+        def run(x2, Sn, t0, pos=None, t_dev=None, beam=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
             for i, lyr in enumerate(layers):
                 ws = merged.get(lyr, stored[i])
+                if K > 1 and beam is None:        # the prefill of a beam cache: B rows into slot 0 of every sample
+                    cache_i, tmax_i = kvc[i].view(B, K * Tmax, 2 * D), K * Tmax
+                else:
+                    cache_i, tmax_i = kvc[i], Tmax
                 x2 = eng.llama_layer_cached(
-                    x2, B, Sn, t0, kvc[i], Tmax, pos, cos, sin, lyr.self_attn.num_heads,
+                    x2, B, Sn, t0, cache_i, tmax_i, pos, cos, sin, lyr.self_attn.num_heads,
                     lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
                     lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
                     w8=w8[i] if w8 is not None and t_dev is not None else None,
-                    kv8=kvs[i] if kvs is not None else None, ragged=ragged)
+                    kv8=kvs[i] if kvs is not None else None, ragged=ragged, **({"beam": beam} if beam is not None else {}))
             return x2
 
         if ragged is not None:    # prefill over the padded rows; token 0 comes from each sample's last valid row
@@ -786,6 +906,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             last = torch.empty((B, D), dtype=dtype, device=dev)
             ops.copy2d(h, last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
         hd = D // layers[0].self_attn.num_heads
+        if K > 1:
+            graph = decode_graph and max_new_tokens > 2 and not os.environ.get("MACAW_NO_DECODE_GRAPH")
+            return beam_out(*self._generate_beam(run, logits, last, emb_w, B, K, S0, max_new_tokens, eos_token_id, pad, dev,
+                                                 length_penalty, early_stopping, graph))
         if (decode_graph and max_new_tokens > 2 and ops.decode_attn_ok(dtype, hd, Tmax)
                 and not os.environ.get("MACAW_NO_DECODE_GRAPH")):
             return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample)
@@ -973,7 +1097,8 @@ class MM_LLMs(PreTrainedModel):
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
-                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0])
+                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0],
+                                     **BEAM_SEARCH[0])
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1024,6 +1149,15 @@ class MM_LLMs(PreTrainedModel):
         if do_sample:
             _sampling_check("set_sampling", temperature, top_k, top_p)
         SAMPLING[0] = dict(do_sample=bool(do_sample), temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+
+    @staticmethod
+    def set_beam_search(num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1):
+        """Beam search for `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the same names): greedy
+        (num_beams=1) by default.  Validated here; what depends on the call (vocabulary, sampling, cache format, mask)
+        is validated by generate().  No arguments: back to the default."""
+        beam_check("set_beam_search", num_beams, num_return_sequences, length_penalty=length_penalty)
+        BEAM_SEARCH[0] = dict(num_beams=int(num_beams), length_penalty=float(length_penalty),
+                              early_stopping=bool(early_stopping), num_return_sequences=int(num_return_sequences))
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

@@ -745,6 +745,56 @@ def decode_step_attn(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_max, 
     return out
 
 
+def decode_step_attn_beam(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, ind, S0, t_max, B, K, H, hd, out, scale,
+                          q_off=0, k_off=0, v_off=0):
+    """decode_step_attn for the B * K (sample, beam) rows of a beam step over cache [B, K, t_max, 2 * H * hd], read
+    through the indirection table ind int32 [B * K, n]: key t < S0 from slot 0 of the row's sample (the shared prompt),
+    key S0 <= t < *t_dev from slot ind[row, t - S0], the new key appended to row *t_dev of the row's own slot.  No cache
+    row is copied; bit-identical per row to decode_step_attn on a physically gathered [B * K, t_max, 2D] cache"""
+    lib = _L.load()
+    es = q.element_size()
+    D = H * hd
+    if cache.dtype != q.dtype or tuple(cache.shape) != (B, K, t_max, 2 * D) or not cache.is_contiguous():
+        raise MacawHipError(f"decode_step_attn_beam: cache {cache.dtype} {tuple(cache.shape)}; expected {q.dtype} "
+                            f"{(B, K, t_max, 2 * D)}, contiguous")
+    if ind.dtype != torch.int32 or ind.dim() != 2 or ind.shape[0] != B * K or not ind.is_contiguous():
+        raise MacawHipError(f"decode_step_attn_beam: ind {ind.dtype} {tuple(ind.shape)}; expected contiguous int32 "
+                            f"[{B * K}, n]")
+    _L.check(lib.mk_decode_step_attn_beam(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es, in_bs,
+                                          _p(cos_t), _p(sin_t), _p(cache), _p(cache) + D * es, 2 * D, t_max * 2 * D,
+                                          _p(out), D, _p(t_dev), _p(ind), ind.shape[1], S0, t_max, B, K, H, hd, scale,
+                                          dt(q), _st()), "mk_decode_step_attn_beam")
+    return out
+
+
+class BeamState:
+    """the device state of a beam search (include/macaw_hip.h, "State layout"): B samples, K beams, n_max columns"""
+
+    def __init__(self, B, K, n_max, pad, device):
+        self.B, self.K, self.n_max = B, K, n_max
+        self.tok = torch.full((B * K,), pad, dtype=torch.long, device=device)
+        self.scores = torch.zeros(B * K, dtype=torch.float32, device=device)
+        self.hist = torch.zeros((n_max, B, K, 2), dtype=torch.int32, device=device)
+        self.ind = torch.zeros((B * K, n_max), dtype=torch.int32, device=device)
+        self.pool_score = torch.zeros((B, K), dtype=torch.float32, device=device)
+        self.pool_info = torch.zeros((B, K + 1, 4), dtype=torch.int32, device=device)
+        self.done = torch.zeros(B, dtype=torch.bool, device=device)
+
+
+def beam_emit(logits, V, K_in, pad, eos, length_penalty, early_stopping, bs: BeamState, state):
+    """one beam-search step for every sample in one launch (see mk_beam_emit): logits [B * K_in, >= V] row-major, K_in
+    = 1 (the prefill's row) or K; eos None or negative never matches; state int32 [>= 3] = (position, output column,
+    0) as decode_emit's.  Updates bs (tok, scores, hist, ind, pool, done) in place"""
+    lib = _L.load()
+    B, K = bs.B, bs.K
+    if logits.shape[0] != B * K_in:
+        raise MacawHipError(f"beam_emit: {logits.shape[0]} rows of logits for B = {B}, K_in = {K_in}")
+    _L.check(lib.mk_beam_emit(_p(logits), _rowmajor(logits), V, B, K, K_in, pad, -1 if eos is None else eos,
+                              float(length_penalty), int(bool(early_stopping)), _p(bs.tok), _p(bs.scores), _p(bs.hist),
+                              _p(bs.ind), bs.n_max, _p(bs.pool_score), _p(bs.pool_info), _p(bs.done), _p(state),
+                              dt(logits), _st()), "mk_beam_emit")
+
+
 def kv8_cache(B, t_max, H, hd, device):
     """an empty e4m3 KV cache in the one format of include/macaw_hip.h: (bytes uint8 [B, t_max, 2 * H * hd] =
     [keys of all heads | values of all heads] per position, scales f32 [B, t_max, 2 * H])"""

@@ -29,7 +29,12 @@ with torch.no_grad():
 # B = 1 8 16 32, R = 5): the bytes each mode streams per token (mxfp4: codes + E8M0 exponents of the layers' projections, the
 # e4m3 lm_head with its f32 scales), ms per token of every run, the medians, the implied bandwidth, the ratios and the
 # run-to-run spread of every mode (a difference counts only beyond the spreads)
+#        bench_generate.py --beam-ab [--reps R]: greedy at batch B * K against num_beams=K at batch B for (B, K) = (1, 4), (8, 4),
+# (2, 16) -- the same number of token rows per step -- alternated the same way: ms per token of every run, the medians,
+# their difference and the greedy run-to-run spread, then the stand-alone time of one ops.beam_emit launch against
+# ops.decode_emit on [B * K, 32000] logits
 AB = "--fp8-ab" in sys.argv
+BEAM = "--beam-ab" in sys.argv
 MX4 = "--mxfp4-ab" in sys.argv
 RAGGED = "--ragged-ab" in sys.argv
 SAMPLE = "--sample-ab" in sys.argv
@@ -38,7 +43,57 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if BEAM:
+    from macaw_llm_amd import ops
+    for B, K in ((1, 4), (8, 4), (2, 16)):
+        big = synthetic_inputs(cfg, B * K, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {"greedy": [], "beam": []}
+        with torch.no_grad():
+            emb_g = model.prepare_inputs_for_generation(big)[0]
+            emb_b = emb_g[::K].contiguous()         # the beam call's B prompts are B of the greedy call's B * K
+            call = {"greedy": lambda n: model.llm.generate(inputs_embeds=emb_g, max_new_tokens=n, eos_token_id=-1),
+                    "beam": lambda n: model.llm.generate(inputs_embeds=emb_b, max_new_tokens=n, eos_token_id=-1, num_beams=K)}
+            for mode in call:                       # untimed: each mode's first call at this size
+                call[mode](4)
+            for rep in range(REPS):
+                for mode in ("greedy", "beam"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        call[mode](new)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} K={K:2d} rep {rep} {mode:6s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = max(ms["greedy"]) - min(ms["greedy"])
+        diff = med["beam"] - med["greedy"]
+        print(f"B={B:2d} K={K:2d}: greedy at batch {B * K} {med['greedy']:6.3f} ms/token, num_beams={K} at batch {B} {med['beam']:6.3f} ms/token, "
+              f"beam - greedy = {diff * 1e3:+7.1f} us ({diff / med['greedy'] * 100:+5.2f} %), greedy run-to-run spread {spread * 1e3:6.1f} us "
+              f"({spread / med['greedy'] * 100:4.1f} %), beam spread {(max(ms['beam']) - min(ms['beam'])) * 1e3:6.1f} us: "
+              f"{'inside' if abs(diff) <= spread else 'OUTSIDE'} the greedy spread", flush=True)
+        # one selection launch by itself: 200 back-to-back launches between two events, after 20 warm-up launches
+        x = torch.randn(B * K, 32000, device=dev).mul_(3).to(torch.bfloat16)
+        tok, done = torch.zeros(B * K, dtype=torch.long, device=dev), torch.zeros(B * K, dtype=torch.bool, device=dev)
+        out = torch.zeros((B * K, 256), dtype=torch.long, device=dev)
+        bs = ops.BeamState(B, K, 256, 0, dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        us = {}
+        for name, fn in (("decode_emit", lambda: ops.decode_emit(x, 32000, 0, -1, tok, done, out, st)),
+                         ("beam_emit", lambda: ops.beam_emit(x, 32000, K, 0, -1, 1.0, False, bs, st))):
+            for i in range(20):
+                fn()
+            st.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
+            st.zero_()
+        print(f"B={B:2d} K={K:2d}: one launch on [{B * K}, 32000] bf16 logits (back to back, incl. launch gaps; beam_emit at output "
+              f"columns 0 ... 199): " + ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if SAMPLE:
     from macaw_llm_amd import ops
     SKW = dict(do_sample=True, top_k=50, top_p=0.9, seed=1)
