@@ -437,6 +437,44 @@ int mk_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, floa
 int mk_decode_emit_sample(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, int64_t eos,
                           int64_t* tok, void* done, int64_t* out, int64_t out_ld, int32_t* state, float temperature,
                           int32_t top_k, float top_p, uint64_t seed, int32_t dtype, void* stream);
+/* Logits processors (generate(repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=)): HF's
+ *   RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor -> MinNewTokensLengthLogitsProcessor, in that
+ *   order and with their arithmetic, written down here; restated in torch in tests/logits_proc_ref.py, to which the
+ *   kernel is pinned bit for bit.  They rewrite a row of logits IN PLACE, in front of the emit (mk_decode_emit,
+ *   mk_decode_emit_sample, mk_argmax_rows, mk_sample_rows): processors first, warpers and the selection behind them.
+ *
+ * History of row b: h_b = prompt_b ++ generated_b.
+ *   prompt     int64 [B][P] at pitch p_ld, the first clamp(p_len[b], 0, P) ids of row b (p_len int32 [B]); a null
+ *              pointer means no prompt history (P, p_ld and p_len are then not read).
+ *   generated  the step's output matrix, int64 [B][n_max] at pitch out_ld, columns [0, n) of row b, with
+ *              n = clamp((n_dev ? *n_dev : 0) + n_add, 0, n_max): n_dev is read on the device (the graph loop passes
+ *              state + 1, the output column that mk_decode_emit advances, so a captured step replays); a host loop may
+ *              pass n_dev null and its count in n_add.
+ *   An id outside [0, V) names no column: it takes part in the n-gram comparison and changes no logit.
+ *
+ * The rule, L = |h_b|:
+ *   1. repetition_penalty theta (1.0 = off): for every DISTINCT id c of h_b, x = float(logit[c]) and
+ *      x = x < 0 ? x * theta : x / theta, both in fp32, the division correctly rounded; then one rounding, to nearest
+ *      even, to the logits' type.  Each distinct id is penalised once, however often it occurs.  (-0, a NaN and +inf
+ *      take the division, -inf stays -inf.)
+ *   2. no_repeat_ngram_size n (0 = off): when L + 1 >= n, every i in [0, L - n + 1) with
+ *      h[i .. i + n - 1) == h[L - n + 1 .. L) bans h[i + n - 1]: its logit becomes -inf.  n = 1 bans every id of the
+ *      history; L < n bans nothing.
+ *   3. min_new_tokens m (0 = off): while n < m (generated tokens only), logit[eos] = -inf.  Needs 0 <= eos < V;
+ *      eos < 0 (eos_token_id=None) switches it off.
+ *
+ * mk_logits_process: one workgroup per row; the distinct ids are found with a V-bit bitmap in LDS (atomic OR: the
+ *   thread that sets an id's bit rewrites its column), the windows are compared in parallel over i.  Exact and
+ *   deterministic whatever the history length and the duplicates.  Only the columns the history and eos name are read
+ *   or written: the other columns and the padding [V, ld) keep their bits.  With everything off (theta == 1, n == 0,
+ *   and m == 0 or eos < 0) nothing is launched.  Logits bf16 / f16 / f32 [B][V] at pitch ld >= V.
+ *   MK_ERR_BAD_ARG: logits or out null, a prompt without p_len, B <= 0, V <= 0, ld < V, n_max < 0, out_ld < n_max,
+ *   P < 0, p_ld < P, theta not finite or <= 0, n < 0, m < 0.  The bitmap takes 32 KiB of LDS: V <= 2^18 = 262144, else
+ *   MK_ERR_UNSUPPORTED. */
+int mk_logits_process(void* logits, int64_t ld, int32_t V, int32_t B, const int64_t* prompt, int64_t p_ld, int32_t P,
+                      const int32_t* p_len, const int64_t* out, int64_t out_ld, int32_t n_max, const int32_t* n_dev,
+                      int32_t n_add, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens,
+                      int64_t eos, int32_t dtype, void* stream);
 /* mk_decode_step_attn: the attention block of one decode step in one launch: p = clamp(*t_dev, 0,
  *   t_max - 1); q and k_new (rows [H * hd] at batch stride in_bs) are rotated with rows p of the
  *   [positions][hd] cos / sin tables (modeling.py:76-91, rope rounding points of mk_rope); the rotated

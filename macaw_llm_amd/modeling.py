@@ -61,6 +61,8 @@ KV_CACHE = [None]
 SAMPLING = [dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None)]
 # MM_LLMs.set_beam_search: the beam arguments MM_LLMs.forward hands to generate()
 BEAM_SEARCH = [dict(num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1)]
+# MM_LLMs.set_logits_processors: the logits processors MM_LLMs.forward hands to generate()
+PROCESSORS = [dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0)]
 # MM_LLMs.set_generate_mask: whether MM_LLMs.forward hands its extended attention mask to generate()
 GENERATE_MASK = [False]
 
@@ -78,6 +80,19 @@ def _sampling_check(where, temperature, top_k, top_p):
     if not isinstance(top_k, numbers.Integral) or top_k < 0:
         raise ValueError(f"{where}: top_k must be None or an integer >= 0, got {top_k!r}")
     return float(temperature), int(top_k), float(top_p)
+
+
+def _processors_check(where, repetition_penalty, no_repeat_ngram_size, min_new_tokens):
+    """the logits-processor arguments of generate() / set_logits_processors -> (repetition_penalty, no_repeat_ngram_size,
+    min_new_tokens), or None when all three are off (1.0, 0, 0)"""
+    if not (isinstance(repetition_penalty, numbers.Real) and not isinstance(repetition_penalty, bool)
+            and math.isfinite(repetition_penalty) and repetition_penalty > 0):
+        raise ValueError(f"{where}: repetition_penalty must be a finite number > 0, got {repetition_penalty!r}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"{where}: {name} must be an integer >= 0, got {v!r}")
+    proc = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens))
+    return None if proc == (1.0, 0, 0) else proc
 
 
 def _rows_view(ts):
@@ -481,14 +496,15 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                       hidden_states=None, attentions=None)
 
     @torch.no_grad()
-    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None):
+    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
         memory -- the position (int32 counter read by the fused RoPE + cache append + attention
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
         by ops.decode_emit) -- so the launches of a step (5 per layer + 3) are captured once, after
         one eager step that also serves as the warm-up, and replayed; the host only looks at the
         finished flags every few tokens.  sample = (temperature, top_k, top_p, seed): ops.decode_emit_sample draws the
-        token instead, its random number a hash of (seed, output column, sample) computed on the device."""
+        token instead, its random number a hash of (seed, output column, sample) computed on the device.  process(logits,
+        out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1]."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         tok = torch.zeros(B, dtype=torch.long, device=dev)
@@ -497,10 +513,13 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         V = self.lm_head.weight.shape[0]
 
         def emit(h_last):                # argmax, pad / eos handling, output column, position += 1
+            lg = logits(h_last)
+            if process is not None:
+                process(lg, out_buf, state[1:2])
             if sample is not None:
-                ops.decode_emit_sample(logits(h_last), V, pad, eos, tok, done, out_buf, state, *sample)
+                ops.decode_emit_sample(lg, V, pad, eos, tok, done, out_buf, state, *sample)
             else:
-                ops.decode_emit(logits(h_last), V, pad, eos, tok, done, out_buf, state)
+                ops.decode_emit(lg, V, pad, eos, tok, done, out_buf, state)
 
         def step():
             emit(run(ops.embedding_fwd(emb_w, tok), 1, 0, pos=t_dev, t_dev=t_dev))
@@ -608,7 +627,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
                  kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None,
                  attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
-                 return_beam_scores=False, **_):
+                 return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -697,8 +716,33 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         condition for num_beams outside [1, 16], num_return_sequences > num_beams, a vocabulary below 2 * num_beams,
         do_sample=True, kv_cache="fp8" and a padded attention_mask (the last two are not built), and for use_cache=True
         with fp32 parameters or a shape outside ops.decode_attn_ok (use use_cache=False).  num_beams=1 (default): today's
-        path whatever the other beam arguments say, not one launch different."""
+        path whatever the other beam arguments say, not one launch different.
+
+        repetition_penalty, no_repeat_ngram_size, min_new_tokens: HF's logits processors of the same names, in HF's
+        order and arithmetic (the rule is written down in include/macaw_hip.h and restated in tests/logits_proc_ref.py):
+        every distinct id of the history has its logit divided by the penalty (multiplied when negative), in fp32 with
+        one rounding to the logits' type; every id that would complete an n-gram the history already holds gets -inf;
+        eos gets -inf while fewer than min_new_tokens tokens were generated.  One launch (ops.logits_process) rewrites
+        the step's logits in place in front of the emit -- on the hipGraph path inside the captured step, the history
+        length read from the device, so the host still does not touch a step -- and in front of the selection of the
+        eager, use_cache=False and padded-batch loops; token 0 is processed too.  Sampling runs behind them
+        (processors, then warpers).  The history is this call's generated tokens, with the prompt's ids in front when
+        input_ids is passed (alone or next to inputs_embeds, where it is otherwise ignored; [B, P] with any P, or
+        [B, S0] under a padded attention_mask, of which only the valid ids count, in order: what the sample would
+        generate alone).  Embeddings alone, MM_LLMs' call, give a history of generated tokens, as in HF.  Composes with
+        decode_weights, kv_cache, sampling, a padded mask and LoRA.  ValueError for a penalty that is not a finite
+        number > 0, for a non-integer or negative no_repeat_ngram_size / min_new_tokens, and for any of them with
+        num_beams > 1 (processors along each beam's back-tracked history are not built).  min_new_tokens needs an
+        eos_token_id; a vocabulary above 2^18 is outside ops.logits_process.  With the defaults (1.0, 0, 0) not one
+        launch differs."""
         K = beam_check("generate", num_beams)
+        proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+        if proc is not None and K > 1:
+            on = [f"{k}={v!r}" for k, v, off in (("repetition_penalty", repetition_penalty, 1.0),
+                                                  ("no_repeat_ngram_size", no_repeat_ngram_size, 0),
+                                                  ("min_new_tokens", min_new_tokens, 0)) if v != off]
+            raise ValueError(f"generate({', '.join(on)}) with num_beams={K}: logits processors along each beam's "
+                             "back-tracked history are not built; use num_beams=1")
         if decode_weights not in (None, "fp8", "mxfp4"):
             raise ValueError(f"generate: decode_weights must be None, 'fp8' or 'mxfp4', got {decode_weights!r}")
         if kv_cache not in (None, "fp8"):
@@ -726,6 +770,30 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ragged, rg_pos, rg_last = padded
         V = self.lm_head.weight.shape[0]
         out = []
+        process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add)
+        if proc is not None:
+            hist = hist_len = None    # the prompt's ids as history: [B, P] int64 and the count per row
+            if input_ids is not None:
+                hist = input_ids.to(dev).long()
+                if hist.dim() != 2 or hist.shape[0] != B:
+                    raise ValueError(f"generate: input_ids should be [{B}, P] as the processors' prompt history, but is "
+                                     f"{tuple(hist.shape)}")
+                if ragged is not None:    # only the valid ids, in order, as the sample alone would hold them
+                    if hist.shape[1] != S0:
+                        raise ValueError(f"generate: input_ids should be of size {(B, S0)} next to a padded "
+                                         f"attention_mask, but is {tuple(hist.shape)}")
+                    valid = ragged.kmask != 0
+                    slot = torch.where(valid, ragged.slot, torch.full_like(ragged.slot, S0)).long()
+                    hist = torch.zeros((B, S0 + 1), dtype=torch.long, device=dev).scatter_(1, slot, hist)[:, :S0]
+                    hist_len = valid.sum(1).to(torch.int32).contiguous()
+                else:
+                    hist_len = torch.full((B,), hist.shape[1], dtype=torch.int32, device=dev)
+                hist = hist.contiguous()
+
+            def process(lg, gen, n_dev=None, n_add=0):
+                ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
+
+            gen_buf = torch.full((B, max_new_tokens), pad, dtype=torch.long, device=dev)   # the eager loops' ids so far
         if K > 1:
             beam_check("generate", K, num_return_sequences, V, do_sample, kv_cache, ragged is not None, length_penalty)
             hd0 = D // self.model.layers[0].self_attn.num_heads
@@ -748,9 +816,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             return ops.linear_fwd(y, self.lm_head.weight)
 
         def select(h_last, t):    # h_last [B, D] -> ids [B] of new token t
+            lg = logits(h_last)
+            if process is not None:
+                process(lg, gen_buf, n_add=t)
             if sample is not None:
-                return ops.sample_rows(logits(h_last), V, *sample, step=t)
-            return ops.argmax_rows(logits(h_last), V)
+                return ops.sample_rows(lg, V, *sample, step=t)
+            return ops.argmax_rows(lg, V)
 
         def beam_out(bs, state):      # the books after the loop -> what generate returns
             n_cols = int(state[1])
@@ -807,6 +878,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                src_off=(S - 1) * D)
                 nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
                 out.append(nxt)
+                if gen_buf is not None:
+                    gen_buf[:, t] = nxt
                 done = done | (nxt == eos_token_id)
                 if bool(done.all()):
                     break
@@ -912,11 +985,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                                  length_penalty, early_stopping, graph))
         if (decode_graph and max_new_tokens > 2 and ops.decode_attn_ok(dtype, hd, Tmax)
                 and not os.environ.get("MACAW_NO_DECODE_GRAPH")):
-            return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample)
+            return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample,
+                                        process)
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
         for t in range(max_new_tokens):
             nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
             out.append(nxt)
+            if gen_buf is not None:
+                gen_buf[:, t] = nxt
             done = done | (nxt == eos_token_id)
             if t + 1 == max_new_tokens or bool(done.all()):
                 break
@@ -1098,7 +1174,7 @@ class MM_LLMs(PreTrainedModel):
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0],
-                                     **BEAM_SEARCH[0])
+                                     **BEAM_SEARCH[0], **PROCESSORS[0])
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1158,6 +1234,16 @@ class MM_LLMs(PreTrainedModel):
         beam_check("set_beam_search", num_beams, num_return_sequences, length_penalty=length_penalty)
         BEAM_SEARCH[0] = dict(num_beams=int(num_beams), length_penalty=float(length_penalty),
                               early_stopping=bool(early_stopping), num_return_sequences=int(num_return_sequences))
+
+    @staticmethod
+    def set_logits_processors(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+        """Logits processors for `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the same names):
+        off (1.0, 0, 0) by default.  forward passes embeddings only, so the history they look at is the generated
+        tokens, as in HF for the reference's call.  Validated here; with beam search on, generate() refuses them.  No
+        arguments: back to the default."""
+        _processors_check("set_logits_processors", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+        PROCESSORS[0] = dict(repetition_penalty=float(repetition_penalty), no_repeat_ngram_size=int(no_repeat_ngram_size),
+                             min_new_tokens=int(min_new_tokens))
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

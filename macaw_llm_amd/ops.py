@@ -730,6 +730,39 @@ def decode_emit_sample(logits, V, pad, eos, tok, done, out, state, temperature=1
                                        int(seed) & 0xFFFFFFFFFFFFFFFF, dt(logits), _st()), "mk_decode_emit_sample")
 
 
+def logits_process(logits, V, out, n_dev=None, n_add=0, prompt=None, prompt_len=None, repetition_penalty=1.0,
+                   no_repeat_ngram_size=0, min_new_tokens=0, eos=None):
+    """the logits processors in one launch, in place, in front of an emit (see mk_logits_process): logits [B, >= V]
+    row-major; the history of row b is prompt[b, :prompt_len[b]] (int64 [B, P] and int32 [B], or None) followed by
+    out[b, :n] (int64 [B, n_max], the emit's output matrix), n = (n_dev[0] if n_dev is not None else 0) + n_add with
+    n_dev an int32 device tensor (the graph loop's state[1:2]).  repetition_penalty (1.0 = off), then
+    no_repeat_ngram_size (0 = off), then min_new_tokens (0 = off; eos None or negative = off).  Everything off: no
+    launch.  Returns logits"""
+    lib = _L.load()
+    B = logits.shape[0]
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise MacawHipError(f"logits_process: out {out.dtype} {tuple(out.shape)} {out.stride()}; expected row-major int64 "
+                            f"[{B}, n]")
+    if n_dev is not None and (n_dev.dtype != torch.int32 or n_dev.numel() < 1):
+        raise MacawHipError(f"logits_process: n_dev {n_dev.dtype} {tuple(n_dev.shape)}; expected int32 [>= 1]")
+    P = p_ld = 0
+    if prompt is not None:
+        if (prompt.dtype != torch.int64 or prompt.dim() != 2 or prompt.shape[0] != B
+                or (prompt.shape[1] > 1 and prompt.stride(1) != 1)):
+            raise MacawHipError(f"logits_process: prompt {prompt.dtype} {tuple(prompt.shape)} {prompt.stride()}; expected "
+                                f"row-major int64 [{B}, P]")
+        if (prompt_len is None or prompt_len.dtype != torch.int32 or prompt_len.numel() != B
+                or not prompt_len.is_contiguous()):
+            raise MacawHipError(f"logits_process: prompt_len must be a contiguous int32 [{B}] next to a prompt")
+        P, p_ld = prompt.shape[1], max(prompt.stride(0), prompt.shape[1])
+    _L.check(lib.mk_logits_process(_p(logits), _rowmajor(logits), V, B, _p(prompt), p_ld, P,
+                                   _p(prompt_len) if prompt is not None else None, _p(out),
+                                   max(out.stride(0), out.shape[1]), out.shape[1], _p(n_dev), int(n_add),
+                                   float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
+                                   -1 if eos is None else int(eos), dt(logits), _st()), "mk_logits_process")
+    return logits
+
+
 def decode_step_attn(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_max, B, H, hd, out, scale,
                      q_off=0, k_off=0, v_off=0):
     """RoPE(q, k_new) at position *t_dev + append [k_new | v_new] to cache [B, t_max, 2 * H * hd] row

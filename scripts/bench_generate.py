@@ -33,7 +33,13 @@ with torch.no_grad():
 # (2, 16) -- the same number of token rows per step -- alternated the same way: ms per token of every run, the medians,
 # their difference and the greedy run-to-run spread, then the stand-alone time of one ops.beam_emit launch against
 # ops.decode_emit on [B * K, 32000] logits
+#        bench_generate.py --processors-ab [--reps R] [B ...]: greedy against repetition_penalty=1.2, no_repeat_ngram_size=3,
+# min_new_tokens=8 (the logits processors, one ops.logits_process launch in front of the emit of every step), alternated the
+# same way: ms per token of every run, the medians, their difference and the greedy run-to-run spread (the difference counts
+# only beyond it), then the stand-alone time of one ops.logits_process launch against ops.decode_emit on [B, 32000] logits
+# with a history of 200 prompt + 100 generated ids
 AB = "--fp8-ab" in sys.argv
+PROC = "--processors-ab" in sys.argv
 BEAM = "--beam-ab" in sys.argv
 MX4 = "--mxfp4-ab" in sys.argv
 RAGGED = "--ragged-ab" in sys.argv
@@ -43,7 +49,7 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
 if BEAM:
     from macaw_llm_amd import ops
     for B, K in ((1, 4), (8, 4), (2, 16)):
@@ -93,6 +99,61 @@ if BEAM:
             st.zero_()
         print(f"B={B:2d} K={K:2d}: one launch on [{B * K}, 32000] bf16 logits (back to back, incl. launch gaps; beam_emit at output "
               f"columns 0 ... 199): " + ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
+if PROC:
+    from macaw_llm_amd import ops
+    PKW = dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=8)
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {"greedy": [], "processors": []}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for mode in ms:                         # untimed: each mode's first call at this batch size
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=2, **(PKW if mode == "processors" else {}))
+            for rep in range(REPS):
+                for mode in ("greedy", "processors"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        ids = model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=2,      # (an eos: min_new_tokens is live)
+                                                 **(PKW if mode == "processors" else {}))
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                        assert ids.shape[1] == new, f"stopped early at {ids.shape[1]} of {new} tokens: the timing would be of another loop"
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {mode:10s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = max(ms["greedy"]) - min(ms["greedy"])
+        diff = med["processors"] - med["greedy"]
+        print(f"B={B:2d}: greedy {med['greedy']:6.3f} ms/token, processors {med['processors']:6.3f} ms/token, processors - greedy = "
+              f"{diff * 1e3:+7.1f} us ({diff / med['greedy'] * 100:+5.2f} %), greedy run-to-run spread {spread * 1e3:6.1f} us "
+              f"({spread / med['greedy'] * 100:4.1f} %): {'inside' if abs(diff) <= spread else 'OUTSIDE'} the spread", flush=True)
+        # one launch by itself: 200 back-to-back launches between two events, after 20 warm-up launches
+        x = torch.randn(B, 32000, device=dev).mul_(3).to(torch.bfloat16)
+        g = torch.Generator(device=dev).manual_seed(3)
+        prompt = torch.randint(0, 32000, (B, 200), generator=g, device=dev)
+        p_len = torch.full((B,), 200, dtype=torch.int32, device=dev)
+        out = torch.randint(0, 32000, (B, 256), generator=g, device=dev)
+        tok, done = torch.zeros(B, dtype=torch.long, device=dev), torch.zeros(B, dtype=torch.bool, device=dev)
+        out_e = torch.zeros((B, 256), dtype=torch.long, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        n_dev = torch.tensor([100], dtype=torch.int32, device=dev)
+        us = {}
+        for name, fn in (("decode_emit", lambda: ops.decode_emit(x, 32000, 0, -1, tok, done, out_e, st)),
+                         ("logits_process (1.2, 3, 8), 300 ids", lambda: ops.logits_process(x, 32000, out, n_dev, 0, prompt, p_len, 1.2, 3, 8, 2)),
+                         ("logits_process (1.2, 0, 0), 300 ids", lambda: ops.logits_process(x, 32000, out, n_dev, 0, prompt, p_len, 1.2, 0, 0, 2)),
+                         ("logits_process (1.0, 3, 0), 300 ids", lambda: ops.logits_process(x, 32000, out, n_dev, 0, prompt, p_len, 1.0, 3, 0, 2))):
+            for i in range(20):
+                fn()
+            st.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
+            st.zero_()
+        print(f"B={B:2d}: one launch on [B, 32000] bf16 logits (back to back, incl. launch gaps): " +
+              ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
     sys.exit(0)
 if SAMPLE:
     from macaw_llm_amd import ops
