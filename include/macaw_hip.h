@@ -608,6 +608,77 @@ int mk_decode_step_attn_beam(const void* q, const void* k_new, const void* v_new
                              int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
                              const int32_t* ind, int32_t n_ind, int32_t S0, int32_t t_max, int32_t B, int32_t K,
                              int32_t H, int32_t hd, float scale, int32_t dtype, void* stream);
+/* Prompt-lookup speculative decoding (generate(prompt_lookup_num_tokens=G)): HF's prompt_lookup_num_tokens, greedy.  A
+ *   step proposes up to G draft tokens per sample by matching an n-gram in the history and verifies them in ONE pass of
+ *   Q = G + 1 token rows per sample over the weights.  The rule is written down here and restated in numpy in
+ *   tests/spec_ref.py, to which the kernels are pinned.
+ *
+ * Per-sample state (all on the device; B samples, Q = G + 1, n_max = max_new_tokens; no batch-wide counter and no
+ *   arrival counter):
+ *   pos      int32 [B]         position and cache row of the row-0 token of the next step
+ *   n_out    int32 [B]         tokens emitted so far
+ *   done     one byte per sample
+ *   out      int64 [B][n_max]  the emitted ids (pitch out_ld); the host fills it with pad before the first step
+ *   tok      int64 [B][Q]      the ids fed to the step: column 0 the last emitted token, columns 1 ... G the draft
+ *   n_draft  int32 [B]         draft tokens of the step
+ *   steps    int32 [B]         verify steps taken (token 0 included)
+ *
+ * Draft (mk_spec_lookup, one workgroup per sample).  h = prompt history ++ out[b][:n_out[b]], L = |h|; the prompt history
+ *   is the processors': prompt int64 [B][P] at pitch p_ld, the first clamp(p_len[b], 0, P) ids of row b, a null pointer
+ *   = empty.  For n = min(max_matching_ngram_size, L - 1) down to 1:
+ *   1. take the SMALLEST i with i + n < L and h[i:i+n] == h[L-n:L] (the trailing window itself is never a match);
+ *   2. on the first n that has such an i, draft = h[i+n : min(i+n+G, L)];
+ *   3. cut the draft BEFORE its first eos;
+ *   4. stop after that n: if the cut leaves nothing there is no draft, and no smaller n is tried.
+ *   This is transformers' PromptLookupCandidateGenerator.get_candidates without a logits processor.  No match, or L < 2,
+ *   gives n_draft = 0.  Draft columns beyond n_draft hold pad.  Ids outside [0, V) never match (a window that holds one
+ *   equals nothing) and are never proposed (the draft is cut before the first of them, like an eos).  A finished sample
+ *   gets n_draft = 0.  eos < 0 never matches (eos_token_id=None).  tok[b][0] is not written.
+ *   MK_ERR_BAD_ARG: out, n_out, done, tok or n_draft null, a prompt without p_len, B <= 0, G outside [1, 15],
+ *   max_matching_ngram_size < 1, V <= 0, n_max < 0, out_ld < n_max, P < 0, p_ld < P.
+ *
+ * Step.  Rows (b, g), g = 0 ... G, at row index b * Q + g, carry tok[b][g] at position pos[b] + g.  Every row runs through
+ *   every layer and the lm_head whatever n_draft is: the launch sequence is fixed.
+ *
+ * Verify and emit (mk_spec_verify_emit, one workgroup per sample).  Logits bf16 / f16 / f32 [B * R][V] at pitch ld >= V,
+ *   R rows per sample: R = Q for a step, R = 1 for token 0 (the prefill's [B][V] logits: no draft, n_draft is not read).
+ *   a_g = the first argmax of row (b, g) over [0, V), with mk_argmax_rows' treatment of NaN and -inf.
+ *   A = the number of leading draft tokens with tok[b][1 + j] == a_j, j < n_draft[b].  The step emits a_0 ... a_A, cut
+ *   after the first eos (inclusive) and to n_max - n_out[b] tokens.  With m tokens emitted: out[b][n_out ... n_out + m)
+ *   receives them, n_out += m, pos += m, steps += 1, done[b] is set on an emitted eos or when n_out == n_max, and
+ *   tok[b][0] becomes the last emitted id.  A finished sample changes nothing; its rows keep running at its frozen pos
+ *   and touch only cache rows nobody reads.  Token 0 starts from pos[b] = S0 - 1, so that pos[b] = S0 after it.
+ *   MK_ERR_BAD_ARG: a null pointer, V <= 0, B <= 0, ld < V, Q outside [1, 16], R not in {1, Q}, n_max < 0,
+ *   out_ld < n_max.  Another dtype: MK_ERR_UNSUPPORTED.
+ *
+ * Multi-query step attention (mk_decode_step_attn_multi, one workgroup per head, sample and row): mk_decode_step_attn for
+ *   the B * Q rows of a step.  q, k_new, v_new: rows [H * hd] at ROW stride in_bs, row b * Q + g; o likewise at row
+ *   stride o_bs; the 16-bit cache [B][t_max][2D] (kv_ld, kv_bs as mk_decode_step_attn); pos int32 [B] on the device
+ *   (negative values count as 0).  For g = 0 ... Q - 1: p = pos[b] + g; RoPE of q and k at row p of the tables
+ *   (mk_rope's rounding points); the rotated key and the value go to cache row p; query g attends over keys 0 ... p --
+ *   the cached prefix and the new rows 0 ... g of its own sample, nothing later.  Row (b, g)'s output is BIT FOR BIT what
+ *   mk_decode_step_attn writes for a single sample at *t_dev = pos[b] + g on a cache whose rows pos[b] ... pos[b] + g - 1
+ *   already hold the rotated keys and values of rows 0 ... g - 1 (the one-workgroup-per-head kernel the plain entry
+ *   selects for B * H < 512): the same kernel body with the plain kernel's key -> lane / wave assignment and reduction
+ *   order.  The Q rows of a (head, sample) run in Q workgroups side by side, at the latency of one plain launch: row g
+ *   rotates the keys of rows 0 ... g - 1 itself (into LDS) and reads their values from v_new -- the bits the cache
+ *   will hold -- so no workgroup waits for another, and no cache row >= pos[b] is read.  With H a multiple of 8 the Q
+ *   workgroups of a (head, sample) share an XCD: the cached prefix comes from HBM once and from that L2 for the other
+ *   rows.  A row with pos[b] + g >= t_max writes nothing to the cache, and its output is zeros.
+ *   Domain, else MK_ERR_UNSUPPORTED and nothing is launched: dtype bf16 / f16; hd in {16, 32, 64, 128}; Q <= 16;
+ *   alignment and strides as mk_decode_step_attn, pos 4-byte aligned.  The kernel keeps no per-key buffer in LDS, so
+ *   t_max does not bound the domain.  MK_ERR_BAD_ARG: a null pointer, B, H or t_max <= 0, Q < 1. */
+int mk_spec_lookup(const int64_t* prompt, int64_t p_ld, int32_t P, const int32_t* p_len, const int64_t* out,
+                   int64_t out_ld, int32_t n_max, const int32_t* n_out, const void* done, int64_t* tok,
+                   int32_t* n_draft, int32_t B, int32_t G, int32_t max_matching_ngram_size, int32_t V, int64_t pad,
+                   int64_t eos, void* stream);
+int mk_spec_verify_emit(const void* logits, int64_t ld, int32_t V, int32_t B, int32_t R, int32_t Q, int64_t eos,
+                        int64_t* tok, const int32_t* n_draft, int32_t* pos, int32_t* n_out, void* done, int64_t* out,
+                        int64_t out_ld, int32_t n_max, int32_t* steps, int32_t dtype, void* stream);
+int mk_decode_step_attn_multi(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                              const void* sin_t, void* k_cache, void* v_cache, int64_t kv_ld, int64_t kv_bs, void* o,
+                              int64_t o_bs, const int32_t* pos, int32_t t_max, int32_t B, int32_t Q, int32_t H,
+                              int32_t hd, float scale, int32_t dtype, void* stream);
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);

@@ -145,21 +145,35 @@ MK_DEV long beam_slot_off(const A& a, int row, int t) {
 
 // VAR (mk_decode_step_attn_var): p = clamp(*t_dev + t_off[b]) per sample, a padded batch's ragged cache; everything
 // after p is the same code, so a sample's arithmetic is that of the plain kernel at *t_dev = p.
-template <int HD, int NWV, bool VAR = false, bool BEAM = false>
-__global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(typename StepArgsOf<BEAM>::type a) {
+// RoPE of the 8 elements a lane holds of a head's row (its partner half comes from lane +- LPK / 2), rope_kernel's
+// rounding points: each product and the sum rounded to e16.  first half: x cos - partner sin; second half: x cos + partner sin
+template <int LPK>
+MK_DEV void rope8(const e16x8& xv, const e16x8& cv, const e16x8& sv, bool first, float (&out)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float cs = (float)cv[e], sn = (float)sv[e];
+    const float xo = (float)xv[e];
+    const float xp = __shfl_xor(xo, LPK / 2, 64);
+    const float sx = first ? rnd_e16(-xp * sn) : rnd_e16(xp * sn);
+    out[e] = rnd_e16(rnd_e16(xo * cs) + sx);
+  }
+}
+
+// The step of ONE query row at position p, shared by every form of the kernel: the new q / k / v row at element offset
+// in_row, the output row at o_row, b = the sample (BEAM: the row) whose cache slot the row appends to and reads.
+// MULTI (mk_decode_step_attn_multi): keys p0 ... p - 1 are the EARLIER rows of the same step, which other workgroups append
+// at the same time: their rotated keys come from knew (LDS, rotated by this workgroup) and their values from the step's
+// v_new rows (row 0 of the sample at element offset vn0) -- the bits the cache will hold -- and no cache row >= p0 is read.
+template <int HD, int NWV, bool BEAM, bool MULTI = false, typename A>
+MK_DEV void decode_step_attn_body(const A& a, float (*red)[HD], float* redw, int h, int b, long in_row, long o_row, int p,
+                                  int p0 = 0, const e16 (*knew)[HD] = nullptr, long vn0 = 0) {
   constexpr int LPK = HD / 8, KPW = 64 / LPK, KPP = NWV * KPW;
-  __shared__ float red[NWV][HD];
-  __shared__ float redw[2 * NWV];
-  const int h = blockIdx.x, b = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int tp = *a.t_dev;
-  if constexpr (VAR) tp += a.t_off[b];
-  const int p = min(max(tp, 0), a.t_max - 1);
   const int T = p + 1;
   const int sub = lane % LPK, grp = lane / LPK;
   const int d0 = sub * 8;
   const bool first = d0 < HD / 2;
-  const long in_off = (long)b * a.in_bs + (long)h * HD + d0;
+  const long in_off = in_row + (long)h * HD + d0;
   float qf[8], kf[8];
   e16x8 vnew = *reinterpret_cast<const e16x8*>(a.vn + in_off);
   {
@@ -167,17 +181,8 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(typename Ste
     const e16x8 kv = *reinterpret_cast<const e16x8*>(a.kn + in_off);
     const e16x8 cv = *reinterpret_cast<const e16x8*>(a.cos_t + (long)p * HD + d0);
     const e16x8 sv = *reinterpret_cast<const e16x8*>(a.sin_t + (long)p * HD + d0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float cs = (float)cv[e], sn = (float)sv[e];
-      const float qo = (float)qv[e], ko = (float)kv[e];
-      const float qp = __shfl_xor(qo, LPK / 2, 64), kp = __shfl_xor(ko, LPK / 2, 64);
-      // first half: x cos - partner sin; second half: x cos + partner sin
-      const float sq = first ? rnd_e16(-qp * sn) : rnd_e16(qp * sn);
-      const float sk = first ? rnd_e16(-kp * sn) : rnd_e16(kp * sn);
-      qf[e] = rnd_e16(rnd_e16(qo * cs) + sq);
-      kf[e] = rnd_e16(rnd_e16(ko * cs) + sk);
-    }
+    rope8<LPK>(qv, cv, sv, first, qf);
+    rope8<LPK>(kv, cv, sv, first, kf);
   }
   if (wave == 0 && grp == 0) {     // append the new key / value (cache row p)
     e16x8 kb;
@@ -201,7 +206,10 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(typename Ste
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const int t = t0 + j * KPP;
-      if (t < p) {
+      if (MULTI && t >= p0 && t < p) {
+        kv[j] = *reinterpret_cast<const e16x8*>(&knew[t - p0][d0]);
+        vv[j] = *reinterpret_cast<const e16x8*>(a.vn + vn0 + (long)(t - p0) * a.in_bs + (long)h * HD + d0);
+      } else if (t < p) {
         const long so = beam_slot_off<BEAM>(a, b, t);
         kv[j] = *reinterpret_cast<const e16x8*>(K + so + (long)t * a.kv_ld);
         vv[j] = *reinterpret_cast<const e16x8*>(V + so + (long)t * a.kv_ld);
@@ -273,8 +281,63 @@ __global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(typename Ste
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < NWV; ++i) v += red[i][tid];
-    a.o[(long)b * a.o_bs + (long)h * HD + tid] = (e16)(v / sum);
+    a.o[o_row + (long)h * HD + tid] = (e16)(v / sum);
   }
+}
+
+template <int HD, int NWV, bool VAR = false, bool BEAM = false>
+__global__ __launch_bounds__(NWV * 64) void decode_step_attn_kernel(typename StepArgsOf<BEAM>::type a) {
+  __shared__ float red[NWV][HD];
+  __shared__ float redw[2 * NWV];
+  const int h = blockIdx.x, b = blockIdx.y;
+  int tp = *a.t_dev;
+  if constexpr (VAR) tp += a.t_off[b];
+  const int p = min(max(tp, 0), a.t_max - 1);
+  decode_step_attn_body<HD, NWV, BEAM>(a, red, redw, h, b, (long)b * a.in_bs, (long)b * a.o_bs, p);
+}
+
+// MULTI (mk_decode_step_attn_multi): Q query rows per sample, row (b, g) at position pos[b] + g (a.t_dev = pos [B]).  One
+// workgroup per (head, sample, ROW), so the Q rows of a step run side by side at the latency of one plain launch.  Row g
+// appends cache row pos[b] + g and attends over rows 0 ... pos[b] + g; the g rows before it belong to the same step and are
+// being appended by its sister workgroups, so it rotates their keys itself (one lane group per row, into LDS) and takes
+// their values from the step's input: the same bits, no cross-workgroup order needed.  Everything else IS the plain
+// kernel's code -- the same key -> lane / wave assignment and reduction order, so the same bits.  With H a multiple of 8
+// the Q workgroups of a (head, sample) have linear ids H apart and land on one XCD: the cached prefix is read from HBM once
+// and from that XCD's L2 by the others.  A row at or past t_max appends nothing and its output is zeros.
+constexpr int MULTI_MAX_Q = 16;
+template <int HD, int NWV>
+__global__ __launch_bounds__(NWV * 64) void decode_step_attn_multi_kernel(DecodeStepArgs a, int Q) {
+  constexpr int LPK = HD / 8, KPW = 64 / LPK;
+  static_assert(NWV * KPW >= MULTI_MAX_Q - 1, "one lane group per earlier row");
+  __shared__ float red[NWV][HD];
+  __shared__ float redw[2 * NWV];
+  __shared__ __attribute__((aligned(16))) e16 knew[MULTI_MAX_Q - 1][HD];
+  const int h = blockIdx.x, b = blockIdx.y / Q, g = blockIdx.y % Q;
+  const long row = blockIdx.y;
+  const int p0 = max(a.t_dev[b], 0);
+  if (p0 >= a.t_max - g) {             // (p0 + g cannot overflow here)
+    if (threadIdx.x < HD) a.o[row * a.o_bs + (long)h * HD + threadIdx.x] = (e16)0.f;
+    return;
+  }
+  if (g > 0) {                         // the rotated keys of rows 0 ... g - 1: lane group (wave, grp) takes row wave * KPW + grp
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane % LPK, grp = lane / LPK, d0 = sub * 8;
+    const int jr = wave * KPW + grp, jc = min(jr, g - 1);        // (every lane runs the shuffles: a clamped row)
+    const e16x8 kv = *reinterpret_cast<const e16x8*>(a.kn + ((long)b * Q + jc) * a.in_bs + (long)h * HD + d0);
+    const e16x8 cv = *reinterpret_cast<const e16x8*>(a.cos_t + (long)(p0 + jc) * HD + d0);
+    const e16x8 sv = *reinterpret_cast<const e16x8*>(a.sin_t + (long)(p0 + jc) * HD + d0);
+    float kf[8];
+    rope8<LPK>(kv, cv, sv, d0 < HD / 2, kf);
+    if (jr < g) {
+      e16x8 kb;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) kb[e] = (e16)kf[e];
+      *reinterpret_cast<e16x8*>(&knew[jr][d0]) = kb;
+    }
+    __syncthreads();
+  }
+  decode_step_attn_body<HD, NWV, false, true>(a, red, redw, h, b, row * a.in_bs, row * a.o_bs, p0 + g, p0, knew,
+                                              (long)b * Q * a.in_bs);
 }
 
 // Greedy token selection and the bookkeeping of a decode step in one launch (HF greedy_search as the
@@ -438,6 +501,36 @@ int decode_step_attn_impl(const void* q, const void* k_new, const void* v_new, i
   else if (hd == 64) MK_LAUNCH((decode_step_attn_kernel<64, 8>), grid, block, lds, st, a);
   else if (hd == 32) MK_LAUNCH((decode_step_attn_kernel<32, 8>), grid, block, lds, st, a);
   else MK_LAUNCH((decode_step_attn_kernel<16, 8>), grid, block, lds, st, a);
+  return mk_check_launch();
+}
+
+// mk_decode_step_attn_multi: the plain entry point's checks over B * Q rows, positions per sample from pos [B]
+int decode_step_attn_multi_impl(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                                const void* sin_t, void* k_cache, void* v_cache, int64_t kv_ld, int64_t kv_bs, void* o,
+                                int64_t o_bs, const int32_t* pos, int32_t t_max, int32_t B, int32_t Q, int32_t H,
+                                int32_t hd, float scale, int32_t dtype, void* stream) {
+  if (!q || !k_new || !v_new || !cos_t || !sin_t || !k_cache || !v_cache || !o || !pos || B <= 0 || H <= 0 ||
+      t_max <= 0 || Q < 1)
+    return MK_ERR_BAD_ARG;
+  if (dtype != E16<e16>::dtype || (hd != 16 && hd != 32 && hd != 64 && hd != 128) || Q > MULTI_MAX_Q) return MK_ERR_UNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_new) |
+                       reinterpret_cast<uintptr_t>(v_new) | reinterpret_cast<uintptr_t>(cos_t) |
+                       reinterpret_cast<uintptr_t>(sin_t) | reinterpret_cast<uintptr_t>(k_cache) |
+                       reinterpret_cast<uintptr_t>(v_cache);
+  if ((al & 15) || (reinterpret_cast<uintptr_t>(pos) & 3) || (in_bs % 8) || (kv_ld % 8) || (kv_bs % 8))
+    return MK_ERR_UNSUPPORTED;
+  DecodeStepArgs a;
+  a.q = (const e16*)q; a.kn = (const e16*)k_new; a.vn = (const e16*)v_new; a.in_bs = in_bs;
+  a.cos_t = (const e16*)cos_t; a.sin_t = (const e16*)sin_t;
+  a.kc = (e16*)k_cache; a.vc = (e16*)v_cache; a.kv_ld = kv_ld; a.kv_bs = kv_bs;
+  a.o = (e16*)o; a.o_bs = o_bs;
+  a.t_dev = pos; a.t_max = t_max; a.scale = scale; a.t_off = nullptr;
+  dim3 grid(H, B * Q), block(512);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hd == 128) MK_LAUNCH((decode_step_attn_multi_kernel<128, 8>), grid, block, 0, st, a, (int)Q);
+  else if (hd == 64) MK_LAUNCH((decode_step_attn_multi_kernel<64, 8>), grid, block, 0, st, a, (int)Q);
+  else if (hd == 32) MK_LAUNCH((decode_step_attn_multi_kernel<32, 8>), grid, block, 0, st, a, (int)Q);
+  else MK_LAUNCH((decode_step_attn_multi_kernel<16, 8>), grid, block, 0, st, a, (int)Q);
   return mk_check_launch();
 }
 

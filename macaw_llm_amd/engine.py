@@ -640,6 +640,13 @@ class Beam(NamedTuple):
     S0: int                  # prompt length: keys below it are read from slot 0 of the sample
 
 
+class Spec(NamedTuple):
+    """a prompt-lookup verify step for llama_layer_cached (generate(prompt_lookup_num_tokens=G)): Q = G + 1 token rows per
+    sample, row (b, g) at position pos[b] + g, the positions kept per sample on the device by ops.spec_verify_emit"""
+    pos: torch.Tensor        # int32 [B]: position and cache row of each sample's row 0
+    Q: int                   # rows per sample
+
+
 def ragged_from_mask(mask, B, S0):
     """The host side of generate(attention_mask=): mask [B, S0], any integer or bool dtype, non-zero = valid.
     Returns None for a mask without a zero (the unpadded path), else (Ragged, pos, last):
@@ -665,10 +672,14 @@ def ragged_from_mask(mask, B, S0):
     return rg, pos.to(torch.int32).reshape(-1).contiguous(), last.contiguous()
 
 
-def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged=None, beam=None, **off):
+def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged=None, beam=None, spec=None,
+               **off):
     """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
     e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8; with ragged (a padded batch) their per-sample-position forms;
-    with beam (a Beam; B samples of beam.K rows each) ops.decode_step_attn_beam over the [B, K, Tmax, 2D] cache"""
+    with beam (a Beam; B samples of beam.K rows each) ops.decode_step_attn_beam over the [B, K, Tmax, 2D] cache; with
+    spec (a Spec; B samples of spec.Q rows each) ops.decode_step_attn_multi at the per-sample positions spec.pos"""
+    if spec is not None:
+        return ops.decode_step_attn_multi(q, k, v, in_bs, cos, sin, kvc, spec.pos, Tmax, B, spec.Q, H, hd, att, scale, **off)
     if beam is not None:
         return ops.decode_step_attn_beam(q, k, v, in_bs, cos, sin, kvc, t_dev, beam.ind, beam.S0, Tmax, B, beam.K, H, hd,
                                          att, scale, **off)
@@ -709,7 +720,8 @@ def _stream_linear(x, W, q8, pro, w_ln, eps, residual, FF):
 
 
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
-                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None, ragged=None, beam=None):
+                       wd, ln1, ln2, wqkv=None, wgu=None, t_dev=None, w8=None, kv8=None, ragged=None, beam=None,
+                       spec=None):
     """No-grad decoder layer over `Sn` NEW positions per sample (rows of x2 are (b, s)) that
     start at position t0, with a preallocated KV cache kvc [B, Tmax, 2D] = [keys | values] per
     position (post-RoPE keys, modeling.py:183-195 semantics without the torch.cat per step).
@@ -746,9 +758,19 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     B * beam.K (sample, beam) rows and kvc is [B, K, Tmax, 2D]; the step attention reads it through beam.ind
     (ops.decode_step_attn_beam), every other launch sees B * K token rows and is unchanged.  The prefill of such a
     cache is a plain call at B rows on kvc.view(B, K * Tmax, 2D) with Tmax = K * Tmax: it writes slot 0 of every
-    sample.  Not with kv8 or ragged."""
+    sample.  Not with kv8 or ragged.
+
+    spec (a Spec; decode steps with t_dev only, Sn = spec.Q): a prompt-lookup verify step.  x2 holds the B * spec.Q rows
+    (b, g), row g of sample b at position spec.pos[b] + g; the step attention is ops.decode_step_attn_multi, which
+    appends the Q new rows of a sample and lets row g attend over the cache up to its own position; every other launch
+    sees B * Q token rows and is unchanged.  Not with kv8, ragged or beam, and not with a host position."""
     M, D = x2.shape
     dyn = t_dev is not None
+    if spec is not None:
+        if not dyn or kv8 is not None or ragged is not None or beam is not None or Sn != spec.Q or M != B * spec.Q:
+            raise ValueError("llama_layer_cached: spec takes decode steps at device positions (t_dev) of B * Q rows "
+                             "(Sn = Q) on the 16-bit unpadded cache, not kv8, ragged, beam or a host position")
+        Sn = 1                  # per row it is a single-position step
     if beam is not None and (not dyn or kv8 is not None or ragged is not None or M != B * beam.K):
         raise ValueError("llama_layer_cached: beam takes single-position decode steps (t_dev) of B * K rows on the 16-bit "
                          "unpadded cache, not kv8 or ragged")
@@ -774,7 +796,7 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         # without w8; under the gate above that matters only for a non-contiguous wo, which takes ops.linear_fwd.
         q_qkv, q_o, q_gu, q_d = w8 if w8 is not None else (None,) * 4
         qkv = _stream_linear(x2, wqkv, q_qkv, 1, ln1, eps, None, FF)
-        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, k_off=D,
+        _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, spec, k_off=D,
                    v_off=2 * D)
         h1 = _stream_linear(att, wo, q_o, 0, None, eps, x2, FF)
         gu = _stream_linear(h1, wgu, q_gu, 1, ln2, eps, None, FF)
@@ -795,7 +817,7 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         new, off = (q, k, v), {}
         ropes, appends = ((q, H), (k, H)), ((k, D, 0, 0), (v, D, 0, D))
     if dyn:     # RoPE + cache append + attention of the new position: one launch
-        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, **off)
+        _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, spec, **off)
     else:
         for t, heads in ropes:
             ops.rope_(t, cos, sin, pos, heads, hd)

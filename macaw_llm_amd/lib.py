@@ -132,6 +132,11 @@ SIGNATURES = {
                      _vp, _i32, _vp],
     "mk_decode_step_attn_beam": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32,
                                  _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
+    "mk_spec_lookup": [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _vp],
+    "mk_spec_verify_emit": [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32,
+                            _vp],
+    "mk_decode_step_attn_multi": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32,
+                                  _i32, _i32, _f32, _i32, _vp],
     "mk_kv_append_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mk_kv_quant_append_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mk_adamw_bias_correction": [_f32, _f32, _i32, _vp],

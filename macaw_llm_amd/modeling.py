@@ -63,6 +63,8 @@ SAMPLING = [dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=Non
 BEAM_SEARCH = [dict(num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1)]
 # MM_LLMs.set_logits_processors: the logits processors MM_LLMs.forward hands to generate()
 PROCESSORS = [dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0)]
+# MM_LLMs.set_prompt_lookup: the prompt-lookup arguments MM_LLMs.forward hands to generate() (None = off)
+PROMPT_LOOKUP = [dict(prompt_lookup_num_tokens=None, max_matching_ngram_size=2)]
 # MM_LLMs.set_generate_mask: whether MM_LLMs.forward hands its extended attention mask to generate()
 GENERATE_MASK = [False]
 
@@ -93,6 +95,22 @@ def _processors_check(where, repetition_penalty, no_repeat_ngram_size, min_new_t
             raise ValueError(f"{where}: {name} must be an integer >= 0, got {v!r}")
     proc = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens))
     return None if proc == (1.0, 0, 0) else proc
+
+
+MAX_LOOKUP_TOKENS = 15    # Q = G + 1 <= 16 rows per sample (ops.SPEC_MAX_Q)
+
+
+def _lookup_check(where, num_tokens, max_matching_ngram_size):
+    """the prompt-lookup arguments of generate() / set_prompt_lookup -> G, the draft tokens per step (0 = off: None or 0)"""
+    if num_tokens is None:
+        return 0
+    if isinstance(num_tokens, bool) or not isinstance(num_tokens, numbers.Integral) or not 0 <= num_tokens <= MAX_LOOKUP_TOKENS:
+        raise ValueError(f"{where}: prompt_lookup_num_tokens must be None or an integer in [0, {MAX_LOOKUP_TOKENS}] (0 = off), "
+                         f"got {num_tokens!r}")
+    n = max_matching_ngram_size
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"{where}: max_matching_ngram_size must be an integer >= 1, got {n!r}")
+    return int(num_tokens)
 
 
 def _rows_view(ts):
@@ -592,6 +610,51 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             del g
         return bs, state
 
+    @torch.no_grad()
+    def _generate_lookup(self, run, logits, last, emb_w, B, G, S0, max_new_tokens, eos, pad, dev, ngram, hist, hist_len,
+                         graph):
+        """The prompt-lookup decode loop (_generate_graph's, with one VERIFY step of Q = G + 1 rows per sample in place of
+        the one-row step): token 0 from the prefill's B rows through ops.spec_verify_emit (one row per sample, no draft),
+        then per step ops.spec_lookup -> embedding of the [B, Q] ids -> the layers with engine.Spec -> the lm_head ->
+        ops.spec_verify_emit.  Position, count and done flag live per sample on the device (ops.SpecState).  graph: the
+        step is captured once after one eager step and replayed, the host looking at the done flags every 8 steps;
+        otherwise the same launches run kernel by kernel and the host looks after every step.  An unfinished sample emits
+        at least one token per step, so max_new_tokens - 1 steps behind token 0 always suffice.  Returns (ids [B, most
+        tokens of a sample], steps int32 [B])."""
+        ss = ops.SpecState(B, G, max_new_tokens, pad, dev)
+        ss.pos.fill_(S0 - 1)             # token 0 advances it to S0, the position its id is fed at
+        spec = eng.Spec(ss.pos, G + 1)
+        V = self.lm_head.weight.shape[0]
+
+        def verify(h_rows):
+            ops.spec_verify_emit(logits(h_rows), V, eos, ss)
+
+        def step():
+            ops.spec_lookup(ss, V, ngram, eos, hist, hist_len)
+            verify(run(ops.embedding_fwd(emb_w, ss.tok.view(-1)), G + 1, 0, pos=ss.pos, t_dev=ss.pos, spec=spec))
+
+        verify(last)                     # token 0 (from the prefill)
+        if not graph or max_new_tokens <= 2:     # no decode step would be captured
+            for _ in range(max_new_tokens - 1):
+                if bool(ss.done.all()):
+                    break
+                step()
+        else:
+            if not bool(ss.done.all()):
+                step()                   # eager (kernel attributes, allocator pools, workspace)
+            remaining = max_new_tokens - 2
+            if remaining > 0 and not bool(ss.done.all()):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    step()
+                for i in range(remaining):
+                    g.replay()
+                    if (i & 7) == 7 and bool(ss.done.all()):
+                        break
+                del g
+        width = int(ss.n_out.max())      # pad behind each sample's end; the column at which every sample has finished
+        return ss.out[:, :width].clone(), ss.steps.clone()
+
     def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="decode_weights",
                           value="fp8", beams=1):
         """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
@@ -627,7 +690,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
                  kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None,
                  attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
-                 return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, **_):
+                 return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
+                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -734,7 +798,27 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         number > 0, for a non-integer or negative no_repeat_ngram_size / min_new_tokens, and for any of them with
         num_beams > 1 (processors along each beam's back-tracked history are not built).  min_new_tokens needs an
         eos_token_id; a vocabulary above 2^18 is outside ops.logits_process.  With the defaults (1.0, 0, 0) not one
-        launch differs."""
+        launch differs.
+
+        prompt_lookup_num_tokens=G in [1, 15]: prompt-lookup speculative decoding, HF's argument of the same name, greedy
+        (the rule is written down in include/macaw_hip.h and restated in tests/spec_ref.py).  Every step proposes up to G
+        draft tokens per sample -- the continuation of the earliest earlier occurrence of the history's last
+        max_matching_ngram_size ids, shorter n-grams down to 1 when that one has none (ops.spec_lookup) -- and verifies
+        them in ONE pass of G + 1 token rows per sample over the weights: ops.decode_step_attn_multi appends the G + 1
+        keys and lets row g attend up to its own position, ops.spec_verify_emit keeps the draft tokens that equal the
+        model's own argmax plus one more token.  Every emitted id is the argmax of the model's logits given the ids
+        before it, as in plain greedy decoding; a step's linears see B * (G + 1) rows and choose their kernel by that, so
+        last bits, and with them near-ties, may differ from the one-row step's.  The history is this call's generated
+        tokens with input_ids [B, P] in front where it is given (alone or next to inputs_embeds, any P).  All state
+        (position, count, done flag per sample) is on the device: one hipGraph replay per step, the host looking at the
+        done flags every 8 steps; decode_graph=False, MACAW_NO_DECODE_GRAPH and max_new_tokens <= 2 run the same launches
+        kernel by kernel.  The KV cache gets G more rows.  Returns the new ids [B, <= max_new_tokens], pad_token_id behind
+        each sample's end; with return_lookup_stats=True the pair (ids, steps int32 [B]: verify steps per sample, token 0
+        included, so tokens / steps is the gain).  Composes with decode_weights (their limit becomes B * (G + 1) <= 32)
+        and LoRA.  ValueError naming the condition for G outside [0, 15] or not an integer, max_matching_ngram_size < 1,
+        B * (G + 1) > 32, num_beams > 1, do_sample=True, any logits processor, kv_cache="fp8", a padded attention_mask,
+        use_cache=False, fp32 parameters and a shape outside ops.spec_attn_ok: none of these combinations is built.  None
+        or 0 (default): today's path, not one launch different."""
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         if proc is not None and K > 1:
@@ -747,6 +831,31 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             raise ValueError(f"generate: decode_weights must be None, 'fp8' or 'mxfp4', got {decode_weights!r}")
         if kv_cache not in (None, "fp8"):
             raise ValueError(f"generate: kv_cache must be None or 'fp8', got {kv_cache!r}")
+        G = _lookup_check("generate", prompt_lookup_num_tokens, max_matching_ngram_size)
+        if G:                     # what prompt lookup does not compose with, before the model is touched
+            rows_of = inputs_embeds if inputs_embeds is not None else input_ids
+            why = None
+            if K > 1:
+                why = f"num_beams={K} > 1 (lookup along beams is not built)"
+            elif do_sample:
+                why = "do_sample=True (sampling-based acceptance is not built)"
+            elif proc is not None:
+                why = ("a logits processor (repetition_penalty, no_repeat_ngram_size or min_new_tokens: lookup behind "
+                       "processors is not built)")
+            elif kv_cache == "fp8":
+                why = "kv_cache='fp8' (there is no multi-row step over the e4m3 cache: not built)"
+            elif not use_cache:
+                why = "use_cache=False (the verify step runs on the KV cache: not built without it)"
+            elif attention_mask is not None and not bool((attention_mask != 0).all()):
+                why = "a padded attention_mask (lookup over a ragged cache is not built)"
+            elif rows_of.shape[0] * (G + 1) > 32:
+                why = (f"B x (G + 1) = {rows_of.shape[0]} x {G + 1} = {rows_of.shape[0] * (G + 1)} rows: a verify step takes "
+                       "at most 32 (B * Q <= 32; a wider step is not built)")
+            elif inputs_embeds is not None and inputs_embeds.dtype not in (torch.bfloat16, torch.float16):
+                why = (f"fp32 parameters ({inputs_embeds.dtype}): the multi-row step attention takes bf16 / fp16 (not built "
+                       "for fp32)")
+            if why is not None:
+                raise ValueError(f"generate(prompt_lookup_num_tokens={G}): {why}")
         sample = None
         if do_sample:
             temperature, top_k, top_p = _sampling_check("generate", temperature, top_k, top_p)
@@ -892,8 +1001,23 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     mask = torch.cat([mask, torch.ones((B, 1), dtype=mask.dtype, device=dev)], dim=1)
             return torch.stack(out, dim=1)
 
-        Tmax = S0 + max_new_tokens
+        Tmax = S0 + max_new_tokens + G        # (prompt lookup: the G draft rows behind the last token)
         layers = self.model.layers
+        look_hist = look_len = None           # prompt lookup: the prompt's ids as history, [B, P] int64 and the count per row
+        if G:
+            hd0 = D // layers[0].self_attn.num_heads
+            if not ops.spec_attn_ok(dtype, hd0, Tmax, G + 1):
+                why = (f"fp32 parameters ({dtype})" if dtype not in (torch.bfloat16, torch.float16) else
+                       f"ops.spec_attn_ok is false for head size {hd0}, {Tmax} positions and {G + 1} rows")
+                raise ValueError(f"generate(prompt_lookup_num_tokens={G}): {why}: the multi-row step attention is not built "
+                                 "for it")
+            if input_ids is not None:
+                look_hist = input_ids.to(dev).long()
+                if look_hist.dim() != 2 or look_hist.shape[0] != B:
+                    raise ValueError(f"generate: input_ids should be [{B}, P] as the lookup history, but is "
+                                     f"{tuple(look_hist.shape)}")
+                look_hist = look_hist.contiguous()
+                look_len = torch.full((B,), look_hist.shape[1], dtype=torch.int32, device=dev)
         if ragged is not None:
             hd0 = D // layers[0].self_attn.num_heads
             if not ops.decode_attn_ok(dtype, hd0, Tmax):
@@ -930,7 +1054,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         w8 = None                 # decode_weights="fp8" / "mxfp4": per layer the copies of q|k|v, o, gate|up, down
         if decode_weights is not None:
-            probe = torch.empty((B * K, 0), dtype=dtype, device=dev)     # the token rows of a step
+            probe = torch.empty((B * K * (G + 1), 0), dtype=dtype, device=dev)     # the token rows of a step
 
             def q8(W, own):       # own: a stored parameter (version-keyed cache); else a merged copy of this call
                 if W is None or not ops.decode_linear_fp8_ok(probe, W):
@@ -954,7 +1078,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 w8.append((ql(ws.wqkv, own.wqkv), ql(ws.wo, own.wo), ql(ws.wgu, own.wgu), ql(ws.wd, own.wd)))
             w8_head = q8(self.lm_head.weight, self.lm_head.weight)
 
-        def run(x2, Sn, t0, pos=None, t_dev=None, beam=None):
+        def run(x2, Sn, t0, pos=None, t_dev=None, beam=None, spec=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
             for i, lyr in enumerate(layers):
@@ -968,7 +1092,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
                     lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
                     w8=w8[i] if w8 is not None and t_dev is not None else None,
-                    kv8=kvs[i] if kvs is not None else None, ragged=ragged, **({"beam": beam} if beam is not None else {}))
+                    kv8=kvs[i] if kvs is not None else None, ragged=ragged, **({"beam": beam} if beam is not None else {}),
+                    **({"spec": spec} if spec is not None else {}))
             return x2
 
         if ragged is not None:    # prefill over the padded rows; token 0 comes from each sample's last valid row
@@ -979,6 +1104,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             last = torch.empty((B, D), dtype=dtype, device=dev)
             ops.copy2d(h, last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
         hd = D // layers[0].self_attn.num_heads
+        if G:
+            graph = decode_graph and max_new_tokens > 2 and not os.environ.get("MACAW_NO_DECODE_GRAPH")
+            ids, steps = self._generate_lookup(run, logits, last, emb_w, B, G, S0, max_new_tokens, eos_token_id, pad, dev,
+                                               max_matching_ngram_size, look_hist, look_len, graph)
+            return (ids, steps) if return_lookup_stats else ids
         if K > 1:
             graph = decode_graph and max_new_tokens > 2 and not os.environ.get("MACAW_NO_DECODE_GRAPH")
             return beam_out(*self._generate_beam(run, logits, last, emb_w, B, K, S0, max_new_tokens, eos_token_id, pad, dev,
@@ -1170,11 +1300,13 @@ class MM_LLMs(PreTrainedModel):
         if lora is not None:        # the adapters' dropout follows this model's step seeds (slot 41)
             lora.ext_seed = self._dropout_seed(lora.SLOT)
         if "inference" in inputs and inputs["inference"] is True:
+            # prompt lookup on: the text ids are the lookup history; off: exactly the call without it
+            look = dict(input_ids=inputs["input_ids"], **PROMPT_LOOKUP[0]) if PROMPT_LOOKUP[0]["prompt_lookup_num_tokens"] else {}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0],
-                                     **BEAM_SEARCH[0], **PROCESSORS[0])
+                                     **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1244,6 +1376,15 @@ class MM_LLMs(PreTrainedModel):
         _processors_check("set_logits_processors", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         PROCESSORS[0] = dict(repetition_penalty=float(repetition_penalty), no_repeat_ngram_size=int(no_repeat_ngram_size),
                              min_new_tokens=int(min_new_tokens))
+
+    @staticmethod
+    def set_prompt_lookup(num_tokens=None, max_matching_ngram_size=2):
+        """Prompt-lookup speculative decoding for `inputs["inference"] = True` (LlamaForCausalLM.generate's
+        prompt_lookup_num_tokens and max_matching_ngram_size): off (None or 0) by default.  With it on, forward hands its
+        text input_ids to generate() as the lookup history.  Validated here; what depends on the call (batch, sampling,
+        beams, processors, cache format, mask) is validated by generate().  No arguments: back to the default."""
+        G = _lookup_check("set_prompt_lookup", num_tokens, max_matching_ngram_size)
+        PROMPT_LOOKUP[0] = dict(prompt_lookup_num_tokens=G or None, max_matching_ngram_size=int(max_matching_ngram_size))
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

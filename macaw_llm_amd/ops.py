@@ -828,6 +828,92 @@ def beam_emit(logits, V, K_in, pad, eos, length_penalty, early_stopping, bs: Bea
                               dt(logits), _st()), "mk_beam_emit")
 
 
+SPEC_MAX_Q = 16
+
+
+def spec_attn_ok(dtype, hd, t_max, Q):
+    """mk_decode_step_attn_multi's domain: bf16 / fp16, hd in {16, 32, 64, 128}, 1 <= Q <= 16 rows per sample.  The
+    kernel keeps no per-key buffer in LDS, so any t_max >= 1 is inside"""
+    return dtype in (torch.bfloat16, torch.float16) and hd in (16, 32, 64, 128) and 1 <= Q <= SPEC_MAX_Q and t_max >= 1
+
+
+def decode_step_attn_multi(q, k_new, v_new, in_bs, cos_t, sin_t, cache, pos, t_max, B, Q, H, hd, out, scale,
+                           q_off=0, k_off=0, v_off=0):
+    """decode_step_attn for the B * Q rows of a prompt-lookup verify step (see mk_decode_step_attn_multi): row b * Q + g
+    of q / k_new / v_new (row stride in_bs; slices of one fused [B * Q, 3D] buffer through the element offsets) runs at
+    position pos[b] + g (pos int32 [B] on the device): RoPE, append to row pos[b] + g of cache [B, t_max, 2 * H * hd],
+    attention over keys 0 ... pos[b] + g.  out [B * Q, H * hd].  Bit-identical per row to decode_step_attn at that
+    position; one launch, one workgroup per (head, sample, row)"""
+    lib = _L.load()
+    es = q.element_size()
+    D = H * hd
+    if cache.dtype != q.dtype or tuple(cache.shape) != (B, t_max, 2 * D) or not cache.is_contiguous():
+        raise MacawHipError(f"decode_step_attn_multi: cache {cache.dtype} {tuple(cache.shape)}; expected {q.dtype} "
+                            f"{(B, t_max, 2 * D)}, contiguous")
+    if pos.dtype != torch.int32 or pos.numel() != B or not pos.is_contiguous():
+        raise MacawHipError(f"decode_step_attn_multi: pos {pos.dtype} {tuple(pos.shape)}; expected contiguous int32 [{B}]")
+    if out.shape[0] != B * Q or q.shape[0] != B * Q:
+        raise MacawHipError(f"decode_step_attn_multi: {q.shape[0]} input and {out.shape[0]} output rows for B * Q = {B * Q}")
+    _L.check(lib.mk_decode_step_attn_multi(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es, in_bs,
+                                           _p(cos_t), _p(sin_t), _p(cache), _p(cache) + D * es, 2 * D, t_max * 2 * D,
+                                           _p(out), _rowmajor(out), _p(pos), t_max, B, Q, H, hd, scale, dt(q), _st()),
+             "mk_decode_step_attn_multi")
+    return out
+
+
+class SpecState:
+    """the per-sample device state of prompt-lookup decoding (include/macaw_hip.h, "Per-sample state"): B samples, G
+    draft tokens (Q = G + 1 rows per sample and step), n_max = max_new_tokens output columns.  pos starts at 0: the loop
+    sets it to S0 - 1 in front of token 0"""
+
+    def __init__(self, B, G, n_max, pad, device):
+        self.B, self.G, self.Q, self.n_max, self.pad = B, G, G + 1, n_max, pad
+        self.pos = torch.zeros(B, dtype=torch.int32, device=device)
+        self.n_out = torch.zeros(B, dtype=torch.int32, device=device)
+        self.done = torch.zeros(B, dtype=torch.bool, device=device)
+        self.out = torch.full((B, n_max), pad, dtype=torch.long, device=device)
+        self.tok = torch.full((B, G + 1), pad, dtype=torch.long, device=device)
+        self.n_draft = torch.zeros(B, dtype=torch.int32, device=device)
+        self.steps = torch.zeros(B, dtype=torch.int32, device=device)
+
+
+def spec_lookup(ss: SpecState, V, max_matching_ngram_size, eos, prompt=None, prompt_len=None):
+    """the draft of a prompt-lookup step for every sample in one launch (see mk_spec_lookup): the history of sample b is
+    prompt[b, :prompt_len[b]] (int64 [B, P] and int32 [B], or None) followed by ss.out[b, :ss.n_out[b]].  Writes
+    ss.tok[:, 1:] (pad behind the draft) and ss.n_draft; eos None or negative never matches"""
+    lib = _L.load()
+    B = ss.B
+    P = p_ld = 0
+    if prompt is not None:
+        if (prompt.dtype != torch.int64 or prompt.dim() != 2 or prompt.shape[0] != B
+                or (prompt.shape[1] > 1 and prompt.stride(1) != 1)):
+            raise MacawHipError(f"spec_lookup: prompt {prompt.dtype} {tuple(prompt.shape)} {prompt.stride()}; expected "
+                                f"row-major int64 [{B}, P]")
+        if (prompt_len is None or prompt_len.dtype != torch.int32 or prompt_len.numel() != B
+                or not prompt_len.is_contiguous()):
+            raise MacawHipError(f"spec_lookup: prompt_len must be a contiguous int32 [{B}] next to a prompt")
+        P, p_ld = prompt.shape[1], max(prompt.stride(0), prompt.shape[1])
+    _L.check(lib.mk_spec_lookup(_p(prompt), p_ld, P, _p(prompt_len) if prompt is not None else None, _p(ss.out),
+                                max(ss.out.stride(0), ss.n_max), ss.n_max, _p(ss.n_out), _p(ss.done), _p(ss.tok),
+                                _p(ss.n_draft), B, ss.G, min(int(max_matching_ngram_size), 2 ** 31 - 1), V, ss.pad,
+                                -1 if eos is None else int(eos), _st()), "mk_spec_lookup")
+
+
+def spec_verify_emit(logits, V, eos, ss: SpecState):
+    """verify the draft against the step's logits and emit, for every sample in one launch (see mk_spec_verify_emit):
+    logits [B * R, >= V] row-major with R = ss.Q rows per sample, or R = 1 for token 0 (the prefill's rows, no draft).
+    Updates ss (out, n_out, pos, steps, done, tok[:, 0]) in place"""
+    lib = _L.load()
+    B = ss.B
+    R = logits.shape[0] // B
+    if logits.shape[0] != B * R or R not in (1, ss.Q):
+        raise MacawHipError(f"spec_verify_emit: {logits.shape[0]} rows of logits for B = {B}, Q = {ss.Q}")
+    _L.check(lib.mk_spec_verify_emit(_p(logits), _rowmajor(logits), V, B, R, ss.Q, -1 if eos is None else int(eos),
+                                     _p(ss.tok), _p(ss.n_draft), _p(ss.pos), _p(ss.n_out), _p(ss.done), _p(ss.out),
+                                     max(ss.out.stride(0), ss.n_max), ss.n_max, _p(ss.steps), dt(logits), _st()),
+             "mk_spec_verify_emit")
+
+
 def kv8_cache(B, t_max, H, hd, device):
     """an empty e4m3 KV cache in the one format of include/macaw_hip.h: (bytes uint8 [B, t_max, 2 * H * hd] =
     [keys of all heads | values of all heads] per position, scales f32 [B, t_max, 2 * H])"""

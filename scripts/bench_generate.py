@@ -38,6 +38,12 @@ with torch.no_grad():
 # same way: ms per token of every run, the medians, their difference and the greedy run-to-run spread (the difference counts
 # only beyond it), then the stand-alone time of one ops.logits_process launch against ops.decode_emit on [B, 32000] logits
 # with a history of 200 prompt + 100 generated ids
+#        bench_generate.py --lookup-ab [--reps R]: greedy against prompt_lookup_num_tokens=7 (prompt-lookup speculative decoding)
+# at batch 1, alternated the same way, over two histories: "accepting" = the greedy output itself handed in as input_ids (the
+# drafts are the answer: an upper bound) and "cold" = no input_ids (the history is the generated tokens only: the price of the
+# 8-row verify step wherever the output does not repeat itself).  ms per EMITTED token of every run, tokens per verify step,
+# the medians, lookup / greedy and the run-to-run spread of each arm
+LOOKUP = "--lookup-ab" in sys.argv
 AB = "--fp8-ab" in sys.argv
 PROC = "--processors-ab" in sys.argv
 BEAM = "--beam-ab" in sys.argv
@@ -49,7 +55,38 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if LOOKUP:
+    G = 7
+    inp = synthetic_inputs(cfg, 1, 128, modalities=("images", "audios"), seed=2, device=dev)
+    with torch.no_grad():
+        emb = model.prepare_inputs_for_generation(inp)[0]
+        y = model.llm.generate(inputs_embeds=emb, max_new_tokens=72, eos_token_id=-1)
+        print(f"greedy output: {len(set(y[0].tolist()))} distinct ids among {y.shape[1]}", flush=True)
+        arms = {"greedy": {}, "cold": dict(prompt_lookup_num_tokens=G), "accepting": dict(prompt_lookup_num_tokens=G, input_ids=y)}
+        ms, tps = {a: [] for a in arms}, {a: [] for a in arms}
+        for kw in arms.values():                    # untimed: each arm's first call
+            model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=-1, **kw)
+        for rep in range(REPS):
+            for arm, kw in arms.items():
+                t, st = {}, {}
+                for new in (8, 72):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    out = model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, return_lookup_stats=arm != "greedy", **kw)
+                    torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ids, st[new] = (out[0], int(out[1][0])) if arm != "greedy" else (out, new)
+                    assert ids.shape[1] == new
+                ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                tps[arm].append(64 / max(st[72] - st[8], 1))
+                print(f"B= 1 rep {rep} {arm:9s}: {ms[arm][-1]:6.3f} ms per emitted token, {tps[arm][-1]:5.2f} tokens per step "
+                      f"({st[72]} steps for 72 tokens)", flush=True)
+    med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+    for arm in arms:
+        sp = max(ms[arm]) - min(ms[arm])
+        print(f"B= 1 G={G}: {arm:9s} {med[arm]:6.3f} ms per emitted token ({arm} / greedy = {med[arm] / med['greedy']:5.3f}), "
+              f"{sorted(tps[arm])[len(tps[arm]) // 2]:5.2f} tokens per step, ms per step {med[arm] * sorted(tps[arm])[len(tps[arm]) // 2]:6.3f}, "
+              f"run-to-run spread {sp * 1e3:6.1f} us ({sp / med[arm] * 100:4.1f} %)", flush=True)
+    sys.exit(0)
 if BEAM:
     from macaw_llm_amd import ops
     for B, K in ((1, 4), (8, 4), (2, 16)):
