@@ -113,6 +113,118 @@ def _lookup_check(where, num_tokens, max_matching_ngram_size):
     return int(num_tokens)
 
 
+# ---------------------------------------------------------------- the helpers of generate()'s decode loops -----
+_16BIT = (torch.bfloat16, torch.float16)
+
+
+def _no_decode_graph(decode_graph, max_new_tokens):
+    """why generate() does not capture its decode step in a hipGraph; None: it does"""
+    if not decode_graph:
+        return "decode_graph=False selects the eager decode loop"
+    if os.environ.get("MACAW_NO_DECODE_GRAPH"):
+        return "MACAW_NO_DECODE_GRAPH selects the eager decode loop"
+    if max_new_tokens <= 2:
+        return f"max_new_tokens={max_new_tokens} <= 2: no decode step is captured"
+    return None
+
+
+def _attn_refusal(dtype, hd, positions, rows=None):
+    """the clause that names why a step attention kernel does not take a call -- ops.decode_attn_ok, or with rows (the
+    token rows per sample of a verify step) ops.spec_attn_ok; None: it does"""
+    if rows is None:
+        ok = ops.decode_attn_ok(dtype, hd, positions)
+        what = f"ops.decode_attn_ok is false for head size {hd} and {positions} positions"
+    else:
+        ok = ops.spec_attn_ok(dtype, hd, positions, rows)
+        what = f"ops.spec_attn_ok is false for head size {hd}, {positions} positions and {rows} rows"
+    return None if ok else f"fp32 parameters ({dtype})" if dtype not in _16BIT else what
+
+
+def _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, switch="decode_weights", value="fp8", beams=1):
+    """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
+    what keeps a call off that path instead of decoding it in 16 bits (no_graph: _no_decode_graph's answer).  The limit
+    of 32 sequences belongs to the weight-streaming step (switch="decode_weights", value "fp8" or "mxfp4"); the e4m3
+    cache takes any batch."""
+    why = None
+    attn = _attn_refusal(dtype, hd, S0 + max_new_tokens)
+    if dtype not in _16BIT:
+        why = f"{attn}: the decode kernels stream bf16 / fp16 tokens"
+    elif not use_cache:
+        why = ("use_cache=False recomputes the prefix with the 16-bit weights" if switch == "decode_weights" else
+               "use_cache=False keeps no KV cache")
+    elif no_graph is not None:
+        why = no_graph
+    elif B * beams > 32 and switch == "decode_weights" and beams > 1:
+        why = (f"B x num_beams = {B} x {beams} = {B * beams} rows: the weight-streaming decode step takes at most 32 "
+               "(B * K <= 32)")
+    elif B > 32 and switch == "decode_weights":
+        why = f"{B} sequences: the weight-streaming decode step takes at most 32"
+    elif attn is not None:
+        why = f"{attn}: the eager decode loop would run"
+    if why is not None:
+        raise ValueError(f"generate({switch}='{value}'): {why}")
+
+
+def _prompt_history(input_ids, B, dev, what, ragged=None):
+    """the prompt's ids as the history in front of the generated tokens -> (hist int64 [B, P], count int32 [B]).  `what`
+    names the user in the refusal of another shape.  ragged (a padded batch): only the valid ids, in order, as the sample
+    alone would hold them"""
+    hist = input_ids.to(dev).long()
+    if hist.dim() != 2 or hist.shape[0] != B:
+        raise ValueError(f"generate: input_ids should be [{B}, P] as {what}, but is {tuple(hist.shape)}")
+    if ragged is None:
+        return hist.contiguous(), torch.full((B,), hist.shape[1], dtype=torch.int32, device=dev)
+    S0 = ragged.kmask.shape[1]
+    if hist.shape[1] != S0:
+        raise ValueError(f"generate: input_ids should be of size {(B, S0)} next to a padded attention_mask, but is "
+                         f"{tuple(hist.shape)}")
+    valid = ragged.kmask != 0
+    slot = torch.where(valid, ragged.slot, torch.full_like(ragged.slot, S0)).long()
+    hist = torch.zeros((B, S0 + 1), dtype=torch.long, device=dev).scatter_(1, slot, hist)[:, :S0]
+    return hist.contiguous(), valid.sum(1).to(torch.int32).contiguous()
+
+
+def _decode_steps(step, done, n_steps, graph):
+    """Run step() -- the launches of one decode step, every input and output in device memory -- until n_steps have run
+    or every flag of `done` (bool, on the device) is set; returns the steps run.  graph: one step runs eagerly (it sets
+    kernel attributes, allocator pools and the workspace), the next is captured in a hipGraph and replayed, and the host
+    reads the flags only before those two and after every 8th replay, so up to 7 steps may run past the end (their
+    emits write pad).  Otherwise the host reads the flags before every step.  Each read is a device synchronisation."""
+    ran = 0
+    if not graph:
+        while ran < n_steps and not bool(done.all()):
+            step()
+            ran += 1
+        return ran
+    if ran < n_steps and not bool(done.all()):
+        step()
+        ran += 1
+    if ran < n_steps and not bool(done.all()):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            step()
+        for i in range(n_steps - ran):
+            g.replay()
+            ran += 1
+            if (i & 7) == 7 and bool(done.all()):
+                break
+    return ran
+
+
+def _append_column(emb, emb_w, ids, src=None):
+    """use_cache=False: the prefixes emb [R, S, D] grown by the embedding of the new ids [R'] -> [R', S + 1, D].  Row r
+    continues row src[r] of emb (a beam continues its parent); None: row r, R' = R"""
+    S, D = emb.shape[1:]
+    R = ids.shape[0]
+    nemb = torch.empty((R, S + 1, D), dtype=emb.dtype, device=emb.device)
+    if src is None:
+        ops.copy2d(emb, nemb, S, D, D, D, batch=R, s_src=S * D, s_dst=(S + 1) * D)
+    else:
+        nemb[:, :S] = emb.index_select(0, src)
+    ops.copy2d(ops.embedding_fwd(emb_w, ids), nemb, 1, D, D, D, batch=R, s_src=D, s_dst=(S + 1) * D, dst_off=S * D)
+    return nemb
+
+
 def _rows_view(ts):
     """tensor [sum rows, ...] aliasing `ts` if they lie back to back in one storage, else None"""
     t0 = ts[0]
@@ -513,6 +625,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None,
                                       hidden_states=None, attentions=None)
 
+    # The three decode loops on device state.  Each is its state, its emit and its step closure: token 0 comes from the
+    # prefill's rows, then _decode_steps runs the step max_new_tokens - 1 times at the most -- with graph captured once
+    # after one eager step and replayed, the host looking at the done flags every 8 steps; otherwise kernel by kernel, the
+    # host looking before every step.
     @torch.no_grad()
     def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
@@ -544,22 +660,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         emit(last)                       # token 0 (from the prefill) ...
         state[0] = S0                    # ... is the one fed at position S0
-        emitted = 1
-        if not bool(done.all()):
-            step()                       # token 1: eager (kernel attributes, allocator pools, workspace)
-            emitted += 1
-        remaining = max_new_tokens - emitted
-        if remaining > 0 and not bool(done.all()):
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                step()
-            for i in range(remaining):
-                graph.replay()
-                emitted += 1
-                if (i & 7) == 7 and bool(done.all()):
-                    break
-            del graph
-        res = out_buf[:, :emitted]
+        res = out_buf[:, :1 + _decode_steps(step, done, max_new_tokens - 1, True)]
         # the eager loop stops right after the token at which every sample has finished
         fin = ((res == eos).cumsum(1) > 0).all(0)
         if bool(fin.any()):
@@ -569,12 +670,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     @torch.no_grad()
     def _generate_beam(self, run, logits, last, emb_w, B, K, S0, max_new_tokens, eos, pad, dev, length_penalty,
                        early_stopping, graph):
-        """The beam-search decode loop (_generate_graph's, with ops.beam_emit in place of ops.decode_emit and the step's
-        B * K rows attending through the indirection table): token 0 from the prefill's B rows (K_in = 1), then one step
-        per token -- embedding of the K tokens per sample, the layers with engine.Beam, the lm_head, the emit.  graph:
-        the step is captured once after one eager step and replayed, the host looking at the done flags every 8 tokens;
-        otherwise the same launches run kernel by kernel and the host looks after every token.  Returns the device
-        books and the step state for generate's beam_out."""
+        """The beam-search decode loop (ops.beam_emit in place of ops.decode_emit, the step's B * K rows attending through
+        the indirection table): token 0 from the prefill's B rows (K_in = 1), then one step per token -- embedding of the
+        K tokens per sample, the layers with engine.Beam, the lm_head, the emit.  Returns the device books and the step
+        state for generate's beam_out."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         bs = ops.BeamState(B, K, max_new_tokens, pad, dev)
@@ -589,38 +688,18 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         emit(last, 1)                    # token 0 (from the prefill) ...
         state[0] = S0                    # ... is the one fed at position S0
-        emitted = 1
-        if not graph or max_new_tokens <= 2:     # no decode step would be captured
-            while emitted < max_new_tokens and not bool(bs.done.all()):
-                step()
-                emitted += 1
-            return bs, state
-        if not bool(bs.done.all()):
-            step()                       # token 1: eager (kernel attributes, allocator pools, workspace)
-            emitted += 1
-        remaining = max_new_tokens - emitted
-        if remaining > 0 and not bool(bs.done.all()):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                step()
-            for i in range(remaining):
-                g.replay()
-                if (i & 7) == 7 and bool(bs.done.all()):
-                    break
-            del g
+        _decode_steps(step, bs.done, max_new_tokens - 1, graph)
         return bs, state
 
     @torch.no_grad()
     def _generate_lookup(self, run, logits, last, emb_w, B, G, S0, max_new_tokens, eos, pad, dev, ngram, hist, hist_len,
                          graph):
-        """The prompt-lookup decode loop (_generate_graph's, with one VERIFY step of Q = G + 1 rows per sample in place of
-        the one-row step): token 0 from the prefill's B rows through ops.spec_verify_emit (one row per sample, no draft),
-        then per step ops.spec_lookup -> embedding of the [B, Q] ids -> the layers with engine.Spec -> the lm_head ->
-        ops.spec_verify_emit.  Position, count and done flag live per sample on the device (ops.SpecState).  graph: the
-        step is captured once after one eager step and replayed, the host looking at the done flags every 8 steps;
-        otherwise the same launches run kernel by kernel and the host looks after every step.  An unfinished sample emits
-        at least one token per step, so max_new_tokens - 1 steps behind token 0 always suffice.  Returns (ids [B, most
-        tokens of a sample], steps int32 [B])."""
+        """The prompt-lookup decode loop (one VERIFY step of Q = G + 1 rows per sample in place of the one-row step):
+        token 0 from the prefill's B rows through ops.spec_verify_emit (one row per sample, no draft), then per step
+        ops.spec_lookup -> embedding of the [B, Q] ids -> the layers with engine.Spec -> the lm_head ->
+        ops.spec_verify_emit.  Position, count and done flag live per sample on the device (ops.SpecState).  An unfinished
+        sample emits at least one token per step, so max_new_tokens - 1 steps behind token 0 always suffice.  Returns (ids
+        [B, most tokens of a sample], steps int32 [B])."""
         ss = ops.SpecState(B, G, max_new_tokens, pad, dev)
         ss.pos.fill_(S0 - 1)             # token 0 advances it to S0, the position its id is fed at
         spec = eng.Spec(ss.pos, G + 1)
@@ -634,56 +713,28 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             verify(run(ops.embedding_fwd(emb_w, ss.tok.view(-1)), G + 1, 0, pos=ss.pos, t_dev=ss.pos, spec=spec))
 
         verify(last)                     # token 0 (from the prefill)
-        if not graph or max_new_tokens <= 2:     # no decode step would be captured
-            for _ in range(max_new_tokens - 1):
-                if bool(ss.done.all()):
-                    break
-                step()
-        else:
-            if not bool(ss.done.all()):
-                step()                   # eager (kernel attributes, allocator pools, workspace)
-            remaining = max_new_tokens - 2
-            if remaining > 0 and not bool(ss.done.all()):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    step()
-                for i in range(remaining):
-                    g.replay()
-                    if (i & 7) == 7 and bool(ss.done.all()):
-                        break
-                del g
+        _decode_steps(step, ss.done, max_new_tokens - 1, graph)
         width = int(ss.n_out.max())      # pad behind each sample's end; the column at which every sample has finished
         return ss.out[:, :width].clone(), ss.steps.clone()
 
-    def _decode_fp8_check(self, dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="decode_weights",
-                          value="fp8", beams=1):
-        """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
-        what keeps a call off that path instead of decoding it in 16 bits.  The limit of 32 sequences belongs to the
-        weight-streaming step (switch="decode_weights", value "fp8" or "mxfp4"); the e4m3 cache takes any batch."""
-        why = None
-        a0 = self.model.layers[0].self_attn
-        hd = self.config.hidden_size // a0.num_heads
-        if dtype not in (torch.bfloat16, torch.float16):
-            why = f"fp32 parameters ({dtype}): the decode kernels stream bf16 / fp16 tokens"
-        elif not use_cache:
-            why = ("use_cache=False recomputes the prefix with the 16-bit weights" if switch == "decode_weights" else
-                   "use_cache=False keeps no KV cache")
-        elif not decode_graph:
-            why = "decode_graph=False selects the eager decode loop"
-        elif os.environ.get("MACAW_NO_DECODE_GRAPH"):
-            why = "MACAW_NO_DECODE_GRAPH selects the eager decode loop"
-        elif max_new_tokens <= 2:
-            why = f"max_new_tokens={max_new_tokens} <= 2: no decode step is captured"
-        elif B * beams > 32 and switch == "decode_weights" and beams > 1:
-            why = (f"B x num_beams = {B} x {beams} = {B * beams} rows: the weight-streaming decode step takes at most 32 "
-                   "(B * K <= 32)")
-        elif B > 32 and switch == "decode_weights":
-            why = f"{B} sequences: the weight-streaming decode step takes at most 32"
-        elif not ops.decode_attn_ok(dtype, hd, S0 + max_new_tokens):
-            why = (f"ops.decode_attn_ok is false for head size {hd} and {S0 + max_new_tokens} positions: the eager "
-                   "decode loop would run")
-        if why is not None:
-            raise ValueError(f"generate({switch}='{value}'): {why}")
+    def _hidden_last(self, emb, mask=None, last_valid=None):
+        """use_cache=False: the whole prefix emb [R, S, D] through the layers, the final norm left to the lm_head, ->
+        the hidden rows [R, D] that predict the next token: the last row of every sample, or (last_valid: the flat
+        indices of a padded prompt's last valid rows) those rows.  mask [R, S]: the key mask of a padded batch"""
+        R, S, D = emb.shape
+        self.model._defer_final_norm = True
+        try:
+            if mask is not None:
+                h = self.model(inputs_embeds=emb, attention_mask=mask, position_ids=(mask.cumsum(1) - 1).clamp_(min=0))
+            else:
+                h = self.model(inputs_embeds=emb)
+        finally:
+            self.model._defer_final_norm = False
+        if last_valid is not None:
+            return ops.embedding_fwd(h.contiguous().view(R * S, D), last_valid)
+        last = torch.empty((R, D), dtype=emb.dtype, device=emb.device)
+        ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=R, s_src=S * D, s_dst=D, src_off=(S - 1) * D)
+        return last
 
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
@@ -819,6 +870,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         B * (G + 1) > 32, num_beams > 1, do_sample=True, any logits processor, kv_cache="fp8", a padded attention_mask,
         use_cache=False, fp32 parameters and a shape outside ops.spec_attn_ok: none of these combinations is built.  None
         or 0 (default): today's path, not one launch different."""
+        # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         if proc is not None and K > 1:
@@ -832,7 +884,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if kv_cache not in (None, "fp8"):
             raise ValueError(f"generate: kv_cache must be None or 'fp8', got {kv_cache!r}")
         G = _lookup_check("generate", prompt_lookup_num_tokens, max_matching_ngram_size)
-        if G:                     # what prompt lookup does not compose with, before the model is touched
+        if G:                     # what prompt lookup does not compose with
             rows_of = inputs_embeds if inputs_embeds is not None else input_ids
             why = None
             if K > 1:
@@ -851,7 +903,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             elif rows_of.shape[0] * (G + 1) > 32:
                 why = (f"B x (G + 1) = {rows_of.shape[0]} x {G + 1} = {rows_of.shape[0] * (G + 1)} rows: a verify step takes "
                        "at most 32 (B * Q <= 32; a wider step is not built)")
-            elif inputs_embeds is not None and inputs_embeds.dtype not in (torch.bfloat16, torch.float16):
+            elif inputs_embeds is not None and inputs_embeds.dtype not in _16BIT:
                 why = (f"fp32 parameters ({inputs_embeds.dtype}): the multi-row step attention takes bf16 / fp16 (not built "
                        "for fp32)")
             if why is not None:
@@ -862,6 +914,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
             sample = (temperature, top_k, top_p, int(seed))
+        no_graph = _no_decode_graph(decode_graph, max_new_tokens)
+        graph = no_graph is None  # the decode step is captured in a hipGraph (the greedy loop also needs decode_attn_ok)
+
         emb_w = self.model.embed_tokens.weight
         if inputs_embeds is None:
             inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(*input_ids.shape, -1)
@@ -869,53 +924,52 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         B, S0, D = inputs_embeds.shape
         dev, dtype = inputs_embeds.device, inputs_embeds.dtype
         pad = pad_token_id if pad_token_id is not None else (eos_token_id or 0)
-        done = torch.zeros(B, dtype=torch.bool, device=dev)
         eps = self.model.norm.variance_epsilon
+        layers = self.model.layers
+        V = self.lm_head.weight.shape[0]
+        hd = D // layers[0].self_attn.num_heads
+        Tmax = S0 + max_new_tokens + G        # rows of the KV cache (prompt lookup: the G draft rows behind the last token)
+
+        # ---- refusals (b): what needs the shapes, the dtype, the head size or the mask, before anything is allocated
         # a padded batch: engine.Ragged, the prefill's positions, the flat index of each sample's last valid row
         ragged = rg_pos = rg_last = None
         if attention_mask is not None:
             padded = eng.ragged_from_mask(attention_mask.to(dev), B, S0)        # None for a mask without a zero
             if padded is not None:
                 ragged, rg_pos, rg_last = padded
-        V = self.lm_head.weight.shape[0]
-        out = []
+        hist = hist_len = None    # the prompt's ids as history (the processors' or the lookup's): [B, P] int64, count per row
+        if proc is not None and input_ids is not None:
+            hist, hist_len = _prompt_history(input_ids, B, dev, "the processors' prompt history", ragged)
+        if K > 1:
+            beam_check("generate", K, num_return_sequences, V, do_sample, kv_cache, ragged is not None, length_penalty)
+            why = _attn_refusal(dtype, hd, S0 + max_new_tokens) if use_cache else None
+            if why is not None:
+                raise ValueError(f"generate(num_beams={K}) with use_cache=True: {why}; the beam step attention takes bf16 / "
+                                 "fp16 inside ops.decode_attn_ok: pass use_cache=False")
+        if decode_weights is not None:
+            _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, value=decode_weights, beams=K)
+        if kv_cache == "fp8":
+            _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, switch="kv_cache")
+        if G:
+            why = _attn_refusal(dtype, hd, Tmax, G + 1)
+            if why is not None:
+                raise ValueError(f"generate(prompt_lookup_num_tokens={G}): {why}: the multi-row step attention is not built "
+                                 "for it")
+            if input_ids is not None:
+                hist, hist_len = _prompt_history(input_ids, B, dev, "the lookup history")
+        if ragged is not None and use_cache:
+            why = _attn_refusal(dtype, hd, Tmax)
+            if why is not None:
+                raise ValueError(f"generate(attention_mask=) with a padded mask and use_cache=True: {why}; the "
+                                 "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
+                                 "there is no masked attention over a cache: pass use_cache=False")
+
         process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add)
         if proc is not None:
-            hist = hist_len = None    # the prompt's ids as history: [B, P] int64 and the count per row
-            if input_ids is not None:
-                hist = input_ids.to(dev).long()
-                if hist.dim() != 2 or hist.shape[0] != B:
-                    raise ValueError(f"generate: input_ids should be [{B}, P] as the processors' prompt history, but is "
-                                     f"{tuple(hist.shape)}")
-                if ragged is not None:    # only the valid ids, in order, as the sample alone would hold them
-                    if hist.shape[1] != S0:
-                        raise ValueError(f"generate: input_ids should be of size {(B, S0)} next to a padded "
-                                         f"attention_mask, but is {tuple(hist.shape)}")
-                    valid = ragged.kmask != 0
-                    slot = torch.where(valid, ragged.slot, torch.full_like(ragged.slot, S0)).long()
-                    hist = torch.zeros((B, S0 + 1), dtype=torch.long, device=dev).scatter_(1, slot, hist)[:, :S0]
-                    hist_len = valid.sum(1).to(torch.int32).contiguous()
-                else:
-                    hist_len = torch.full((B,), hist.shape[1], dtype=torch.int32, device=dev)
-                hist = hist.contiguous()
-
             def process(lg, gen, n_dev=None, n_add=0):
                 ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
 
             gen_buf = torch.full((B, max_new_tokens), pad, dtype=torch.long, device=dev)   # the eager loops' ids so far
-        if K > 1:
-            beam_check("generate", K, num_return_sequences, V, do_sample, kv_cache, ragged is not None, length_penalty)
-            hd0 = D // self.model.layers[0].self_attn.num_heads
-            if use_cache and not ops.decode_attn_ok(dtype, hd0, S0 + max_new_tokens):
-                why = (f"fp32 parameters ({dtype})" if dtype not in (torch.bfloat16, torch.float16) else
-                       f"ops.decode_attn_ok is false for head size {hd0} and {S0 + max_new_tokens} positions")
-                raise ValueError(f"generate(num_beams={K}) with use_cache=True: {why}; the beam step attention takes bf16 / "
-                                 "fp16 inside ops.decode_attn_ok: pass use_cache=False")
-
-        if decode_weights is not None:
-            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, value=decode_weights, beams=K)
-        if kv_cache == "fp8":
-            self._decode_fp8_check(dtype, B, S0, max_new_tokens, use_cache, decode_graph, switch="kv_cache")
         w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
 
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
@@ -924,13 +978,16 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
             return ops.linear_fwd(y, self.lm_head.weight)
 
-        def select(h_last, t):    # h_last [B, D] -> ids [B] of new token t
+        def select(h_last, t, done):  # h_last [B, D] -> ids [B] of new token t (pad where done), the flags behind it
+            pads = torch.full((B,), pad, dtype=torch.long, device=dev)
             lg = logits(h_last)
             if process is not None:
                 process(lg, gen_buf, n_add=t)
-            if sample is not None:
-                return ops.sample_rows(lg, V, *sample, step=t)
-            return ops.argmax_rows(lg, V)
+            ids = ops.sample_rows(lg, V, *sample, step=t) if sample is not None else ops.argmax_rows(lg, V)
+            nxt = torch.where(done, pads, ids)
+            if gen_buf is not None:
+                gen_buf[:, t] = nxt
+            return nxt, done | (nxt == eos_token_id)
 
         def beam_out(bs, state):      # the books after the loop -> what generate returns
             n_cols = int(state[1])
@@ -943,95 +1000,37 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)
             bs = ops.BeamState(B, K, max_new_tokens, pad, dev)
             emb = inputs_embeds.contiguous()
-            base = torch.arange(B, device=dev).repeat_interleave(K) * K
+            own = torch.arange(B, device=dev).repeat_interleave(K)      # the sample of row (b, j) ...
+            base = own * K                                              # ... and the row of its beam 0
             for t in range(max_new_tokens):
-                R, S = emb.shape[0], emb.shape[1]
-                self.model._defer_final_norm = True
-                try:
-                    h = self.model(inputs_embeds=emb)
-                finally:
-                    self.model._defer_final_norm = False
-                last = torch.empty((R, D), dtype=dtype, device=dev)
-                ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=R, s_src=S * D, s_dst=D, src_off=(S - 1) * D)
-                ops.beam_emit(logits(last), V, 1 if t == 0 else K, pad, eos_token_id, length_penalty, early_stopping, bs, state)
+                ops.beam_emit(logits(self._hidden_last(emb)), V, 1 if t == 0 else K, pad, eos_token_id, length_penalty,
+                              early_stopping, bs, state)
                 if t + 1 == max_new_tokens or bool(bs.done.all()):
                     break
                 # row (b, j) continues the prefix of its parent (b, parent[j]) with its new token
-                src = (base + bs.hist[t, :, :, 1].reshape(-1).long()) if t > 0 else torch.arange(B, device=dev).repeat_interleave(K)
-                nemb = torch.empty((B * K, S + 1, D), dtype=dtype, device=dev)
-                nemb[:, :S] = emb.index_select(0, src)
-                ops.copy2d(ops.embedding_fwd(emb_w, bs.tok), nemb, 1, D, D, D, batch=B * K, s_src=D, s_dst=(S + 1) * D,
-                           dst_off=S * D)
-                emb = nemb
+                emb = _append_column(emb, emb_w, bs.tok, base + bs.hist[t, :, :, 1].reshape(-1).long() if t > 0 else own)
             return beam_out(bs, state)
 
         if not use_cache:
             emb = inputs_embeds.contiguous()
             mask = ragged.kmask if ragged is not None else None        # grows by a one per new token
+            done, out = torch.zeros(B, dtype=torch.bool, device=dev), []
             for t in range(max_new_tokens):
-                S = emb.shape[1]
-                self.model._defer_final_norm = True
-                try:
-                    if mask is not None:
-                        h = self.model(inputs_embeds=emb, attention_mask=mask,
-                                       position_ids=(mask.cumsum(1) - 1).clamp_(min=0))
-                    else:
-                        h = self.model(inputs_embeds=emb)
-                finally:
-                    self.model._defer_final_norm = False
-                if mask is not None and t == 0:         # token 0: predicted by each sample's last valid row
-                    last = ops.embedding_fwd(h.contiguous().view(B * S, D), rg_last)
-                else:
-                    last = torch.empty((B, D), dtype=dtype, device=dev)
-                    ops.copy2d(h.contiguous(), last, 1, D, D, D, batch=B, s_src=S * D, s_dst=D,
-                               src_off=(S - 1) * D)
-                nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
+                # under a mask token 0 is predicted by each sample's last valid row
+                nxt, done = select(self._hidden_last(emb, mask, rg_last if mask is not None and t == 0 else None), t, done)
                 out.append(nxt)
-                if gen_buf is not None:
-                    gen_buf[:, t] = nxt
-                done = done | (nxt == eos_token_id)
                 if bool(done.all()):
                     break
-                nemb = torch.empty((B, S + 1, D), dtype=dtype, device=dev)
-                ops.copy2d(emb, nemb, S, D, D, D, batch=B, s_src=S * D, s_dst=(S + 1) * D)
-                ops.copy2d(ops.embedding_fwd(emb_w, nxt.contiguous()), nemb, 1, D, D, D, batch=B,
-                           s_src=D, s_dst=(S + 1) * D, dst_off=S * D)
-                emb = nemb
+                emb = _append_column(emb, emb_w, nxt.contiguous())
                 if mask is not None:
                     mask = torch.cat([mask, torch.ones((B, 1), dtype=mask.dtype, device=dev)], dim=1)
             return torch.stack(out, dim=1)
 
-        Tmax = S0 + max_new_tokens + G        # (prompt lookup: the G draft rows behind the last token)
-        layers = self.model.layers
-        look_hist = look_len = None           # prompt lookup: the prompt's ids as history, [B, P] int64 and the count per row
-        if G:
-            hd0 = D // layers[0].self_attn.num_heads
-            if not ops.spec_attn_ok(dtype, hd0, Tmax, G + 1):
-                why = (f"fp32 parameters ({dtype})" if dtype not in (torch.bfloat16, torch.float16) else
-                       f"ops.spec_attn_ok is false for head size {hd0}, {Tmax} positions and {G + 1} rows")
-                raise ValueError(f"generate(prompt_lookup_num_tokens={G}): {why}: the multi-row step attention is not built "
-                                 "for it")
-            if input_ids is not None:
-                look_hist = input_ids.to(dev).long()
-                if look_hist.dim() != 2 or look_hist.shape[0] != B:
-                    raise ValueError(f"generate: input_ids should be [{B}, P] as the lookup history, but is "
-                                     f"{tuple(look_hist.shape)}")
-                look_hist = look_hist.contiguous()
-                look_len = torch.full((B,), look_hist.shape[1], dtype=torch.int32, device=dev)
-        if ragged is not None:
-            hd0 = D // layers[0].self_attn.num_heads
-            if not ops.decode_attn_ok(dtype, hd0, Tmax):
-                why = (f"fp32 parameters ({dtype})" if dtype not in (torch.bfloat16, torch.float16) else
-                       f"ops.decode_attn_ok is false for head size {hd0} and {Tmax} positions")
-                raise ValueError(f"generate(attention_mask=) with a padded mask and use_cache=True: {why}; the "
-                                 "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
-                                 "there is no masked attention over a cache: pass use_cache=False")
         rot = layers[0].self_attn.rotary_emb
         cos, sin = rot.tables(Tmax, dtype, dev)
         kvs = None                # kv_cache="fp8": per layer the f32 scales of the e4m3 cache (kvc: its bytes)
         if kv_cache == "fp8":
-            H0 = layers[0].self_attn.num_heads
-            kvc, kvs = zip(*(ops.kv8_cache(B, Tmax, H0, D // H0, dev) for _ in layers))
+            kvc, kvs = zip(*(ops.kv8_cache(B, Tmax, D // hd, hd, dev) for _ in layers))
         elif K > 1:               # one slot per beam; the prompt lives in slot 0 of its sample only
             kvc = [torch.empty((B, K, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]
         else:
@@ -1092,8 +1091,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
                     lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
                     w8=w8[i] if w8 is not None and t_dev is not None else None,
-                    kv8=kvs[i] if kvs is not None else None, ragged=ragged, **({"beam": beam} if beam is not None else {}),
-                    **({"spec": spec} if spec is not None else {}))
+                    kv8=kvs[i] if kvs is not None else None, ragged=ragged, beam=beam, spec=spec)
             return x2
 
         if ragged is not None:    # prefill over the padded rows; token 0 comes from each sample's last valid row
@@ -1103,27 +1101,22 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)             # prefill
             last = torch.empty((B, D), dtype=dtype, device=dev)
             ops.copy2d(h, last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
-        hd = D // layers[0].self_attn.num_heads
         if G:
-            graph = decode_graph and max_new_tokens > 2 and not os.environ.get("MACAW_NO_DECODE_GRAPH")
             ids, steps = self._generate_lookup(run, logits, last, emb_w, B, G, S0, max_new_tokens, eos_token_id, pad, dev,
-                                               max_matching_ngram_size, look_hist, look_len, graph)
+                                               max_matching_ngram_size, hist, hist_len, graph)
             return (ids, steps) if return_lookup_stats else ids
         if K > 1:
-            graph = decode_graph and max_new_tokens > 2 and not os.environ.get("MACAW_NO_DECODE_GRAPH")
             return beam_out(*self._generate_beam(run, logits, last, emb_w, B, K, S0, max_new_tokens, eos_token_id, pad, dev,
                                                  length_penalty, early_stopping, graph))
-        if (decode_graph and max_new_tokens > 2 and ops.decode_attn_ok(dtype, hd, Tmax)
-                and not os.environ.get("MACAW_NO_DECODE_GRAPH")):
+        if graph and ops.decode_attn_ok(dtype, hd, Tmax):
             return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample,
                                         process)
+        # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
+        done, out = torch.zeros(B, dtype=torch.bool, device=dev), []
         for t in range(max_new_tokens):
-            nxt = torch.where(done, torch.full((B,), pad, dtype=torch.long, device=dev), select(last, t))
+            nxt, done = select(last, t, done)
             out.append(nxt)
-            if gen_buf is not None:
-                gen_buf[:, t] = nxt
-            done = done | (nxt == eos_token_id)
             if t + 1 == max_new_tokens or bool(done.all()):
                 break
             x = ops.embedding_fwd(emb_w, nxt.contiguous())                 # [B, D]

@@ -236,26 +236,12 @@ def test_beam_check_raises_for_each_bad_value_and_ignores_everything_at_one_beam
 
 
 def test_decode_weights_limit_names_b_times_k():
-    class Cfg:
-        hidden_size = 128
-
-    class Attn:
-        num_heads = 2
-
-    class Layer:
-        self_attn = Attn()
-
-    class Fake:
-        config = Cfg()
-
-        class model:
-            layers = [Layer()]
-    chk = Mo.LlamaForCausalLM._decode_fp8_check
-    chk(Fake(), torch.bfloat16, 8, 5, 12, True, True, value="mxfp4", beams=4)          # 32 rows: inside
+    chk = Mo._decode_fp8_check          # (dtype, head size, B, S0, max_new_tokens, use_cache, why no graph is captured)
+    chk(torch.bfloat16, 64, 8, 5, 12, True, None, value="mxfp4", beams=4)              # 32 rows: inside
     with pytest.raises(ValueError, match=r"B x num_beams = 9 x 4 = 36"):
-        chk(Fake(), torch.bfloat16, 9, 5, 12, True, True, value="fp8", beams=4)
+        chk(torch.bfloat16, 64, 9, 5, 12, True, None, value="fp8", beams=4)
     with pytest.raises(ValueError, match="33 sequences"):                              # the greedy text is unchanged
-        chk(Fake(), torch.bfloat16, 33, 5, 12, True, True)
+        chk(torch.bfloat16, 64, 33, 5, 12, True, None)
 
 
 # ---------------------------------------------------------------------- 5. the launch sequence of a beam step --
@@ -419,13 +405,61 @@ def test_beam_loop_emits_once_from_the_prefill_then_runs_one_fixed_step_per_toke
     assert tuple(bs.pool_info.shape) == (B, K + 1, 4) and bs.ind.dtype == torch.int32
 
 
-def test_generate_keeps_the_greedy_path_for_one_beam_and_routes_the_rest():
-    src = inspect.getsource(Mo.LlamaForCausalLM.generate)
-    assert 'K = beam_check("generate", num_beams)' in src
-    # every beam branch is behind K > 1: with one beam not one line of them runs
-    assert src.count("if K > 1") >= 3 and "if not use_cache and K > 1" in src
-    loop = inspect.getsource(Mo.LlamaForCausalLM._generate_beam)
-    assert "(i & 7) == 7" in loop and "ops.beam_emit(" in loop and "eng.Beam(bs.ind, K, S0)" in loop
+def test_generate_keeps_the_greedy_path_for_one_beam_and_routes_the_rest(monkeypatch):
+    """with one beam not one launch or host read differs from the plain greedy call, whatever the other beam arguments
+    say; with more, every selection is ops.beam_emit and every step of the cached loops carries engine.Beam on the
+    emit's own table (the loop test above), on the graph path, on the loop and without a cache.  All of it is read off
+    generate()'s own launch log (tests/test_generate_trace_cpu.py), not off its source"""
+    import test_generate_trace_cpu as T
+    beams = dict(T.BEAMS)
+    for more in ({}, dict(decode_graph=False), dict(use_cache=False)):
+        with monkeypatch.context() as mp:
+            plain = T.run_trace_case(dict(N=12, finish=3, kw=more), mp)
+        with monkeypatch.context() as mp:
+            one = T.run_trace_case(dict(N=12, finish=3, kw={**beams, "num_beams": 1, **more}), mp)
+        assert one == plain
+        with monkeypatch.context() as mp:
+            log = T.run_trace_case(dict(N=12, finish=3, kw={**beams, **more}), mp)["log"]
+        names = [e if isinstance(e, str) else e[0] for e in log]
+        assert "beam_emit" in names and not {"decode_emit", "argmax_rows", "sample_rows"} & set(names)
+        steps = [e for e in log if e[0] == "llama_layer_cached" and e[3] == 1]         # (Sn = 1: behind the prefill)
+        assert all(e[-2][0] == "Beam" and e[-2][2:] == [beams["num_beams"], T.S0] for e in steps)
+        assert bool(steps) == more.get("use_cache", True)
+
+
+class _Flags:
+    """done flags that turn true once `after` replays have run; every host look at them is logged"""
+
+    def __init__(self, log, after):
+        self.log, self.after = log, after
+
+    def all(self):
+        self.log.append("read")
+        return self.log.count("replay") > self.after
+
+
+@pytest.mark.parametrize("r", [0, 7, 8])
+def test_decode_steps_captures_one_graph_and_reads_the_flags_after_every_eighth_replay(monkeypatch, r):
+    """the one loop driver under the three decode loops: one eager step, ONE captured step, then replays only, and a done
+    flag that turns true at replay r stops the loop after replay 8 * (r // 8) + 7 and not earlier"""
+    log = _FakeGraph.log = []
+    made = []
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", lambda: made.append(_FakeGraph()) or made[-1])
+    monkeypatch.setattr(torch.cuda, "graph", _FakeCapture)
+    ran = Mo._decode_steps(lambda: log.append("step"), _Flags(log, r), 40, True)
+    last = 8 * (r // 8) + 7
+    want = ["read", "step", "read", "capture{", "step", "}"]
+    for i in range(last + 1):
+        want += ["replay"] + (["read"] if (i & 7) == 7 else [])
+    assert log == want and ran == 1 + last + 1 and len(made) == 1
+    # the steps end with n_steps where no flag turns true, without a last look
+    log.clear()
+    assert Mo._decode_steps(lambda: log.append("step"), _Flags(log, 99), 12, True) == 12
+    assert log.count("replay") == 11 and log[-1] == "replay" and log.count("read") == 3
+    # without a graph: a look before every step, none behind the last
+    log.clear()
+    assert Mo._decode_steps(lambda: log.append("step"), _Flags(log, -1 if r else 99), 3, False) == (0 if r else 3)
+    assert log == (["read"] if r else ["read", "step"] * 3) and len(made) == 2
 
 
 # ------------------------------------------------------------- 6. the input generator of the GPU selection test --

@@ -231,11 +231,33 @@ def test_every_refusal_names_its_argument_and_the_defaults_raise_nothing():
     assert "repetition_penalty" not in inspect.getsource(beam)
 
 
-def test_the_processors_sit_in_front_of_every_selection():
-    graph = inspect.getsource(Mo.LlamaForCausalLM._generate_graph)
-    assert "process(lg, out_buf, state[1:2])" in graph
-    assert graph.index("process(lg, out_buf") < graph.index("ops.decode_emit_sample(lg") < graph.index("ops.decode_emit(lg")
-    gen = inspect.getsource(Mo.LlamaForCausalLM.generate)
-    sel = gen[gen.index("def select(h_last, t)"):]
-    assert sel.index("process(lg, gen_buf, n_add=t)") < sel.index("ops.sample_rows(lg") < sel.index("ops.argmax_rows(lg")
-    assert gen.count("gen_buf[:, t] = nxt") == 2                        # the use_cache=False loop and the cached loop
+def test_the_processors_sit_in_front_of_every_selection(monkeypatch):
+    for loop in ("graph", "cached", "nocache"):
+        for sampled in (False, True):
+            _processors_in_front(monkeypatch, loop, sampled)
+
+
+def _processors_in_front(monkeypatch, loop, sampled):
+    """read off generate()'s own launch log (tests/test_generate_trace_cpu.py): on the graph loop, the cached eager loop
+    and the use_cache=False loop every selection -- decode_emit / decode_emit_sample, argmax_rows / sample_rows -- has
+    ops.logits_process directly in front of it, on the same logits; the graph loop hands it the emit's output matrix
+    and the device's column counter, the eager loops the ids they have selected so far and the count from the host"""
+    import test_generate_trace_cpu as T
+    more = {"graph": {}, "cached": dict(decode_graph=False), "nocache": dict(use_cache=False)}[loop]
+    with monkeypatch.context() as mp:
+        got = T.run_trace_case(dict(N=12, finish=None, kw={**T.PROC, **(T.SAMPLE if sampled else {}), **more}), mp)
+    log = [e for e in got["log"] if not isinstance(e, str)]
+    want = {("graph", False): "decode_emit", ("graph", True): "decode_emit_sample"}.get((loop, sampled),
+                                                                                          "sample_rows" if sampled else "argmax_rows")
+    picks = [i for i, e in enumerate(log) if e[0] in ("decode_emit", "decode_emit_sample", "argmax_rows", "sample_rows")]
+    assert {log[i][0] for i in picks} == {want} and len(picks) == (3 if loop == "graph" else 12)   # (eager, eager, captured)
+    ids = got["returns"][0][2]
+    for t, i in enumerate(picks):
+        name, logits, _, out, n_dev, n_add = log[i - 1][:6]
+        assert name == "logits_process" and logits == log[i][1]
+        if loop == "graph":
+            assert n_add == 0 and n_dev.endswith(f"={[t]}".replace(" ", "")) and out == log[i][7]      # column t of the emit's matrix
+        else:
+            assert (n_dev, n_add) == (None, t)
+            have = [row[:t] + [0] * (12 - t) for row in ids]            # the ids selected so far, pad behind them
+            assert out.endswith("=" + str(have).replace(" ", ""))

@@ -283,8 +283,22 @@ def test_every_refusal_raises_through_generate_and_names_its_condition():
         _generate(prompt_lookup_num_tokens=15, B=2, attention_mask=torch.ones(2, 2, dtype=torch.long))
     with pytest.raises(_PastTheChecks):
         _generate(prompt_lookup_num_tokens=4, B=6, dtype=torch.float16, max_matching_ngram_size=9)
-    gen = inspect.getsource(Mo.LlamaForCausalLM.generate)                # the shape check behind the model
-    assert "ops.spec_attn_ok(dtype, hd0, Tmax, G + 1)" in gen and "Tmax = S0 + max_new_tokens + G" in gen
+
+
+def test_the_shape_check_behind_the_model_asks_spec_attn_ok_about_the_cache_rows_and_the_step_rows(monkeypatch):
+    """ops.spec_attn_ok(dtype, head size, Tmax = S0 + max_new_tokens + G, G + 1): a head size outside it is refused with
+    exactly those numbers, before anything is launched"""
+    from transformers import LlamaConfig
+    lm = Mo.LlamaForCausalLM(LlamaConfig(hidden_size=96, intermediate_size=64, num_hidden_layers=1, num_attention_heads=2,
+                                         num_key_value_heads=2, vocab_size=40, max_position_embeddings=64)).to(torch.bfloat16)
+    monkeypatch.setattr(Mo, "_dev_check", lambda t: None)
+    asked = []
+    real = ops.spec_attn_ok
+    monkeypatch.setattr(ops, "spec_attn_ok", lambda *a: asked.append(a) or real(*a))
+    with pytest.raises(ValueError, match=r"prompt_lookup_num_tokens=4.*spec_attn_ok is false for head size 48, 21 positions "
+                                         r"and 5 rows.*not built"):
+        lm.generate(inputs_embeds=torch.zeros(2, 5, 96, dtype=torch.bfloat16), max_new_tokens=12, prompt_lookup_num_tokens=4)
+    assert asked == [(torch.bfloat16, 48, 5 + 12 + 4, 4 + 1)]
 
 
 # ------------------------------------------------------------------- 5. the launch sequence of a verify step --
@@ -399,5 +413,5 @@ def test_lookup_loop_verifies_once_from_the_prefill_then_runs_one_fixed_step(mon
     else:
         assert log == first + step + ["capture{"] + step + ["}"] + ["replay"] * (N - 2)
     assert tuple(ids.shape) == (B, min(N, seen["ss"].n_out.max().item())) and tuple(steps.shape) == (B,) and steps.dtype == I32
-    loop = inspect.getsource(Mo.LlamaForCausalLM._generate_lookup)
-    assert "(i & 7) == 7" in loop and "eng.Spec(ss.pos, G + 1)" in loop
+    # (engine.Spec on the state's positions with Q = G + 1 rows: asserted in run() above; the look at the done flags
+    # after every 8th replay: test_beam_cpu.py's test of modeling._decode_steps, the one driver under this loop)
