@@ -475,6 +475,43 @@ int mk_logits_process(void* logits, int64_t ld, int32_t V, int32_t B, const int6
                       const int32_t* p_len, const int64_t* out, int64_t out_ld, int32_t n_max, const int32_t* n_dev,
                       int32_t n_add, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens,
                       int64_t eos, int32_t dtype, void* stream);
+/* Token log-probabilities (generate(return_logprobs=True, top_logprobs=n)): how sure the model was of a token, HF's
+ *   compute_transition_scores(normalize_logits=True), written down here; restated in numpy in tests/logprobs_ref.py, to
+ *   which the kernels are pinned.  The logits are read as they stand in front of the selection: behind the logits
+ *   processors, which rewrite them in place, and in front of temperature / top-k / top-p.  Neither emit writes them.
+ *
+ * The rule, for a row of logits x[0:V) (bf16 / f16 / f32 at pitch ld >= V; columns [V, ld) are never read):
+ *   1. m = the fp32 maximum over the columns that are neither NaN nor -inf; S = sum of expf(x_c - m) over the same columns,
+ *      accumulated in fp64 in a fixed order: a thread's own columns, then the lane tree, then wave order (mk_beam_emit's
+ *      rule; expf, not a fast intrinsic).  lse = (double)m + log(S), kept in fp64.
+ *   2. logprob(c) = (float)((double)x_c - lse): a single rounding.  A -inf column gives -inf, a NaN column gives NaN.
+ *   3. A row with no finite logit, or with a +inf in it, is degenerate, as in mk_beam_emit: every log-probability of a
+ *      degenerate row is NaN.
+ *   4. Top-n, for n = top_logprobs > 0: the n columns with the largest x_c, NaN columns excluded (-inf columns are
+ *      columns like any other, and -0 == +0), in descending order; ties go to the LOWER column.  The selection is exact,
+ *      by order-preserving integer keys as in mk_sample_rows / mk_beam_emit, never decided by arrival order.  When fewer
+ *      than n non-NaN columns exist, the remaining slots are id -1 with log-probability -inf (in a degenerate row too).
+ *      In a degenerate row the ids are still the n largest keys and their values are NaN.
+ *   Deterministic: the same logits give the same bits.
+ *
+ * mk_token_logprobs: the stand-alone twin of mk_argmax_rows, one workgroup per row: lp[r] = logprob(ids[r]) of row r, NaN
+ *   for an id outside [0, V); with n_top > 0 also top_ids int64 [rows][n_top] and top_lp f32 [rows][n_top], both dense.
+ * mk_decode_emit_logprobs: the step form, launched right BEHIND mk_decode_emit / mk_decode_emit_sample, one workgroup per
+ *   sample: the token is the one the emit just stored in tok[b], the output column is state[1] - 1, read on the device
+ *   (the emit has advanced state[1]), and the kernel fills that column of lp f32 [B][n_max] (pitch lp_ld) and, with
+ *   n_top > 0, of top_ids int64 [B][n_max][n_top] and top_lp f32 [B][n_max][n_top] (pitch lp_ld * n_top).  A column
+ *   outside [0, n_max) writes nothing to them.  A sample that was finished BEFORE this step gets 0.0, top ids pad and
+ *   top values 0.0; the step at which it emits eos still gets eos's real log-probability.  done[b] behind the emit
+ *   cannot tell the two apart, so the kernel keeps its own latch fin uint8 [B], zero before the first launch: it reads
+ *   fin[b], acts on it, then stores done[b] into it (plain vector stores; the latch follows done whatever the column).
+ *   Its values are bit for bit mk_token_logprobs' on the same row.
+ *   MK_ERR_BAD_ARG: null pointers (top_ids / top_lp may be null only when n_top == 0), rows / B <= 0, V <= 0, ld < V,
+ *   n_top < 0, n_max < 0, lp_ld < n_max.  MK_ERR_UNSUPPORTED: n_top > 20, V > 2^23, another dtype. */
+int mk_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t V, const int64_t* ids, int32_t n_top,
+                      float* lp, int64_t* top_ids, float* top_lp, int32_t dtype, void* stream);
+int mk_decode_emit_logprobs(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, const int64_t* tok,
+                            const void* done, const int32_t* state, void* fin, int32_t n_max, int32_t n_top, float* lp,
+                            int64_t lp_ld, int64_t* top_ids, float* top_lp, int32_t dtype, void* stream);
 /* mk_decode_step_attn: the attention block of one decode step in one launch: p = clamp(*t_dev, 0,
  *   t_max - 1); q and k_new (rows [H * hd] at batch stride in_bs) are rotated with rows p of the
  *   [positions][hd] cos / sin tables (modeling.py:76-91, rope rounding points of mk_rope); the rotated

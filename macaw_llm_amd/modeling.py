@@ -14,6 +14,7 @@ never-used text tower / decoder); their HF `forward` is never called
 """
 from __future__ import annotations
 
+import collections
 import copy
 import math
 import numbers
@@ -67,6 +68,12 @@ PROCESSORS = [dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_token
 PROMPT_LOOKUP = [dict(prompt_lookup_num_tokens=None, max_matching_ngram_size=2)]
 # MM_LLMs.set_generate_mask: whether MM_LLMs.forward hands its extended attention mask to generate()
 GENERATE_MASK = [False]
+# MM_LLMs.set_logprobs: the log-probability arguments MM_LLMs.forward hands to generate() (only when on)
+LOGPROBS = [dict(return_logprobs=False, top_logprobs=0)]
+
+# what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
+# top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
+GenerateLogprobs = collections.namedtuple("GenerateLogprobs", ["ids", "logprobs", "top_ids", "top_logprobs"])
 
 
 from .beam import beam_check, beam_result  # noqa: E402
@@ -111,6 +118,26 @@ def _lookup_check(where, num_tokens, max_matching_ngram_size):
     if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
         raise ValueError(f"{where}: max_matching_ngram_size must be an integer >= 1, got {n!r}")
     return int(num_tokens)
+
+
+def _logprobs_check(where, return_logprobs, top_logprobs, num_beams=1, lookup=0):
+    """the log-probability arguments of generate() / set_logprobs -> n, the top columns per token (0: the selected
+    token's value alone), or None when they are off (False, 0)"""
+    n = top_logprobs
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 0 <= n <= ops.MAX_TOP_LOGPROBS:
+        raise ValueError(f"{where}: top_logprobs must be an integer in [0, {ops.MAX_TOP_LOGPROBS}], got {n!r}")
+    if n > 0 and not return_logprobs:
+        raise ValueError(f"{where}: top_logprobs={n} without return_logprobs=True (the top columns come back with the "
+                         "log-probabilities)")
+    if not return_logprobs:
+        return None
+    if num_beams > 1:
+        raise ValueError(f"{where}(return_logprobs=True) with num_beams={num_beams}: per-token log-probabilities along "
+                         "back-tracked beams are not built; return_beam_scores=True gives each hypothesis' score")
+    if lookup:
+        raise ValueError(f"{where}(return_logprobs=True) with prompt_lookup_num_tokens={lookup}: a verify step emits "
+                         "several tokens per launch; log-probabilities behind it are not built")
+    return int(n)
 
 
 # ---------------------------------------------------------------- the helpers of generate()'s decode loops -----
@@ -630,7 +657,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     # after one eager step and replayed, the host looking at the done flags every 8 steps; otherwise kernel by kernel, the
     # host looking before every step.
     @torch.no_grad()
-    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None):
+    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None,
+                        n_top=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
         memory -- the position (int32 counter read by the fused RoPE + cache append + attention
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
@@ -638,13 +666,17 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         one eager step that also serves as the warm-up, and replayed; the host only looks at the
         finished flags every few tokens.  sample = (temperature, top_k, top_p, seed): ops.decode_emit_sample draws the
         token instead, its random number a hash of (seed, output column, sample) computed on the device.  process(logits,
-        out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1]."""
+        out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1].  n_top (None:
+        off): ops.decode_emit_logprobs behind the emit, on the logits the emit selected from, writes the token's
+        log-probability and the n_top most likely columns into device books (ops.LogprobState); the result is then
+        GenerateLogprobs, trimmed to the ids' columns."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         tok = torch.zeros(B, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         out_buf = torch.full((B, max_new_tokens), pad, dtype=torch.long, device=dev)
         V = self.lm_head.weight.shape[0]
+        ls = ops.LogprobState(B, max_new_tokens, n_top, pad, dev) if n_top is not None else None
 
         def emit(h_last):                # argmax, pad / eos handling, output column, position += 1
             lg = logits(h_last)
@@ -654,6 +686,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ops.decode_emit_sample(lg, V, pad, eos, tok, done, out_buf, state, *sample)
             else:
                 ops.decode_emit(lg, V, pad, eos, tok, done, out_buf, state)
+            if ls is not None:           # neither emit writes the logits: the values in front of the selection
+                ops.decode_emit_logprobs(lg, V, tok, done, state, ls)
 
         def step():
             emit(run(ops.embedding_fwd(emb_w, tok), 1, 0, pos=t_dev, t_dev=t_dev))
@@ -665,7 +699,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         fin = ((res == eos).cumsum(1) > 0).all(0)
         if bool(fin.any()):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
-        return res.clone()
+        if ls is None:
+            return res.clone()
+        w = res.shape[1]
+        return GenerateLogprobs(res.clone(), ls.lp[:, :w].clone(), ls.top_ids[:, :w].clone() if n_top else None,
+                                ls.top_lp[:, :w].clone() if n_top else None)
 
     @torch.no_grad()
     def _generate_beam(self, run, logits, last, emb_w, B, K, S0, max_new_tokens, eos, pad, dev, length_penalty,
@@ -742,7 +780,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None,
                  attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
                  return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
-                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False, **_):
+                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
+                 return_logprobs=False, top_logprobs=0, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -869,7 +908,25 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         and LoRA.  ValueError naming the condition for G outside [0, 15] or not an integer, max_matching_ngram_size < 1,
         B * (G + 1) > 32, num_beams > 1, do_sample=True, any logits processor, kv_cache="fp8", a padded attention_mask,
         use_cache=False, fp32 parameters and a shape outside ops.spec_attn_ok: none of these combinations is built.  None
-        or 0 (default): today's path, not one launch different."""
+        or 0 (default): today's path, not one launch different.
+
+        return_logprobs=True: the call returns the named tuple GenerateLogprobs(ids, logprobs, top_ids, top_logprobs) --
+        ids exactly the tensor the call returns without it, logprobs f32 [B, width] the log-softmax value of every
+        emitted token, and with top_logprobs=n in [1, 20] top_ids int64 [B, width, n] and top_logprobs f32 [B, width, n],
+        the n most likely columns of every step in descending order, ties to the lower column (both None for n = 0).  The
+        rule is written down in include/macaw_hip.h and restated in tests/logprobs_ref.py: fp64 log-sum-exp, one
+        rounding to fp32; a row without a finite logit or with +inf gives NaN.  The log-probabilities are those of the
+        logits as they stand in front of the selection: after the logits processors, which rewrite them in place, and
+        before temperature / top-k / top-p.  For greedy decoding that is HF's compute_transition_scores(...,
+        normalize_logits=True).  For sampling it is the model's unwarped distribution, NOT the renormalised one the draw
+        used.  Columns behind a sample's end hold 0.0, pad_token_id and 0.0; the eos itself has its real value.  On the
+        hipGraph path one more launch per step (ops.decode_emit_logprobs behind the emit, inside the captured step: still
+        one replay per token, and the host reads nothing more); the eager, padded-batch and use_cache=False loops call
+        ops.token_logprobs on the processed logits with the selected ids (any dtype).  Composes with decode_weights,
+        kv_cache, sampling, processors, a padded mask and LoRA.  ValueError naming the condition for top_logprobs not an
+        integer in [0, 20], top_logprobs > 0 without return_logprobs=True, num_beams > 1 (return_beam_scores stays what
+        beams offer) and prompt_lookup_num_tokens > 0: not built.  Defaults (False, 0): nothing is allocated, launched or
+        read."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -908,6 +965,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                        "for fp32)")
             if why is not None:
                 raise ValueError(f"generate(prompt_lookup_num_tokens={G}): {why}")
+        n_top = None              # return_logprobs: the top columns per token (None: off, nothing below runs)
+        if not (return_logprobs is False and type(top_logprobs) is int and top_logprobs == 0):   # not the defaults
+            n_top = _logprobs_check("generate", return_logprobs, top_logprobs, K, G)
         sample = None
         if do_sample:
             temperature, top_k, top_p = _sampling_check("generate", temperature, top_k, top_p)
@@ -987,7 +1047,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             nxt = torch.where(done, pads, ids)
             if gen_buf is not None:
                 gen_buf[:, t] = nxt
+            if n_top is not None:     # of the processed logits, in front of the warpers; 0.0 / pad / 0.0 where finished before
+                lp, ti, tl = ops.token_logprobs(lg, V, ids, n_top)
+                lps.append((torch.where(done, torch.zeros_like(lp), lp),
+                            torch.where(done[:, None], pads[:, None], ti) if n_top else None,
+                            torch.where(done[:, None], torch.zeros_like(tl), tl) if n_top else None))
             return nxt, done | (nxt == eos_token_id)
+
+        lps = []                      # return_logprobs in the eager loops: per new token (lp [B], top ids, top values)
+
+        def with_logprobs(ids):       # ids [B, width] -> what generate returns
+            if n_top is None:
+                return ids
+            return GenerateLogprobs(ids, torch.stack([e[0] for e in lps], dim=1),
+                                    torch.stack([e[1] for e in lps], dim=1) if n_top else None,
+                                    torch.stack([e[2] for e in lps], dim=1) if n_top else None)
 
         def beam_out(bs, state):      # the books after the loop -> what generate returns
             n_cols = int(state[1])
@@ -1024,7 +1098,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 emb = _append_column(emb, emb_w, nxt.contiguous())
                 if mask is not None:
                     mask = torch.cat([mask, torch.ones((B, 1), dtype=mask.dtype, device=dev)], dim=1)
-            return torch.stack(out, dim=1)
+            return with_logprobs(torch.stack(out, dim=1))
 
         rot = layers[0].self_attn.rotary_emb
         cos, sin = rot.tables(Tmax, dtype, dev)
@@ -1110,7 +1184,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                                  length_penalty, early_stopping, graph))
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
             return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample,
-                                        process)
+                                        process, n_top)
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
         done, out = torch.zeros(B, dtype=torch.bool, device=dev), []
@@ -1125,7 +1199,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 t_dev += 1
             else:
                 last = run(x, 1, S0 + t)                                   # decode step
-        return torch.stack(out, dim=1)
+        return with_logprobs(torch.stack(out, dim=1))
 
 
 # ---------------------------------------------------------- multimodal ------
@@ -1295,10 +1369,12 @@ class MM_LLMs(PreTrainedModel):
         if "inference" in inputs and inputs["inference"] is True:
             # prompt lookup on: the text ids are the lookup history; off: exactly the call without it
             look = dict(input_ids=inputs["input_ids"], **PROMPT_LOOKUP[0]) if PROMPT_LOOKUP[0]["prompt_lookup_num_tokens"] else {}
+            # log-probabilities on: the result is GenerateLogprobs; off: exactly the call without them
+            lps = LOGPROBS[0] if LOGPROBS[0]["return_logprobs"] else {}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
-                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0],
+                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
                                      **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
@@ -1378,6 +1454,16 @@ class MM_LLMs(PreTrainedModel):
         beams, processors, cache format, mask) is validated by generate().  No arguments: back to the default."""
         G = _lookup_check("set_prompt_lookup", num_tokens, max_matching_ngram_size)
         PROMPT_LOOKUP[0] = dict(prompt_lookup_num_tokens=G or None, max_matching_ngram_size=int(max_matching_ngram_size))
+
+    @staticmethod
+    def set_logprobs(return_logprobs=False, top_logprobs=0):
+        """Token log-probabilities for `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the same
+        names): off by default.  With return_logprobs=True forward returns GenerateLogprobs(ids, logprobs, top_ids,
+        top_logprobs) in place of the ids, top_logprobs=n in [1, 20] adding the n most likely columns of every step.
+        Validated here; what depends on the call (beams, prompt lookup) is validated by generate().  No arguments: back
+        to off.  Process-wide switch, like set_sampling."""
+        _logprobs_check("set_logprobs", return_logprobs, top_logprobs)
+        LOGPROBS[0] = dict(return_logprobs=bool(return_logprobs), top_logprobs=int(top_logprobs))
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

@@ -763,6 +763,55 @@ def logits_process(logits, V, out, n_dev=None, n_add=0, prompt=None, prompt_len=
     return logits
 
 
+MAX_TOP_LOGPROBS = 20
+
+
+def token_logprobs(logits, V, ids, top_n=0):
+    """the log-softmax value of ids[r] in row r of logits [rows, >= V] row-major, and with top_n > 0 the top_n most
+    likely columns of every row with theirs, in one launch (see mk_token_logprobs: fp64 log-sum-exp, one rounding, exact
+    selection, ties to the lower column; an id outside [0, V) gives NaN).  ids int64 [rows].  Returns (lp f32 [rows],
+    top_ids int64 [rows, top_n] | None, top_lp f32 [rows, top_n] | None); the stand-alone twin of argmax_rows"""
+    lib = _L.load()
+    rows, top_n = logits.shape[0], int(top_n)
+    if ids.dtype != torch.int64 or ids.numel() != rows or not ids.is_contiguous():
+        raise MacawHipError(f"token_logprobs: ids {ids.dtype} {tuple(ids.shape)}; expected contiguous int64 [{rows}]")
+    lp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    top_ids = top_lp = None
+    if top_n > 0:
+        top_ids = torch.empty((rows, top_n), dtype=torch.long, device=logits.device)
+        top_lp = torch.empty((rows, top_n), dtype=torch.float32, device=logits.device)
+    _L.check(lib.mk_token_logprobs(_p(logits), _rowmajor(logits), rows, V, _p(ids), top_n, _p(lp), _p(top_ids),
+                                   _p(top_lp), dt(logits), _st()), "mk_token_logprobs")
+    return lp, top_ids, top_lp
+
+
+class LogprobState:
+    """the device books of generate(return_logprobs=True) on the step path (include/macaw_hip.h, "Token
+    log-probabilities"): B samples, n_max output columns, n_top top columns per token (0: none).  lp starts as zeros,
+    top_ids as pad, top_lp as zeros: what a column behind a sample's end holds; fin is the kernel's own latch"""
+
+    def __init__(self, B, n_max, n_top, pad, dev):
+        self.B, self.n_max, self.n_top, self.pad = B, n_max, int(n_top), pad
+        self.lp = torch.zeros((B, n_max), dtype=torch.float32, device=dev)
+        self.top_ids = torch.full((B, n_max, self.n_top), pad, dtype=torch.long, device=dev) if self.n_top else None
+        self.top_lp = torch.zeros((B, n_max, self.n_top), dtype=torch.float32, device=dev) if self.n_top else None
+        self.fin = torch.zeros(B, dtype=torch.uint8, device=dev)
+
+
+def decode_emit_logprobs(logits, V, tok, done, state, ls: LogprobState):
+    """the log-probability of the token an emit just stored, launched right behind decode_emit / decode_emit_sample on
+    the same logits (see mk_decode_emit_logprobs): fills column state[1] - 1 of ls.lp (and of ls.top_ids / ls.top_lp),
+    the column read on the device, so a captured step replays; a sample finished before this step gets 0.0 / pad / 0.0"""
+    lib = _L.load()
+    B = logits.shape[0]
+    if B != ls.B or tok.numel() != B or done.numel() != B:
+        raise MacawHipError(f"decode_emit_logprobs: {B} rows of logits, {tok.numel()} tokens and {done.numel()} flags for "
+                            f"B = {ls.B}")
+    _L.check(lib.mk_decode_emit_logprobs(_p(logits), _rowmajor(logits), V, B, ls.pad, _p(tok), _p(done), _p(state),
+                                         _p(ls.fin), ls.n_max, ls.n_top, _p(ls.lp), ls.n_max, _p(ls.top_ids),
+                                         _p(ls.top_lp), dt(logits), _st()), "mk_decode_emit_logprobs")
+
+
 def decode_step_attn(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_max, B, H, hd, out, scale,
                      q_off=0, k_off=0, v_off=0):
     """RoPE(q, k_new) at position *t_dev + append [k_new | v_new] to cache [B, t_max, 2 * H * hd] row

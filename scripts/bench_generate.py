@@ -43,6 +43,12 @@ with torch.no_grad():
 # drafts are the answer: an upper bound) and "cold" = no input_ids (the history is the generated tokens only: the price of the
 # 8-row verify step wherever the output does not repeat itself).  ms per EMITTED token of every run, tokens per verify step,
 # the medians, lookup / greedy and the run-to-run spread of each arm
+#        bench_generate.py --logprobs-ab [--reps R] [B ...]: greedy against return_logprobs=True and return_logprobs=True,
+# top_logprobs=5 (one ops.decode_emit_logprobs launch behind the emit of every step), alternated the same way: ms per token of
+# every run, the medians, their differences to greedy and the greedy run-to-run spread (a difference counts only beyond it), then
+# the stand-alone time of one ops.token_logprobs / ops.decode_emit_logprobs launch (n = 0, 5, 20) against ops.argmax_rows and
+# ops.decode_emit on [B, 32000] logits
+LOGPROBS = "--logprobs-ab" in sys.argv
 LOOKUP = "--lookup-ab" in sys.argv
 AB = "--fp8-ab" in sys.argv
 PROC = "--processors-ab" in sys.argv
@@ -55,7 +61,62 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if LOGPROBS:
+    from macaw_llm_amd import ops
+    ARMS = {"greedy": {}, "logprobs": dict(return_logprobs=True), "top5": dict(return_logprobs=True, top_logprobs=5)}
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {a: [] for a in ARMS}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for kw in ARMS.values():                # untimed: each arm's first call at this batch size
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=-1, **kw)
+            for rep in range(REPS):
+                for arm, kw in ARMS.items():
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        out = model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, **kw)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                        assert (out if arm == "greedy" else out.ids).shape[1] == new
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {arm:8s}: decode {ms[arm][-1]:6.3f} ms/token", flush=True)
+        med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+        spread = max(ms["greedy"]) - min(ms["greedy"])
+        for arm in ("logprobs", "top5"):
+            diff = med[arm] - med["greedy"]
+            print(f"B={B:2d}: greedy {med['greedy']:6.3f} ms/token, {arm} {med[arm]:6.3f} ms/token, {arm} - greedy = {diff * 1e3:+7.1f} us "
+                  f"({diff / med['greedy'] * 100:+5.2f} %), greedy run-to-run spread {spread * 1e3:6.1f} us "
+                  f"({spread / med['greedy'] * 100:4.1f} %): {'inside' if abs(diff) <= spread else 'OUTSIDE'} the spread", flush=True)
+        # one launch by itself: 200 back-to-back launches between two events, after 20 warm-up launches
+        x = torch.randn(B, 32000, device=dev).mul_(3).to(torch.bfloat16)
+        ids = ops.argmax_rows(x)
+        tok, done = ids.clone(), torch.zeros(B, dtype=torch.bool, device=dev)
+        out_e = torch.zeros((B, 256), dtype=torch.long, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        st1 = torch.tensor([0, 1, 0, 0], dtype=torch.int32, device=dev)      # the step form writes column state[1] - 1 = 0
+        books = {n: ops.LogprobState(B, 256, n, 0, dev) for n in (0, 5, 20)}
+        fns = [("argmax_rows", lambda: ops.argmax_rows(x)), ("decode_emit", lambda: ops.decode_emit(x, 32000, 0, -1, tok, done, out_e, st))]
+        for n in (0, 5, 20):
+            fns.append((f"token_logprobs n={n}", lambda n=n: ops.token_logprobs(x, 32000, ids, n)))
+        for n in (0, 5, 20):
+            fns.append((f"decode_emit_logprobs n={n}", lambda n=n: ops.decode_emit_logprobs(x, 32000, ids, done, st1, books[n])))
+        us = {}
+        for name, fn in fns:
+            for i in range(20):
+                fn()
+            st.zero_(); done.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
+            st.zero_(); done.zero_()
+        print(f"B={B:2d}: one launch on [B, 32000] bf16 logits (back to back, incl. launch gaps): " +
+              ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if LOOKUP:
     G = 7
     inp = synthetic_inputs(cfg, 1, 128, modalities=("images", "audios"), seed=2, device=dev)
