@@ -512,6 +512,30 @@ int mk_token_logprobs(const void* logits, int64_t ld, int32_t rows, int32_t V, c
 int mk_decode_emit_logprobs(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, const int64_t* tok,
                             const void* done, const int32_t* state, void* fin, int32_t n_max, int32_t n_top, float* lp,
                             int64_t lp_ld, int64_t* top_ids, float* top_lp, int32_t dtype, void* stream);
+/* Classifier-free guidance (generate(guidance_scale=s, negative_prompt_ids= / negative_inputs_embeds=)): every step is
+ *   scored twice, on the caller's prompt and on a negative prompt, and decodes from the combination of the two rows of
+ *   log-probabilities -- HF's UnbatchedClassifierFreeGuidanceLogitsProcessor, the first of its processors, written down
+ *   here; restated in numpy in tests/cfg_ref.py, to which the kernel is pinned.
+ *
+ * The rule.  The step's logits are 2B rows (bf16 / f16 / f32 at pitch ld >= V; columns [V, ld) are never read): for sample
+ *   b, c is row b (the prompt) and u is row B + b (the negative prompt); the stored values are widened exactly, s is the
+ *   fp32 scale widened exactly.
+ *   1. lc = c - lse(c) and lu = u - lse(u), each by rules 1 - 3 of "Token log-probabilities" without the rounding: lse
+ *      in fp64 over the columns that are neither NaN nor -inf (expf in fp32, the sum accumulated in fp64 in a fixed order);
+ *      a -inf column gives -inf, a NaN column NaN; a row with no finite logit, or with a +inf in it, is all NaN.
+ *   2. g = lu + s * (lc - lu), in fp64.
+ *   3. Where lc or lu is -inf, g = lc: a masked conditional column stays masked, and a column the negative prompt rules
+ *      out is not guided.
+ *   4. NaN propagates (rule 3 first: lc = -inf next to lu = NaN is -inf).
+ *   5. g is rounded ONCE, to nearest even, to the logits' type and stored into row b, in place.
+ *   Rows [B, 2B), the columns [V, ld) and everything outside the 2B rows are not written.  Deterministic: the same logits
+ *   give the same bits.  s = 1 gives log_softmax(c); the public surface treats it as OFF and launches nothing.
+ *
+ * mk_cfg_combine: one workgroup per sample, two passes (an online maximum and sum of both rows; the combine and store,
+ *   re-reading the rows from L2), 16-byte accesses where the base and the pitch are multiples of 16 bytes.  It reads
+ *   nothing from the host: a captured step replays it.
+ *   MK_ERR_BAD_ARG (nothing is launched): logits null, B < 1, V < 1, ld < V, a scale that is not finite, another dtype. */
+int mk_cfg_combine(void* logits, int64_t ld, int32_t V, int32_t B, float scale, int32_t dtype, void* stream);
 /* mk_decode_step_attn: the attention block of one decode step in one launch: p = clamp(*t_dev, 0,
  *   t_max - 1); q and k_new (rows [H * hd] at batch stride in_bs) are rotated with rows p of the
  *   [positions][hd] cos / sin tables (modeling.py:76-91, rope rounding points of mk_rope); the rotated

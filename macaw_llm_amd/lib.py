@@ -122,6 +122,7 @@ SIGNATURES = {
     "mk_token_logprobs": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "mk_decode_emit_logprobs": [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32,
                                 _vp],
+    "mk_cfg_combine": [_vp, _i64, _i32, _i32, _f32, _i32, _vp],
     "mk_decode_step_attn": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32,
                             _i32, _i32, _f32, _i32, _vp],
     "mk_kv_quant_append": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],

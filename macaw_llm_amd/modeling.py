@@ -70,6 +70,9 @@ PROMPT_LOOKUP = [dict(prompt_lookup_num_tokens=None, max_matching_ngram_size=2)]
 GENERATE_MASK = [False]
 # MM_LLMs.set_logprobs: the log-probability arguments MM_LLMs.forward hands to generate() (only when on)
 LOGPROBS = [dict(return_logprobs=False, top_logprobs=0)]
+# MM_LLMs.set_guidance: the guidance_scale MM_LLMs.forward hands to generate() next to the text-only negative prompt
+# (1.0 = off: forward makes the call without them)
+GUIDANCE = [1.0]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -140,6 +143,44 @@ def _logprobs_check(where, return_logprobs, top_logprobs, num_beams=1, lookup=0)
     return int(n)
 
 
+def _guidance_check(where, guidance_scale):
+    """the guidance_scale of generate() / set_guidance -> the scale, or None when guidance is off (None or 1)"""
+    s = guidance_scale
+    if s is None:
+        return None
+    if isinstance(s, bool) or not isinstance(s, numbers.Real) or not math.isfinite(s):
+        raise ValueError(f"{where}: guidance_scale must be None or a finite number (1 = off), got {s!r}")
+    return None if s == 1 else float(s)
+
+
+def _guided_batch(scale, emb, mask, neg, neg_mask):
+    """The token rows of generate(guidance_scale=): the B prompts emb [B, Sc, D] (mask [B, Sc] or None = ones) on top of
+    their negative prompts neg [B, Sn, D] (neg_mask or None = ones), both padded at the right to the longer length ->
+    (embeddings [2B, S, D], key mask [2B, S] with a zero on every pad row).  ValueError for a negative batch, hidden size,
+    dtype or mask shape that does not match"""
+    B, Sc, D = emb.shape
+    what = f"generate(guidance_scale={scale!r})"
+    if neg.dim() != 3 or neg.shape[0] != B or neg.shape[2] != D or neg.shape[1] < 1:
+        raise ValueError(f"{what}: the negative prompt should be [{B}, Sn >= 1, {D}] like the prompt's {tuple(emb.shape)}, "
+                         f"but is {tuple(neg.shape)}")
+    if neg.dtype != emb.dtype:
+        raise ValueError(f"{what}: the negative prompt is {neg.dtype}, the prompt {emb.dtype}")
+    Sn = neg.shape[1]
+    if mask is not None and (mask.dim() != 2 or tuple(mask.shape) != (B, Sc)):
+        raise ValueError(f"attention_mask should be of size {(B, Sc)}, but is {tuple(mask.shape)}")
+    if neg_mask is not None and (neg_mask.dim() != 2 or tuple(neg_mask.shape) != (B, Sn)):
+        raise ValueError(f"{what}: negative_prompt_attention_mask should be of size {(B, Sn)}, but is "
+                         f"{tuple(neg_mask.shape)}")
+    S, dev = max(Sc, Sn), emb.device
+    rows = torch.zeros((2 * B, S, D), dtype=emb.dtype, device=dev)
+    rows[:B, :Sc] = emb
+    rows[B:, :Sn] = neg.to(dev)
+    keys = torch.zeros((2 * B, S), dtype=torch.int32, device=dev)
+    keys[:B, :Sc] = 1 if mask is None else (mask.to(dev) != 0)
+    keys[B:, :Sn] = 1 if neg_mask is None else (neg_mask.to(dev) != 0)
+    return rows, keys
+
+
 # ---------------------------------------------------------------- the helpers of generate()'s decode loops -----
 _16BIT = (torch.bfloat16, torch.float16)
 
@@ -167,11 +208,12 @@ def _attn_refusal(dtype, hd, positions, rows=None):
     return None if ok else f"fp32 parameters ({dtype})" if dtype not in _16BIT else what
 
 
-def _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, switch="decode_weights", value="fp8", beams=1):
+def _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, switch="decode_weights", value="fp8", beams=1,
+                      guided=False):
     """generate(decode_weights="fp8") and generate(kv_cache="fp8") run on the hipGraph decode path only: name
     what keeps a call off that path instead of decoding it in 16 bits (no_graph: _no_decode_graph's answer).  The limit
     of 32 sequences belongs to the weight-streaming step (switch="decode_weights", value "fp8" or "mxfp4"); the e4m3
-    cache takes any batch."""
+    cache takes any batch.  guided: B counts the 2 x samples token rows of a call with guidance_scale."""
     why = None
     attn = _attn_refusal(dtype, hd, S0 + max_new_tokens)
     if dtype not in _16BIT:
@@ -184,6 +226,9 @@ def _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, swi
     elif B * beams > 32 and switch == "decode_weights" and beams > 1:
         why = (f"B x num_beams = {B} x {beams} = {B * beams} rows: the weight-streaming decode step takes at most 32 "
                "(B * K <= 32)")
+    elif B > 32 and switch == "decode_weights" and guided:
+        why = (f"2 x B = 2 x {B // 2} = {B} rows under guidance_scale: the weight-streaming decode step takes at most 32 "
+               "(2 B <= 32)")
     elif B > 32 and switch == "decode_weights":
         why = f"{B} sequences: the weight-streaming decode step takes at most 32"
     elif attn is not None:
@@ -658,7 +703,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     # host looking before every step.
     @torch.no_grad()
     def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None,
-                        n_top=None):
+                        n_top=None, feed=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
         memory -- the position (int32 counter read by the fused RoPE + cache append + attention
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
@@ -669,7 +714,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1].  n_top (None:
         off): ops.decode_emit_logprobs behind the emit, on the logits the emit selected from, writes the token's
         log-probability and the n_top most likely columns into device books (ops.LogprobState); the result is then
-        GenerateLogprobs, trimmed to the ids' columns."""
+        GenerateLogprobs, trimmed to the ids' columns.  feed(tok) (None: the embedding of tok): the token rows a step runs
+        on -- with guidance_scale both rows of every sample, B counting the samples: `logits` then takes 2B hidden rows
+        and returns the B guided rows, and tok, done, out_buf, state and the books stay per sample."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         tok = torch.zeros(B, dtype=torch.long, device=dev)
@@ -690,7 +737,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ops.decode_emit_logprobs(lg, V, tok, done, state, ls)
 
         def step():
-            emit(run(ops.embedding_fwd(emb_w, tok), 1, 0, pos=t_dev, t_dev=t_dev))
+            emit(run(ops.embedding_fwd(emb_w, tok) if feed is None else feed(tok), 1, 0, pos=t_dev, t_dev=t_dev))
 
         emit(last)                       # token 0 (from the prefill) ...
         state[0] = S0                    # ... is the one fed at position S0
@@ -781,7 +828,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
                  return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                  prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
-                 return_logprobs=False, top_logprobs=0, **_):
+                 return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
+                 negative_prompt_attention_mask=None, negative_inputs_embeds=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -926,7 +974,32 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         kv_cache, sampling, processors, a padded mask and LoRA.  ValueError naming the condition for top_logprobs not an
         integer in [0, 20], top_logprobs > 0 without return_logprobs=True, num_beams > 1 (return_beam_scores stays what
         beams offer) and prompt_lookup_num_tokens > 0: not built.  Defaults (False, 0): nothing is allocated, launched or
-        read."""
+        read.
+
+        guidance_scale=s with negative_prompt_ids [B, Sn] or negative_inputs_embeds [B, Sn, D] (and optionally
+        negative_prompt_attention_mask [B, Sn]): classifier-free guidance, HF's arguments of the same names
+        (UnbatchedClassifierFreeGuidanceLogitsProcessor; negative_inputs_embeds is the partner of inputs_embeds).  Every
+        step is scored twice, on the prompt and on the negative prompt, and decodes from
+        log p_neg + s * (log p_prompt - log p_neg) (the rule is written down in include/macaw_hip.h and restated in
+        tests/cfg_ref.py: fp64 log-sum-exp, one rounding; a column either side masks with -inf is not guided).  The call
+        is ONE padded batch of 2B token rows -- rows [0, B) the prompts, rows [B, 2B) their negative prompts, both padded at
+        the right to the longer length under one key mask (attention_mask or ones over negative_prompt_attention_mask or
+        ones) -- on the path attention_mask= built: the masked prefill, the compacted cache, token 0 from each row's last
+        valid hidden row, the per-sample-position step kernels; two prompts of equal length without padding run the
+        unpadded path at 2B rows.  The layers, the cache, the lm_head and the quantised copies see 2B rows; ops.cfg_combine
+        then writes the guided scores into rows [0, B), and the processors, the emit, the sampler and the
+        log-probabilities see B -- HF's order: guidance first among the processors, the warpers last, the
+        log-probabilities those of the guided scores, renormalised.  The emitted token feeds both rows of its sample (two
+        gathers into one [2B, D] buffer); on the hipGraph path all of it is inside the captured step: still one replay per
+        token.  Composes with decode_weights (their limit becomes 2B <= 32), kv_cache, sampling, the processors,
+        log-probabilities, a padded attention_mask, use_cache=False (the 2B prefixes recomputed under the growing mask, any
+        dtype) and LoRA.  ValueError naming the condition for a scale that is not a finite number, guidance without a
+        negative prompt (HF's fallback to the prompt's last token is not built), both forms of the negative prompt, a
+        negative batch, hidden size, dtype or mask shape that does not match, num_beams > 1 and prompt_lookup_num_tokens >
+        0 (not built), and for use_cache=True with fp32 parameters or a shape outside ops.decode_attn_ok when the
+        assembled batch is padded (use use_cache=False).  None or 1 (default): off -- the negative prompt is ignored,
+        nothing is allocated, launched or read.  What guidance does to the quality of a trained checkpoint's answers is
+        unmeasured."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -968,6 +1041,20 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         n_top = None              # return_logprobs: the top columns per token (None: off, nothing below runs)
         if not (return_logprobs is False and type(top_logprobs) is int and top_logprobs == 0):   # not the defaults
             n_top = _logprobs_check("generate", return_logprobs, top_logprobs, K, G)
+        cfg = None                # guidance_scale: the scale (None: off, the negative prompt is ignored, nothing below runs)
+        if guidance_scale is not None:
+            cfg = _guidance_check("generate", guidance_scale)
+        if cfg is not None:
+            what = f"generate(guidance_scale={guidance_scale!r})"
+            if negative_prompt_ids is None and negative_inputs_embeds is None:
+                raise ValueError(f"{what} without a negative prompt: pass negative_prompt_ids or negative_inputs_embeds (HF's "
+                                 "fallback to the prompt's last token is not built)")
+            if negative_prompt_ids is not None and negative_inputs_embeds is not None:
+                raise ValueError(f"{what}: both negative_prompt_ids and negative_inputs_embeds were given; pass one")
+            if K > 1:
+                raise ValueError(f"{what} with num_beams={K}: guidance along beams is not built; use num_beams=1")
+            if G:
+                raise ValueError(f"{what} with prompt_lookup_num_tokens={G}: a guided verify step is not built")
         sample = None
         if do_sample:
             temperature, top_k, top_p = _sampling_check("generate", temperature, top_k, top_p)
@@ -983,6 +1070,18 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         _dev_check(inputs_embeds)
         B, S0, D = inputs_embeds.shape
         dev, dtype = inputs_embeds.device, inputs_embeds.dtype
+        Bs, Sc, own_mask = B, S0, attention_mask     # the samples, their prompt's length and mask as the caller gave them
+        if cfg is not None:       # ONE batch of B = 2 Bs token rows under one key mask: the padded-batch path from here on
+            neg = negative_inputs_embeds
+            if neg is None:
+                if negative_prompt_ids.dim() != 2 or negative_prompt_ids.shape[0] != Bs:
+                    raise ValueError(f"generate(guidance_scale={guidance_scale!r}): negative_prompt_ids should be [{Bs}, Sn], "
+                                     f"but is {tuple(negative_prompt_ids.shape)}")
+                neg = ops.embedding_fwd(emb_w, negative_prompt_ids.to(dev).long().reshape(-1)).view(
+                    *negative_prompt_ids.shape, -1)
+            inputs_embeds, attention_mask = _guided_batch(guidance_scale, inputs_embeds, attention_mask, neg,
+                                                          negative_prompt_attention_mask)
+            B, S0 = inputs_embeds.shape[:2]
         pad = pad_token_id if pad_token_id is not None else (eos_token_id or 0)
         eps = self.model.norm.variance_epsilon
         layers = self.model.layers
@@ -999,7 +1098,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ragged, rg_pos, rg_last = padded
         hist = hist_len = None    # the prompt's ids as history (the processors' or the lookup's): [B, P] int64, count per row
         if proc is not None and input_ids is not None:
-            hist, hist_len = _prompt_history(input_ids, B, dev, "the processors' prompt history", ragged)
+            hist_rg = ragged      # the padding the history leaves out: with guidance the caller's own, of the samples' rows
+            if cfg is not None and ragged is not None:
+                own = own_mask is not None and not bool((own_mask != 0).all())
+                hist_rg = eng.Ragged(ragged.kmask[:Bs, :Sc], ragged.slot[:Bs, :Sc], ragged.t_off[:Bs]) if own else None
+            hist, hist_len = _prompt_history(input_ids, Bs, dev, "the processors' prompt history", hist_rg)
         if K > 1:
             beam_check("generate", K, num_return_sequences, V, do_sample, kv_cache, ragged is not None, length_penalty)
             why = _attn_refusal(dtype, hd, S0 + max_new_tokens) if use_cache else None
@@ -1007,7 +1110,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 raise ValueError(f"generate(num_beams={K}) with use_cache=True: {why}; the beam step attention takes bf16 / "
                                  "fp16 inside ops.decode_attn_ok: pass use_cache=False")
         if decode_weights is not None:
-            _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, value=decode_weights, beams=K)
+            _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, value=decode_weights, beams=K,
+                              guided=cfg is not None)
         if kv_cache == "fp8":
             _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, switch="kv_cache")
         if G:
@@ -1020,7 +1124,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if ragged is not None and use_cache:
             why = _attn_refusal(dtype, hd, Tmax)
             if why is not None:
-                raise ValueError(f"generate(attention_mask=) with a padded mask and use_cache=True: {why}; the "
+                call = ("generate(attention_mask=) with a padded mask" if cfg is None else
+                        f"generate(guidance_scale={guidance_scale!r}) with prompts of two lengths or a padded mask")
+                raise ValueError(f"{call} and use_cache=True: {why}; the "
                                  "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
                                  "there is no masked attention over a cache: pass use_cache=False")
 
@@ -1029,7 +1135,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             def process(lg, gen, n_dev=None, n_add=0):
                 ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
 
-            gen_buf = torch.full((B, max_new_tokens), pad, dtype=torch.long, device=dev)   # the eager loops' ids so far
+            gen_buf = torch.full((Bs, max_new_tokens), pad, dtype=torch.long, device=dev)  # the eager loops' ids so far
         w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
 
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
@@ -1038,8 +1144,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
             return ops.linear_fwd(y, self.lm_head.weight)
 
+        feed = None               # guidance: the token rows of a step from the samples' ids (None: their embedding)
+        if cfg is not None:
+            head = logits
+
+            def logits(h_last):   # h_last [2 Bs, D] -> the guided scores [Bs, V], a view of the lm_head's rows [0, Bs)
+                return ops.cfg_combine(head(h_last), V, Bs, cfg)
+
+            def feed(ids):        # the emitted token feeds both rows of its sample: two gathers into one [2 Bs, D] buffer
+                x = torch.empty((B, D), dtype=dtype, device=dev)
+                ops.embedding_fwd(emb_w, ids, out=x[:Bs])
+                ops.embedding_fwd(emb_w, ids, out=x[Bs:])
+                return x
+
         def select(h_last, t, done):  # h_last [B, D] -> ids [B] of new token t (pad where done), the flags behind it
-            pads = torch.full((B,), pad, dtype=torch.long, device=dev)
+            pads = torch.full((Bs,), pad, dtype=torch.long, device=dev)
             lg = logits(h_last)
             if process is not None:
                 process(lg, gen_buf, n_add=t)
@@ -1088,14 +1207,15 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if not use_cache:
             emb = inputs_embeds.contiguous()
             mask = ragged.kmask if ragged is not None else None        # grows by a one per new token
-            done, out = torch.zeros(B, dtype=torch.bool, device=dev), []
+            done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
             for t in range(max_new_tokens):
                 # under a mask token 0 is predicted by each sample's last valid row
                 nxt, done = select(self._hidden_last(emb, mask, rg_last if mask is not None and t == 0 else None), t, done)
                 out.append(nxt)
                 if bool(done.all()):
                     break
-                emb = _append_column(emb, emb_w, nxt.contiguous())
+                # (guidance: the token continues both prefixes of its sample)
+                emb = _append_column(emb, emb_w, nxt.contiguous() if cfg is None else torch.cat([nxt, nxt]))
                 if mask is not None:
                     mask = torch.cat([mask, torch.ones((B, 1), dtype=mask.dtype, device=dev)], dim=1)
             return with_logprobs(torch.stack(out, dim=1))
@@ -1183,17 +1303,17 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             return beam_out(*self._generate_beam(run, logits, last, emb_w, B, K, S0, max_new_tokens, eos_token_id, pad, dev,
                                                  length_penalty, early_stopping, graph))
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
-            return self._generate_graph(run, logits, last, emb_w, B, S0, max_new_tokens, eos_token_id, pad, dev, sample,
-                                        process, n_top)
+            return self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
+                                        process, n_top, feed)
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
-        done, out = torch.zeros(B, dtype=torch.bool, device=dev), []
+        done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
         for t in range(max_new_tokens):
             nxt, done = select(last, t, done)
             out.append(nxt)
             if t + 1 == max_new_tokens or bool(done.all()):
                 break
-            x = ops.embedding_fwd(emb_w, nxt.contiguous())                 # [B, D]
+            x = ops.embedding_fwd(emb_w, nxt.contiguous()) if feed is None else feed(nxt.contiguous())   # [B, D]
             if ragged is not None:                                         # the graph path's step launches, one by one
                 last = run(x, 1, 0, pos=t_dev, t_dev=t_dev)
                 t_dev += 1
@@ -1371,11 +1491,20 @@ class MM_LLMs(PreTrainedModel):
             look = dict(input_ids=inputs["input_ids"], **PROMPT_LOOKUP[0]) if PROMPT_LOOKUP[0]["prompt_lookup_num_tokens"] else {}
             # log-probabilities on: the result is GenerateLogprobs; off: exactly the call without them
             lps = LOGPROBS[0] if LOGPROBS[0]["return_logprobs"] else {}
+            # guidance on: the negative prompt is the text alone, build_prefix_layout's prompt with no modality, under the
+            # text's own mask where the prompt gets its extended one; off: exactly the call without it
+            guide = {}
+            if GUIDANCE[0] != 1.0:
+                ids = inputs["input_ids"].long()
+                E = self.llm.model.embed_tokens.weight
+                guide = dict(guidance_scale=GUIDANCE[0],
+                             negative_inputs_embeds=ops.embedding_fwd(E, ids.reshape(-1)).view(*ids.shape, -1),
+                             negative_prompt_attention_mask=inputs.get("attention_mask") if GENERATE_MASK[0] else None)
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
-                                     **BEAM_SEARCH[0], **PROCESSORS[0], **look)
+                                     **guide, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1464,6 +1593,17 @@ class MM_LLMs(PreTrainedModel):
         to off.  Process-wide switch, like set_sampling."""
         _logprobs_check("set_logprobs", return_logprobs, top_logprobs)
         LOGPROBS[0] = dict(return_logprobs=bool(return_logprobs), top_logprobs=int(top_logprobs))
+
+    @staticmethod
+    def set_guidance(guidance_scale=1.0):
+        """Classifier-free guidance for `inputs["inference"] = True` (LlamaForCausalLM.generate's guidance_scale): off
+        (1.0) by default.  With it on, forward hands generate() the embedding of its text input_ids alone -- the prompt
+        without the image, audio or video rows -- as negative_inputs_embeds, so every step is steered towards what the
+        modal input adds; with set_generate_mask(True) the text's attention mask goes with it.  Validated here; what
+        depends on the call (beams, prompt lookup, dtype) is validated by generate().  No arguments: back to off.
+        Process-wide switch, like set_sampling."""
+        s = _guidance_check("set_guidance", guidance_scale)
+        GUIDANCE[0] = 1.0 if s is None else s
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

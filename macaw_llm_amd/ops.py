@@ -812,6 +812,19 @@ def decode_emit_logprobs(logits, V, tok, done, state, ls: LogprobState):
                                          _p(ls.top_lp), dt(logits), _st()), "mk_decode_emit_logprobs")
 
 
+def cfg_combine(logits, V, B, scale):
+    """classifier-free guidance in one launch, in place, behind the lm_head of a guided step (see mk_cfg_combine): logits
+    [2B, >= V] row-major, rows [0, B) scored on the prompt and rows [B, 2B) on the negative prompt; row b becomes
+    lu + scale * (lc - lu) of the two rows' log-probabilities (fp64, one rounding), rows [B, 2B) stay as they are.
+    Returns the view logits[:B] -- the same pitch, so the processors, the emits and the log-probabilities take it as
+    they take a step's logits"""
+    lib = _L.load()
+    if logits.dim() != 2 or logits.shape[0] != 2 * B:
+        raise MacawHipError(f"cfg_combine: logits {tuple(logits.shape)}; expected [2 B = {2 * B}, >= V]")
+    _L.check(lib.mk_cfg_combine(_p(logits), _rowmajor(logits), V, B, float(scale), dt(logits), _st()), "mk_cfg_combine")
+    return logits[:B]
+
+
 def decode_step_attn(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, t_max, B, H, hd, out, scale,
                      q_off=0, k_off=0, v_off=0):
     """RoPE(q, k_new) at position *t_dev + append [k_new | v_new] to cache [B, t_max, 2 * H * hd] row

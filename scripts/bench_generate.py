@@ -48,6 +48,12 @@ with torch.no_grad():
 # every run, the medians, their differences to greedy and the greedy run-to-run spread (a difference counts only beyond it), then
 # the stand-alone time of one ops.token_logprobs / ops.decode_emit_logprobs launch (n = 0, 5, 20) against ops.argmax_rows and
 # ops.decode_emit on [B, 32000] logits
+#        bench_generate.py --cfg-ab [--reps R] [B ...]: classifier-free guidance (default B = 1, 8, 16).  Three arms alternated
+# the same way: greedy at batch B, greedy at batch 2B (the token rows of the guided call) and guidance_scale=1.5 at batch B with
+# the text-only prompt as the negative one (another length: the padded-batch path at 2B rows).  ms per token of every run, the
+# medians, guided - greedy(2B) and guided - greedy(B), the greedy run-to-run spreads, then the stand-alone time of one
+# ops.cfg_combine launch on [2B, 32000] logits against ops.decode_emit_logprobs (n = 0) and one embedding gather
+CFG = "--cfg-ab" in sys.argv
 LOGPROBS = "--logprobs-ab" in sys.argv
 LOOKUP = "--lookup-ab" in sys.argv
 AB = "--fp8-ab" in sys.argv
@@ -61,7 +67,67 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if CFG:
+    from macaw_llm_amd import ops
+    for B in [int(a) for a in _args] or [1, 8, 16]:
+        big = synthetic_inputs(cfg, 2 * B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        with torch.no_grad():
+            emb2 = model.prepare_inputs_for_generation(big)[0]
+            emb1 = emb2[:B].contiguous()
+            tids = big["input_ids"][:B].long()
+            neg = ops.embedding_fwd(model.llm.model.embed_tokens.weight, tids.reshape(-1)).view(B, tids.shape[1], -1)
+            call = {"greedy B": lambda n: model.llm.generate(inputs_embeds=emb1, max_new_tokens=n, eos_token_id=-1),
+                    "greedy 2B": lambda n: model.llm.generate(inputs_embeds=emb2, max_new_tokens=n, eos_token_id=-1),
+                    "guided B": lambda n: model.llm.generate(inputs_embeds=emb1, negative_inputs_embeds=neg, guidance_scale=1.5,
+                                                             max_new_tokens=n, eos_token_id=-1)}
+            ms = {a: [] for a in call}
+            for arm in call:                        # untimed: each arm's first call at this size
+                call[arm](4)
+            for rep in range(REPS):
+                for arm in call:
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        out = call[arm](new)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                        assert out.shape == (2 * B if arm == "greedy 2B" else B, new)
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {arm:9s}: decode {ms[arm][-1]:6.3f} ms/token", flush=True)
+        med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+        sp = {a: max(v) - min(v) for a, v in ms.items()}
+        print(f"B={B:2d}: prompt {emb1.shape[1]} rows, negative prompt {neg.shape[1]} rows; greedy at batch {B} {med['greedy B']:6.3f} "
+              f"ms/token (spread {sp['greedy B'] * 1e3:6.1f} us), greedy at batch {2 * B} {med['greedy 2B']:6.3f} ms/token (spread "
+              f"{sp['greedy 2B'] * 1e3:6.1f} us), guidance_scale=1.5 at batch {B} {med['guided B']:6.3f} ms/token (spread "
+              f"{sp['guided B'] * 1e3:6.1f} us)", flush=True)
+        for base in ("greedy 2B", "greedy B"):
+            diff = med["guided B"] - med[base]
+            print(f"B={B:2d}: guided - {base} = {diff * 1e3:+8.1f} us ({diff / med[base] * 100:+6.2f} %): "
+                  f"{'inside' if abs(diff) <= sp[base] else 'OUTSIDE'} the {base} spread", flush=True)
+        # one launch by itself: 200 back-to-back launches between two events, after 20 warm-up launches.  The combine runs at
+        # scale 1 (the op launches whatever the scale; row b then holds its own log-softmax, which a repeat leaves in place)
+        x = torch.randn(2 * B, 32000, device=dev).mul_(3).to(torch.bfloat16)
+        ids = ops.argmax_rows(x[:B])
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        st1 = torch.tensor([0, 1, 0, 0], dtype=torch.int32, device=dev)      # the step form writes column state[1] - 1 = 0
+        book = ops.LogprobState(B, 256, 0, 0, dev)
+        feed = torch.empty((2 * B, emb1.shape[2]), dtype=emb1.dtype, device=dev)
+        fns = [("cfg_combine", lambda: ops.cfg_combine(x, 32000, B, 1.0)),
+               ("decode_emit_logprobs n=0", lambda: ops.decode_emit_logprobs(x[:B], 32000, ids, done, st1, book)),
+               ("embedding gather of B tokens", lambda: ops.embedding_fwd(model.llm.model.embed_tokens.weight, ids, out=feed[B:]))]
+        us = {}
+        for name, fn in fns:
+            for i in range(20):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
+        print(f"B={B:2d}: one launch (back to back, incl. launch gaps), [2B, 32000] bf16 logits: " +
+              ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if LOGPROBS:
     from macaw_llm_amd import ops
     ARMS = {"greedy": {}, "logprobs": dict(return_logprobs=True), "top5": dict(return_logprobs=True, top_logprobs=5)}
