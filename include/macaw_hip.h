@@ -539,7 +539,8 @@ int mk_cfg_combine(void* logits, int64_t ld, int32_t V, int32_t B, float scale, 
 /* mk_decode_step_attn: the attention block of one decode step in one launch: p = clamp(*t_dev, 0,
  *   t_max - 1); q and k_new (rows [H * hd] at batch stride in_bs) are rotated with rows p of the
  *   [positions][hd] cos / sin tables (modeling.py:76-91, rope rounding points of mk_rope); the rotated
- *   key and v_new go to row p of the caches; o = attention of the rotated query over keys 0 ... p. */
+ *   key and v_new go to row p of the caches; o = attention of the rotated query over keys 0 ... p.
+ *   Pinned by tests/test_decode_attn_edges_gpu.py (fp64 reference at every pass and trip edge of the key -> lane map). */
 int mk_decode_step_attn(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
                         const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
                         int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
@@ -570,6 +571,7 @@ int mk_decode_step_attn(const void* q, const void* k_new, const void* v_new, int
 int mk_kv_quant_append(const void* k, const void* v, int64_t ld, int64_t in_bs, void* cache, float* scales,
                        int32_t t0, int32_t Sn, int32_t t_max, int32_t B, int32_t H, int32_t hd, int32_t dtype,
                        void* stream);
+/* Pinned by tests/test_decode_attn_edges_gpu.py. */
 int mk_decode_step_attn_kv8(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
                             const void* sin_t, void* cache, float* scales, void* o, int64_t o_bs,
                             const int32_t* t_dev, int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale,
@@ -589,11 +591,13 @@ int mk_decode_step_attn_kv8(const void* q, const void* k_new, const void* v_new,
  *   [B][t_max][2 * H * hd] = [keys | values], a pure copy in 16-byte pieces.  mk_kv_quant_append_rows: the e4m3 cache
  *   above, bytes and scales of a written row identical to mk_kv_quant_append's for that source row.  Two source rows
  *   of a sample with the same slot: one of them wins.  Domain as mk_kv_quant_append. */
+/* Pinned by tests/test_decode_attn_edges_gpu.py. */
 int mk_decode_step_attn_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
                             const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
                             int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
                             const int32_t* t_off, int32_t t_max, int32_t B, int32_t H, int32_t hd, float scale,
                             int32_t dtype, void* stream);
+/* Pinned by tests/test_decode_attn_edges_gpu.py. */
 int mk_decode_step_attn_kv8_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
                                 const void* cos_t, const void* sin_t, void* cache, float* scales, void* o,
                                 int64_t o_bs, const int32_t* t_dev, const int32_t* t_off, int32_t t_max, int32_t B,
@@ -664,6 +668,7 @@ int mk_beam_emit(const void* logits, int64_t ld, int32_t V, int32_t B, int32_t K
                  int64_t eos, float length_penalty, int32_t early_stopping, int64_t* tok, float* scores,
                  int32_t* hist, int32_t* ind, int32_t n_max, float* pool_score, int32_t* pool_info, void* done,
                  int32_t* state, int32_t dtype, void* stream);
+/* Pinned by tests/test_decode_attn_edges_gpu.py. */
 int mk_decode_step_attn_beam(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
                              const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
                              int64_t kv_ld, int64_t kv_bs, void* o, int64_t o_bs, const int32_t* t_dev,
@@ -736,6 +741,8 @@ int mk_spec_lookup(const int64_t* prompt, int64_t p_ld, int32_t P, const int32_t
 int mk_spec_verify_emit(const void* logits, int64_t ld, int32_t V, int32_t B, int32_t R, int32_t Q, int64_t eos,
                         int64_t* tok, const int32_t* n_draft, int32_t* pos, int32_t* n_out, void* done, int64_t* out,
                         int64_t out_ld, int32_t n_max, int32_t* steps, int32_t dtype, void* stream);
+/* Pinned by tests/test_decode_attn_edges_gpu.py through mk_decode_step_attn, whose bits it reproduces row by row
+ *   (tests/test_prompt_lookup_gpu.py). */
 int mk_decode_step_attn_multi(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
                               const void* sin_t, void* k_cache, void* v_cache, int64_t kv_ld, int64_t kv_bs, void* o,
                               int64_t o_bs, const int32_t* pos, int32_t t_max, int32_t B, int32_t Q, int32_t H,
@@ -743,6 +750,7 @@ int mk_decode_step_attn_multi(const void* q, const void* k_new, const void* v_ne
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);
+/* Pinned by tests/test_decode_attn_edges_gpu.py. */
 int mk_decode_attn(const void* q, const void* k, const void* v, void* o, const int32_t* t_dev,
                    int32_t t_add, int32_t t_max, int32_t B, int32_t H, int32_t hd, int64_t q_bs,
                    int64_t k_ld, int64_t k_bs, int64_t v_ld, int64_t v_bs, int64_t o_bs, float scale,

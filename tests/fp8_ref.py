@@ -23,6 +23,11 @@ def quant_rows_bytes(x):
     return q.view(torch.uint8), torch.where(amax > 0, amax / 448.0, torch.ones_like(amax)).view(-1)
 
 
+def decode_bytes(q):
+    """float64 values of OCP e4m3fn codes (uint8): exact, 0x7F / 0xFF are NaN"""
+    return q.view(torch.float8_e4m3fn).float().double()
+
+
 def fq_rows(t):
     """fake quantisation (quantise + de-quantise in fp32), one scale per row of the last dimension"""
     shp = t.shape

@@ -239,7 +239,7 @@ SENT = 77.0
 
 
 def _attn_case(dev, dtype, B, K, H, hd, S0, p, seed):
-    D, Tmax, R_ = H * hd, S0 + 10, B * K
+    D, Tmax, R_ = H * hd, max(S0 + 10, p + 1), B * K
     g = torch.Generator().manual_seed(seed)
     cache = torch.full((B, K, Tmax, 2 * D), SENT, dtype=dtype)
     cache[:, 0, :S0] = torch.randn((B, S0, 2 * D), generator=g).to(dtype)             # the prompt: slot 0 only
@@ -260,9 +260,14 @@ def _attn_case(dev, dtype, B, K, H, hd, S0, p, seed):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("B,K,H,hd,ps", [(2, 3, 4, 64, range(5, 15)), (2, 3, 4, 128, range(5, 15)),
-                                         (2, 16, 32, 128, (5, 6, 14))], ids=["hd64", "hd128", "four-heads"])
+                                         (2, 16, 32, 128, (5, 6, 14)),
+                                         # both sides of the first pass and of the first trip (one head: 8 waves x 64 / (hd / 8)
+                                         # keys, x 8 in flight; four heads: 8 and 64), hd 16 / 32 behind their first pass
+                                         (2, 3, 4, 64, (63, 64, 65, 511, 512, 513)), (2, 3, 4, 128, (31, 32, 33, 255, 256, 257)),
+                                         (2, 16, 32, 128, (7, 8, 9, 63, 64, 65)), (2, 3, 4, 16, (257,)), (2, 3, 4, 32, (129,))],
+                         ids=["hd64", "hd128", "four-heads", "hd64-edges", "hd128-edges", "four-heads-edges", "hd16", "hd32"])
 def test_step_attn_beam_is_the_plain_kernel_on_a_gathered_cache_bit_for_bit(dev, dtype, B, K, H, hd, ps):
-    S0 = 5
+    S0 = 5          # (the table is consulted for every key from 5 on: in the second pass and the second trip too)
     for p in ps:
         cache, ind, gathered, qkv, cos, sin, D, Tmax = _attn_case(dev, dtype, B, K, H, hd, S0, p, 100 * hd + p)
         t_dev = torch.tensor([p], dtype=torch.int32, device=dev)

@@ -1,8 +1,8 @@
 """GPU: the e4m3 KV cache of generate(kv_cache="fp8") -- mk_kv_quant_append and mk_decode_step_attn_kv8 against the
-quantiser restatement of tests/fp8_ref.py (rows = heads) and fp32 softmax attention over the de-quantised cache, the
+quantiser restatement of tests/fp8_ref.py (rows = heads) and the fp64 reference of tests/decode_attn_ref.py, the
 entry points' domain, and generate() end to end: the path that really ran, batch independence, eos handling, a
 teacher-forced accuracy comparison against the e4m3 FORMAT's own error, one layer at LLaMA-7B width, the refusals.
-Tolerances are those the 16-bit kernels are already held to (tests/test_kernels_gpu.py, test_decode_fp8_gpu.py,
+The other tolerances are those the 16-bit kernels are already held to (tests/test_kernels_gpu.py, test_decode_fp8_gpu.py,
 test_fp8_gpu.py), taken over unchanged."""
 import math
 
@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import decode_attn_ref  # noqa: E402
 import fp8_ref  # noqa: E402
 from golden_util import load_case  # noqa: E402
 from oracle import configs, restate  # noqa: E402
@@ -110,9 +111,9 @@ def test_kv_quant_append_writes_the_restated_bytes_and_scales_and_nothing_else(h
 @pytest.mark.parametrize("hd,H,B,T", DECODE_STEP_SHAPES)
 def test_decode_step_attn_kv8_appends_the_quantised_row_and_attends_over_the_stored_cache(hd, H, B, T, dtype):
     """cache row p = the quantiser restatement of ops.rope_'s key and of the value, all other rows untouched (rows past p
-    hold NaN codes and NaN scales: reading one would poison the output); the output against fp32 softmax attention of
-    the rope_-rotated query over the DE-QUANTISED rows 0 ... p, under the bound the 16-bit step kernel is held to on the
-    same kind of reference; then the same launch with *t_dev = 0: the position is read at execution time."""
+    hold NaN codes and NaN scales: reading one would poison the output); the output against the fp64 reference of
+    tests/decode_attn_ref.py (the rope_-rotated query over the DE-QUANTISED rows 0 ... p of the cache as stored after the
+    call) under its bound; then the same launch with *t_dev = 0: the position is read at execution time."""
     dev = torch.device("cuda:0")
     D, Tmax, p = H * hd, T + 5, T - 1
     _, q0, s0 = _cache_case(hd, H, B, T, dtype)
@@ -142,17 +143,12 @@ def test_decode_step_attn_kv8_appends_the_quantised_row_and_attends_over_the_sto
         rest = [t for t in range(Tmax) if t != pos]
         assert torch.equal(got_q[:, rest], want_q[:, rest])
         assert torch.equal(got_s[:, rest].view(torch.int32), want_s[:, rest].view(torch.int32))
-        return (out.float().cpu(), ref_qkv[:, :D].float().cpu(), _dequant(want_q[:, :pos + 1], want_s[:, :pos + 1], hd),
+        return (out.float().cpu(), ref_qkv[:, :D].cpu(), (got_q[:, :pos + 1], got_s[:, :pos + 1]),
                 _dequant(got_q[:, :pos + 1], got_s[:, :pos + 1], hd))
 
-    out, q, kv, _ = run(p)
-    q = q.view(B, H, 1, hd)
-    k = kv[:, :, :D].reshape(B, T, H, hd).permute(0, 2, 1, 3)
-    v = kv[:, :, D:].reshape(B, T, H, hd).permute(0, 2, 1, 3)
-    ref = (torch.softmax(q @ k.transpose(-1, -2) * scale, -1) @ v).reshape(B, D)
-    err = (out - ref).abs().max().item()
-    print(f"decode_step_attn_kv8 hd={hd} H={H} B={B} T={T} {dtype}: err {err:.3e}, max|ref| {ref.abs().max().item():.3e}")
-    assert err <= 2e-2 * max(1.0, ref.abs().max().item()), err
+    out, q, (got_q, got_s), _ = run(p)
+    ref, o_abs = decode_attn_ref.ref_kv8(q, got_q, got_s, H, hd, scale)
+    decode_attn_ref.assert_within(out, ref, o_abs, dtype, f"decode_step_attn_kv8 hd={hd} H={H} B={B} T={T}")
     # *t_dev = 0: one key, probability 1 -> the output is the de-quantised value row 0 of the cache as STORED (its own
     # scales: the restated ones agree to rtol 1e-6 only), the fp32 product of code and scale rounded once to the output type
     out0, _, _, kv0 = run(0)

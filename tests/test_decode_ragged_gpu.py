@@ -39,15 +39,17 @@ def _four_heads(hd, H, B):
 
 def _positions(hd, H, B, T):
     """p_b per sample: the positions where a lane assignment can go wrong -- both sides of a trip boundary that T allows
-    (four heads per workgroup: 8 waves x 8 keys = 64; one head at hd 128: 32 keys per pass x 8 = 256), then 1, T, 0"""
-    edge = (63, 64, 65) if _four_heads(hd, H, B) else (255, 256, 257) if hd == 128 else ()
+    (four heads per workgroup: 8 waves x 8 keys = 64; one head: 8 waves x 64 / (hd / 8) keys per pass x 8 = 256 / 512 /
+    1024 / 2048 at hd 128 / 64 / 32 / 16), then 1, T, 0"""
+    trip = 64 if _four_heads(hd, H, B) else 8 * 8 * 64 // (hd // 8)
+    edge = (trip - 1, trip, trip + 1)
     cand = [p for p in edge if p <= T] + [1, T, 0, T - 1]
     cand = [p for i, p in enumerate(cand) if 0 <= p <= T and p not in cand[:i]]
     return [cand[b % len(cand)] for b in range(B)]
 
 
-# (the one-head kernel at hd 128 across its 256-key trip boundary: no shape of DECODE_STEP_SHAPES reaches it)
-VAR_SHAPES = DECODE_STEP_SHAPES + [(128, 4, 3, 258)]
+# (the one-head kernels across their trip boundaries: no shape of DECODE_STEP_SHAPES reaches one)
+VAR_SHAPES = DECODE_STEP_SHAPES + [(128, 4, 3, 258), (64, 8, 3, 514), (32, 4, 3, 1026), (16, 4, 3, 2050)]
 
 
 @pytest.mark.parametrize("dtype", H16)

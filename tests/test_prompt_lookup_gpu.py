@@ -87,10 +87,12 @@ def test_multi_query_step_attention_is_the_plain_kernel_row_by_row(dev, hd, Q, d
 
 
 @pytest.mark.parametrize("dtype", H16, ids=["bf16", "fp16"])
-@pytest.mark.parametrize("hd,pos,Tmax", [(16, 62, 70), (64, 62, 70), (128, 62, 70), (128, 254, 260), (16, 254, 260)])
+@pytest.mark.parametrize("hd,pos,Tmax", [(16, 62, 70), (64, 62, 70), (128, 62, 70), (128, 254, 260), (16, 254, 260),
+                                          (64, 510, 520), (32, 1022, 1030), (16, 2046, 2056)])
 def test_multi_query_step_attention_across_a_pass_boundary(dev, hd, pos, Tmax, dtype):
     """Q = 4 rows from position 62: they cross the 64-key pass of hd = 64 (8 waves x 8 keys) and two 32-key passes of
-    hd = 128; from 254: the 256-key trip of hd = 128 (32 keys x 8 in flight) and the 256-key pass of hd = 16"""
+    hd = 128; from 254: the 256-key trip of hd = 128 (32 keys x 8 in flight) and the 256-key pass of hd = 16; from 510,
+    1022 and 2046: the trips of hd = 64, 32 and 16"""
     _attn_case(hd, 2, 4, [pos, pos - 1], Tmax, dtype, dev, seed=pos + hd)
 
 
