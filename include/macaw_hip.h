@@ -118,7 +118,10 @@ int mk_gemm_set_cus(int n_cus);
  * `n_fill` grad-weight GEMMs (layout (1,1)) whose tiles fill the CUs that the main problem's partial last round leaves
  * idle.  A filler may be consumed over several launches: tiles [0, first_tile) of its tile order are done already, and
  * on return `taken` says how many more this launch ran (they start at first_tile).  drain = 0 takes only what balances
- * the launch and leaves the rest queued; drain = 1 takes everything.  main may be NULL (a plain grouped grad-weight
+ * the launch and leaves the rest queued; drain = 1 takes everything; drain = MK_GROUP_CARRY (2) is for a queue that
+ * outlives the launch (one queue for all layers of a backward pass): the launch ends at the level of least idle time
+ * at or above its heaviest workgroup and keeps about one tile per workgroup queued for the launches that follow.
+ * main may be NULL (a plain grouped grad-weight
  * launch: whole rounds of the queue, everything with drain).  Every tile is computed exactly as mk_gemm's
  * configuration 15 computes a whole tile, so results do not depend on how the tiles were grouped.
  * The members of one launch run concurrently and in no defined order, so they must be independent: no member's A or B
@@ -133,6 +136,7 @@ int mk_gemm_set_cus(int n_cus);
  * Replaces cuBLAS behind the backward of nn.Linear (modeling.py:134-140,159-162). */
 #define MK_NOT_GROUPED 1
 #define MK_GROUP_MAX_FILL 8
+#define MK_GROUP_CARRY 2 /* a value of `drain` */
 typedef struct mk_gemm_group_fill {
   mk_gemm_desc d;
   int32_t first_tile; /* in: tiles already done */

@@ -274,6 +274,7 @@ class BucketedStep:
         self._cus_reserved = False
         self.last_step_skipped = False
         self._micro = 0
+        self._carry_window = False     # this runtime opened ops.DW_WINDOW (begin() ... finish() / abort())
         self._order = None             # frozen launch order (bucket indices); None until the discovery step ran
         self._cursor = 0
         self._arrival: List[int] = []
@@ -474,6 +475,11 @@ class BucketedStep:
             p.grad = None
         # straight-into-the-bucket stores only on the first micro-batch (later ones ADD)
         self._install_dst(first)
+        if first and ops.GRAD_DST_OWNER[0] is self:
+            # one grad-weight queue for the whole backward (ops.DW_WINDOW): gradients stored into their slots may still be
+            # queued when their layer returns; every reader below stands behind ops.dw_flush()
+            ops.dw_carry_open()
+            self._carry_window = True
 
     def _last_micro(self):
         return self._micro == self.accumulate_steps - 1
@@ -533,6 +539,7 @@ class BucketedStep:
         b.launched = True
         if not self.collective:
             if self.local_overlap and self._local_live and not self._needs_global():
+                ops.dw_flush()                                          # the update reads the bucket: carried tiles first
                 confined = self.local_cus > 0 and not self._in_finish
                 if confined:
                     self._reserve_cus(True)                             # the GEMMs that follow plan for 256 - c CUs
@@ -545,6 +552,7 @@ class BucketedStep:
                     self._adamw_cap(cap)
                 b.updated = True
             return
+        ops.dw_flush()                           # the collective reads the bucket: carried grad-weight tiles first
         self._reserve_cus(True)
         op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
         if self.zero1:
@@ -627,20 +635,28 @@ class BucketedStep:
         the step: the remaining buckets go out in the frozen order (zeros for parameters without a
         gradient), the global norm is formed if clipping is on, every update and all-gather is
         joined."""
+        ops.dw_flush()                 # grad-weight tiles still carried (none if the backward's own callback ran)
         if not self._last_micro():
             self._micro += 1
             return
         self._micro = 0
+        self._close_carry(False)
         try:
             self._finish_window()
         finally:
             # also when the window raised: eval / generate / the next step plan for the whole chip again
             self._reserve_cus(False)
 
+    def _close_carry(self, drop: bool):
+        if getattr(self, "_carry_window", False):
+            self._carry_window = False
+            (ops.dw_carry_drop if drop else ops.dw_carry_close)()
+
     def abort(self):
         """drop a window whose forward / backward raised (the caller will not reach finish()): the direct
         gradient destinations and the GEMM planning limit are process-global and must not outlive it"""
         self._micro = 0
+        self._close_carry(True)
         self._install_dst(False)
         self._reserve_cus(False)
 

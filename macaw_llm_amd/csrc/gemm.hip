@@ -715,7 +715,10 @@ extern "C" int mk_gemm_grouped(const mk_gemm_desc* main, mk_gemm_group_fill* fil
   const int n_wg = (g_plan_cus > 0 && g_plan_cus < dev_cus) ? g_plan_cus : dev_cus;
   const int main_tiles = main ? (main->M / 256) * (main->N / 256) : 0;
   mkgp::Plan plan;
-  if (!mkgp::plan(n_wg, main_tiles, main ? main->K / 64 : 0, n_fill, rem, nk, drain != 0, plan)) return MK_NOT_GROUPED;
+  const int main_nk = main ? main->K / 64 : 0;
+  if (!(drain == MK_GROUP_CARRY ? mkgp::plan_carry(n_wg, main_tiles, main_nk, n_fill, rem, nk, plan)
+                                : mkgp::plan(n_wg, main_tiles, main_nk, n_fill, rem, nk, drain != 0, plan)))
+    return MK_NOT_GROUPED;
   GrpArgs g{};
   const auto put = [](GrpProb& p, const mk_gemm_desc& d, int first, int count) {
     p.A = d.A; p.B = d.B; p.C = d.C;

@@ -24,6 +24,8 @@
 //            per workgroup when all fillers share one K) go one each to the lightest workgroups.  With fillers of
 //            different K the counts are then priced as dealt and single tiles moved from the heaviest to the lightest
 //            workgroup while the two differ by more than a tile.
+//   carry:   (plan_carry) the queue lives on behind the launch, so the level is free: the L >= lmain of least idle
+//            time, moved by whole tiles per workgroup to keep about one tile per workgroup queued.
 // Limitation: the level pass prices a workgroup as if it took its tiles in one run along the queue, while wg_tile deals
 // a group's span round by round.  With one K for everything a launch takes (every decoder layer: K = tokens / 64) the
 // two are the same; where a balancing launch's span crosses fillers of different K, a workgroup's real cost differs
@@ -97,6 +99,17 @@ inline void price(int n, const double* main_cost, int n_fill, const int* rem, co
     }
   }
 }
+// the plan of cnt[r] filler tiles for the workgroup of rank r: the runs, and the queue's prefix that they cover
+inline void emit(int n_wg, int n_fill, const int* rem, const int* cnt, Plan& out) {
+  long at = 0;
+  for (int r = 0; r < n_wg; ++r) { out.start[r] = (uint16_t)at; at += cnt[r]; }
+  for (int r = n_wg; r <= MAX_WG; ++r) out.start[r] = (uint16_t)at;
+  long rest = at;
+  for (int i = 0; i < MAX_FILL; ++i) {
+    out.taken[i] = i < n_fill ? (int)std::min<long>(rest, rem[i]) : 0;
+    rest -= out.taken[i];
+  }
+}
 }  // namespace detail
 
 // n_wg workgroups, a main problem of main_tiles tiles of main_nk K-tiles (0 tiles: none), fillers with rem[i] remaining
@@ -155,14 +168,80 @@ inline bool plan(int n_wg, int main_tiles, int main_nk, int n_fill, const int* r
       --cnt[h]; ++cnt[l];
     }
   }
-  long at = 0;
-  for (int r = 0; r < n_wg; ++r) { out.start[r] = (uint16_t)at; at += cnt[r]; }
-  for (int r = n_wg; r <= MAX_WG; ++r) out.start[r] = (uint16_t)at;
-  long rest = at;
-  for (int i = 0; i < MAX_FILL; ++i) {
-    out.taken[i] = i < n_fill ? (int)std::min<long>(rest, rem[i]) : 0;
-    rest -= out.taken[i];
+  detail::emit(n_wg, n_fill, rem, cnt, out);
+  return true;
+}
+
+// Tiles that a carrying launch aims to leave queued: one per workgroup.  A level moves in steps of one tile per
+// workgroup, so the backlog lands within n_wg / 2 of this wherever the queue allows it: between n_wg / 2 and 3 n_wg / 2
+// tiles.  Why one: in the decoder every grad-input launch has its own grad-weight GEMM queued in front of it, and that
+// one alone holds more tiles than the launch's least-idle level needs (cfg 3 at 256: 688 for 250, 1376 for 1120, 256
+// for 224, 768 for 672), so no backlog at all would already do; one tile per workgroup is the margin for a launch
+// whose own filler is short, and it ends the step with a single filler-only round.  It is far from the limits: at
+// most 3 n_wg / 2 tiles lie in two or three problems of a decoder layer (MAX_FILL = 8 live ones, 65535 tiles), and the
+// operands they keep alive are those of the layer just left (tests/gemm_group_carry_main.cpp walks 32 layers).
+inline int carry_target(int n_wg) { return n_wg; }
+
+// carry: the queue outlives the launch (it is shared by the layers of a backward pass), so the launch is free to end at any
+// level L >= lmain and takes the one that costs the least idle time, sum over workgroups of (heaviest - cost), priced as
+// dealt.  The workgroups come in at most two classes of main cost (q or q + 1 main tiles); a plan is a filler count per
+// class, kA for the heavier and kB for the lighter one, and every pair whose level can lie in [lmain, lmain + t_max) is
+// priced.  Fillers of one K (every decoder layer): kA = 0 and kB = floor or ceil of the gap in tiles, and adding s tiles
+// to every workgroup leaves the idle time as it is, so s >= 0 is chosen to bring the backlog nearest carry_target().
+// Fillers of different K: the pairs are priced as dealt and ties go to the backlog nearest the target; no shift (its
+// price would depend on what lies further along the queue).
+// Without a main problem, and where today's balance uses the queue up, the plan is that of plan(..., drain = false, ...).
+inline bool plan_carry(int n_wg, int main_tiles, int main_nk, int n_fill, const int* rem, const int* nk, Plan& out) {
+  if (!plan(n_wg, main_tiles, main_nk, n_fill, rem, nk, false, out)) return false;
+  long queued = 0;
+  double t_min = 1e30, t_max = 0;
+  for (int i = 0; i < n_fill; ++i) {
+    queued += rem[i];
+    if (rem[i] > 0) { t_min = std::min(t_min, nk[i] + TILE_C); t_max = std::max(t_max, nk[i] + TILE_C); }
   }
+  if (main_tiles == 0 || out.start[n_wg] >= queued) return true;
+  double main_cost[MAX_WG], cost[MAX_WG];
+  int cnt[MAX_WG];
+  double lmain = 0, lmin = 1e30;
+  for (int r = 0; r < n_wg; ++r) {
+    main_cost[r] = main_tiles_of(wg_of_rank(r, n_wg), n_wg, main_tiles) * (main_nk + TILE_C);
+    lmain = std::max(lmain, main_cost[r]);
+    lmin = std::min(lmin, main_cost[r]);
+  }
+  int n_light = 0;
+  for (int r = 0; r < n_wg; ++r) n_light += main_cost[r] < lmain;
+  const int n_heavy = n_wg - n_light;
+  const double gap = lmain - lmin, eps = 1e-9;
+  const bool one_k = t_max - t_min < eps;
+  const long target = carry_target(n_wg);
+  const auto dist = [&](long taken) { const long d = queued - taken - target; return d < 0 ? -d : d; };
+  double best = 1e300;
+  long best_taken = 0;
+  int best_a = 0, best_b = 0;
+  for (int ka = 0; ka * t_min < t_max - eps; ++ka) {
+    for (int kb = one_k ? (int)(gap / t_min + eps) : 0; lmin + kb * t_min < lmain + t_max - eps; ++kb) {
+      if (n_light == 0 && kb > 0) break;
+      const long taken = (long)ka * n_heavy + (long)kb * n_light;
+      if (taken > queued) break;
+      for (int r = 0; r < n_wg; ++r) cnt[r] = main_cost[r] < lmain ? kb : ka;
+      detail::price(n_wg, main_cost, n_fill, rem, nk, cnt, cost);
+      double heavy = 0, sum = 0;
+      for (int r = 0; r < n_wg; ++r) { heavy = std::max(heavy, cost[r]); sum += cost[r]; }
+      if (heavy >= lmain + t_max - eps) continue;
+      const double idle = heavy * n_wg - sum;
+      if (idle < best - 1e-6 || (idle < best + 1e-6 && dist(taken) < dist(best_taken))) {
+        best = idle; best_taken = taken; best_a = ka; best_b = kb;
+      }
+    }
+  }
+  long shift = 0;
+  if (one_k) {
+    const long room = (queued - best_taken) / n_wg;
+    shift = (queued - best_taken - target + n_wg / 2) / n_wg;      // (C++ division truncates towards zero: negative -> 0 below)
+    shift = std::max(0L, std::min(shift, room));
+  }
+  for (int r = 0; r < n_wg; ++r) cnt[r] = (int)shift + (main_cost[r] < lmain ? best_b : best_a);
+  detail::emit(n_wg, n_fill, rem, cnt, out);
   return true;
 }
 

@@ -20,6 +20,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
+from . import lib as _L
 from . import ops
 
 pad8 = ops.pad8
@@ -245,19 +246,62 @@ class _DwFill:
 
     def __init__(self):
         DW_FILL["layers"] += 1
-        self.q = ops.DwQueue()
+        # inside a carry window the layers of a backward pass share one queue, and a layer leaves it un-drained as long as
+        # every one of its gradients goes straight into its bucket slot (`slots`): nothing reads a slot before ops.dw_flush()
+        self.shared = DW_CARRY["on"] and _dw_window_join()
+        self.slots = True
+        self.q = ops.DW_WINDOW["q"] if self.shared else ops.DwQueue()
 
     def pair(self, dy, W, x, name, want_dw, fp8=False, drain=False):
-        """dW is queued BEFORE the grad-input launch, which takes its tiles as fillers (all that is queued with drain);
-        its destination is the weight's gradient-bucket slot, else a fresh tensor"""
+        """dW is queued BEFORE the grad-input launch, which takes its tiles as fillers (all that is queued with drain, the
+        least-idle level while the layer carries); its destination is the weight's gradient-bucket slot, else a fresh tensor"""
         out = ops.grad_dst(W)
         if out is None:
+            # (a fresh tensor is read by the gradient hook as soon as the layer returns: the layer drains as without a window)
+            self.slots = False
             out = torch.empty((dy.shape[1], x.shape[1]), dtype=dy.dtype, device=dy.device)
         dw = self.q.push(dy, x, out)
-        return self.q.dx(dy, W, drain=drain), dw
+        return self.q.dx(dy, W, drain=_L.GROUP_CARRY if self.shared and self.slots else drain), dw
 
     def join(self):
-        self.q.flush()           # (nothing is left behind a draining launch)
+        if self.shared and self.slots:
+            ops.DW_WINDOW["carried"] += sum(it[2] - it[1] for it in self.q.items)     # (tiles left to the next layer's launches)
+        else:
+            self.q.flush()       # (nothing is left behind a draining launch)
+
+
+# One queue per backward pass instead of one per layer (ops.DW_WINDOW; opened by bucketed.BucketedStep.begin): the dx(q|k|v)
+# launch of a layer no longer has to use the queue up, so each of the four launches ends at the level of least idle time and
+# the tiles left over fill the launches of the layer processed next (csrc/gemm_group_plan.h plan_carry).  The same tiles,
+# the same instruction stream: bit-identical results.  MACAW_DW_CARRY = 0 | 1; DW_CARRY["on"] at run time.
+# Measured: profiles/dw_carry_cfg3.txt.
+DW_CARRY = {"on": os.environ.get("MACAW_DW_CARRY", "1") != "0"}
+
+
+def _dw_window_flush():
+    """end of a backward pass that carried: code that reads .grad without the runtime's finish() sees complete gradients"""
+    ops.DW_WINDOW["callback"] = False
+    ops.dw_flush()
+
+
+def _dw_window_join() -> bool:
+    """may this layer use the open window's queue?  The window lives on ONE stream, and the first carrying layer of a
+    backward pass queues the end-of-backward flush on the autograd engine (no engine running: no carry)"""
+    win = ops.DW_WINDOW
+    if win["q"] is None:
+        return False
+    cur = torch.cuda.current_stream()
+    if win["stream"] is None:
+        win["stream"] = cur
+    elif win["stream"] != cur:
+        return False
+    if not win["callback"]:
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(_dw_window_flush)
+        except RuntimeError:
+            return False
+        win["callback"] = True
+    return True
 
 
 def _fp8_ok(x, W) -> bool:

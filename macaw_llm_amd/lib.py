@@ -54,6 +54,7 @@ class GroupFill(C.Structure):
 
 NOT_GROUPED = 1          # mk_gemm_grouped: a member is outside its domain, nothing was launched
 GROUP_MAX_FILL = 8
+GROUP_CARRY = 2          # mk_gemm_grouped's drain argument: the queue outlives the launch (MK_GROUP_CARRY)
 
 _vp, _i32, _i64, _f32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 

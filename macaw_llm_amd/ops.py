@@ -164,17 +164,61 @@ class DwQueue:
             self.items.pop(0)
 
     def dx(self, dy, W, drain=False):
-        """dx[M, K] = dy[M, N] @ W[N, K] (linear_dx) with queued grad-weight tiles in the same launch"""
+        """dx[M, K] = dy[M, N] @ W[N, K] (linear_dx) with queued grad-weight tiles in the same launch.  drain: False = what
+        balances the launch, True = everything, lib.GROUP_CARRY = the level of least idle time (the queue lives on)"""
         M, N = dy.shape
         K = W.shape[1]
         out = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
         d = gemm_desc(dy, W, out, M, K, N, _rowmajor(dy), _rowmajor(W), _rowmajor(out), b_red=True)
-        if not self._launch(d, drain or len(self.items) >= _L.GROUP_MAX_FILL):
+        if len(self.items) >= _L.GROUP_MAX_FILL:
+            drain = True
+        if not self._launch(d, drain):
             self.flush()
             _L.check(_L.load().mk_gemm(C.byref(d), _st()), "mk_gemm")
-        elif drain:
+        elif drain == 1:
             self.flush()         # (only if more problems were queued than one launch takes)
         return out
+
+
+# One DwQueue for all groupable layers of a backward pass (engine._DwFill, profiles/dw_carry_cfg3.txt).  A step runtime opens
+# the window (bucketed.BucketedStep.begin); inside it a layer whose grad-weight GEMMs all store straight into their gradient-
+# bucket slots does not drain the queue in its last grad-input launch: every launch takes the level of least idle time
+# (lib.GROUP_CARRY) and what stays queued fills the launches of the layer processed next.  Whoever reads a carried gradient
+# calls dw_flush() first -- BucketedStep.finish() and its bucket launches, and the end-of-backward callback that the first
+# carrying layer of a backward pass queues.  Everything runs on the stream of the window's first carrying layer.
+DW_WINDOW = {"q": None, "stream": None, "callback": False, "carried": 0, "flushed": 0}
+
+
+def dw_carry_open():
+    """open the window (a window left open is dropped with what it holds: nobody will read those gradients)"""
+    DW_WINDOW.update(q=DwQueue(), stream=None, callback=False)
+
+
+def dw_carry_close():
+    """launch what is queued and close the window"""
+    dw_flush()
+    DW_WINDOW.update(q=None, stream=None, callback=False)
+
+
+def dw_carry_drop():
+    """close the window without launching anything (the backward raised: its gradients are not read)"""
+    DW_WINDOW.update(q=None, stream=None, callback=False)
+
+
+def dw_flush():
+    """launch every carried grad-weight tile (filler-only grouped launches) on the window's stream, in front of a reader of the
+    gradients; a no-op without a window or with nothing queued"""
+    q = DW_WINDOW["q"]
+    if q is None or not q.items:
+        return
+    DW_WINDOW["flushed"] += sum(it[2] - it[1] for it in q.items)
+    st, cur = DW_WINDOW["stream"], torch.cuda.current_stream()
+    if st is None or st == cur:
+        q.flush()
+        return
+    with torch.cuda.stream(st):
+        q.flush()
+    cur.wait_stream(st)      # (a reader on another stream than the backward's: order it behind the flush)
 
 
 # --------------------------------------------------------------------- fp8 --
