@@ -479,6 +479,50 @@ int mk_logits_process(void* logits, int64_t ld, int32_t V, int32_t B, const int6
                       const int32_t* p_len, const int64_t* out, int64_t out_ld, int32_t n_max, const int32_t* n_dev,
                       int32_t n_add, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens,
                       int64_t eos, int32_t dtype, void* stream);
+/* Token-sequence matching (generate(bad_words_ids=, stop_sequences=)): HF's NoBadWordsLogitsProcessor, and the stop
+ *   lists of TGI (stop_sequences) and vLLM (stop) -- HF's stop_strings at token level -- written down here; restated in
+ *   torch in tests/stop_ref.py, to which both kernels are pinned exactly (integers and the -inf bit pattern only).
+ *
+ * The table, on the device, built once per call: seq_ids int64 [total], the sequences back to back, and seq_off int32
+ *   [n_seq + 1], ascending from 0: sequence q_s = seq_ids[seq_off[s] .. seq_off[s + 1]).  At most 2^16 = 65536 sequences
+ *   of 1 .. 64 ids each; an entry of another length matches nothing.
+ * The history h_b = prompt_b ++ generated_b and its arguments (prompt, p_ld, P, p_len, out, out_ld, n_max, n_dev, n_add)
+ *   exactly as in "Logits processors": n = clamp((n_dev ? *n_dev : 0) + n_add, 0, n_max) generated tokens, read on the
+ *   device, so a captured step replays.
+ *
+ * The ban rule (mk_seq_ban), L = |h_b|: for every sequence q of m ids, logit[q[m - 1]] = -inf when m == 1, and when
+ *   L >= m - 1 and h[L - m + 1 .. L) == q[0 .. m - 1).  A banned sequence is therefore never completed.  Two deliberate
+ *   differences from HF: (1) the installed transformers skips a multi-token sequence while L < m, so a banned m-gram can
+ *   be emitted as the first m ids of a history (the case of a call on embeddings alone, whose history is the generated
+ *   tokens); here L >= m - 1 suffices, and the two agree bit for bit wherever L >= m for every sequence; (2) HF ADDS
+ *   a bias row, -inf in the banned columns and 0.0 elsewhere, which turns a banned +inf or NaN logit into NaN and every -0
+ *   into +0; here the banned column is SET to -inf whatever it held and no other bit changes.  An id outside
+ *   [0, V) names no column: it takes part in the comparison and changes no logit.  Dropping a sequence equal to [eos]
+ *   (HF's rule) is the caller's business: the table is taken as it stands.
+ *   Its place in the chain: HF runs NoBadWords between the n-gram and the min-length processor.  Every neighbour there
+ *   only writes -inf, and the repetition penalty maps -inf to -inf, so a separate launch BEHIND mk_logits_process and in
+ *   front of the selection gives HF's chain exactly.
+ * mk_seq_ban: one workgroup per row, the threads stride over the sequences and compare each prefix with the history's
+ *   tail.  Logits bf16 / f16 / f32 [B][V] at pitch ld >= V.  Only the columns that matching sequences name are written:
+ *   every other column and the padding [V, ld) keep their bits.  Several threads may store the same -inf to one column:
+ *   plain vector stores, no atomics.
+ *
+ * The stop rule (mk_stop_match): a sample that has not finished finishes at the step whose token makes its GENERATED
+ *   tokens end with one of the sequences: out[b][n - m .. n) == q for a sequence of m <= n ids.  The window is the
+ *   generated tokens only: it never reaches into the prompt, and a sequence longer than n cannot match.  The matched
+ *   sequence stays in the output, as eos does.
+ * mk_stop_match: one workgroup per sample, launched right BEHIND mk_decode_emit / mk_decode_emit_sample and in front of
+ *   mk_decode_emit_logprobs (whose latch then gives the last token of a stop sequence its real log-probability and the
+ *   columns behind it 0.0); the graph loop passes n_dev = state + 1, which the emit has already advanced.  A row whose
+ *   done byte is set is not examined; a match stores 1 into done[b] (uint8 [B]); no other byte is written.
+ *
+ * Both: MK_ERR_BAD_ARG for a null logits / out / seq_ids / seq_off / done, a prompt without p_len, B <= 0, V <= 0,
+ *   n_seq <= 0, ld < V, n_max < 0, out_ld < n_max, P < 0, p_ld < P.  MK_ERR_UNSUPPORTED: n_seq > 65536, another dtype. */
+int mk_seq_ban(void* logits, int64_t ld, int32_t V, int32_t B, const int64_t* prompt, int64_t p_ld, int32_t P,
+               const int32_t* p_len, const int64_t* out, int64_t out_ld, int32_t n_max, const int32_t* n_dev,
+               int32_t n_add, const int64_t* seq_ids, const int32_t* seq_off, int32_t n_seq, int32_t dtype, void* stream);
+int mk_stop_match(const int64_t* out, int64_t out_ld, int32_t n_max, int32_t B, const int32_t* n_dev, int32_t n_add,
+                  const int64_t* seq_ids, const int32_t* seq_off, int32_t n_seq, void* done, void* stream);
 /* Token log-probabilities (generate(return_logprobs=True, top_logprobs=n)): how sure the model was of a token, HF's
  *   compute_transition_scores(normalize_logits=True), written down here; restated in numpy in tests/logprobs_ref.py, to
  *   which the kernels are pinned.  The logits are read as they stand in front of the selection: behind the logits

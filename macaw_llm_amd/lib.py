@@ -120,6 +120,8 @@ SIGNATURES = {
                               _vp],
     "mk_logits_process": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _f32, _i32, _i32, _i64,
                           _i32, _vp],
+    "mk_seq_ban": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp],
+    "mk_stop_match": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
     "mk_token_logprobs": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "mk_decode_emit_logprobs": [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32,
                                 _vp],

@@ -73,6 +73,8 @@ LOGPROBS = [dict(return_logprobs=False, top_logprobs=0)]
 # MM_LLMs.set_guidance: the guidance_scale MM_LLMs.forward hands to generate() next to the text-only negative prompt
 # (1.0 = off: forward makes the call without them)
 GUIDANCE = [1.0]
+# MM_LLMs.set_stopping: the stop_sequences and bad_words_ids MM_LLMs.forward hands to generate() (only when one is set)
+STOPPING = [dict(stop_sequences=None, bad_words_ids=None)]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -141,6 +143,37 @@ def _logprobs_check(where, return_logprobs, top_logprobs, num_beams=1, lookup=0)
         raise ValueError(f"{where}(return_logprobs=True) with prompt_lookup_num_tokens={lookup}: a verify step emits "
                          "several tokens per launch; log-probabilities behind it are not built")
     return int(n)
+
+
+def _stopping_check(where, stop_sequences, bad_words_ids, eos=None, num_beams=1, lookup=0):
+    """the token-sequence arguments of generate() / set_stopping -> (stop, bad): each a list of lists of ints, or None when
+    it is off.  A bad word equal to [eos] is dropped (HF's rule); none left: off"""
+    got = []
+    for name, v in (("stop_sequences", stop_sequences), ("bad_words_ids", bad_words_ids)):
+        if v is None:
+            got.append(None)
+            continue
+        shown = repr(v) if len(repr(v)) <= 120 else repr(v)[:117] + "..."
+        if not isinstance(v, list) or len(v) == 0 or any(not isinstance(q, list) or len(q) == 0 for q in v):
+            raise ValueError(f"{where}: {name} must be None or a non-empty list of non-empty lists of token ids, got {shown}")
+        if any(isinstance(c, bool) or not isinstance(c, numbers.Integral) or c < 0 for q in v for c in q):
+            raise ValueError(f"{where}: {name} must hold integer token ids >= 0, got {shown}")
+        if len(v) > ops.MAX_SEQS:
+            raise ValueError(f"{where}: {name} holds {len(v)} sequences; at most {ops.MAX_SEQS} are built")
+        long = max(len(q) for q in v)
+        if long > ops.MAX_SEQ_LEN:
+            raise ValueError(f"{where}: {name} holds a sequence of {long} ids; at most {ops.MAX_SEQ_LEN} are built")
+        if num_beams > 1:
+            raise ValueError(f"{where}({name}=) with num_beams={num_beams}: matching along each beam's back-tracked history "
+                             "is not built; use num_beams=1")
+        if lookup:
+            raise ValueError(f"{where}({name}=) with prompt_lookup_num_tokens={lookup}: matching inside a multi-token verify "
+                             "step is not built")
+        got.append([[int(c) for c in q] for q in v])
+    stop, bad = got
+    if bad is not None:
+        bad = [q for q in bad if q != [eos]] or None
+    return stop, bad
 
 
 def _guidance_check(where, guidance_scale):
@@ -703,7 +736,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     # host looking before every step.
     @torch.no_grad()
     def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None,
-                        n_top=None, feed=None):
+                        n_top=None, feed=None, stopped=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
         memory -- the position (int32 counter read by the fused RoPE + cache append + attention
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
@@ -716,7 +749,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         log-probability and the n_top most likely columns into device books (ops.LogprobState); the result is then
         GenerateLogprobs, trimmed to the ids' columns.  feed(tok) (None: the embedding of tok): the token rows a step runs
         on -- with guidance_scale both rows of every sample, B counting the samples: `logits` then takes 2B hidden rows
-        and returns the B guided rows, and tok, done, out_buf, state and the books stay per sample."""
+        and returns the B guided rows, and tok, done, out_buf, state and the books stay per sample.  stopped(out_buf,
+        done, n_dev) (None: off): the stop-sequence match directly behind the emit, which sets done flags as eos does."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         tok = torch.zeros(B, dtype=torch.long, device=dev)
@@ -733,6 +767,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ops.decode_emit_sample(lg, V, pad, eos, tok, done, out_buf, state, *sample)
             else:
                 ops.decode_emit(lg, V, pad, eos, tok, done, out_buf, state)
+            if stopped is not None:      # in front of the log-probabilities' latch: the stop token keeps its value
+                stopped(out_buf, done, state[1:2])
             if ls is not None:           # neither emit writes the logits: the values in front of the selection
                 ops.decode_emit_logprobs(lg, V, tok, done, state, ls)
 
@@ -743,7 +779,13 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         state[0] = S0                    # ... is the one fed at position S0
         res = out_buf[:, :1 + _decode_steps(step, done, max_new_tokens - 1, True)]
         # the eager loop stops right after the token at which every sample has finished
-        fin = ((res == eos).cumsum(1) > 0).all(0)
+        fin = (res == eos).cumsum(1) > 0
+        if stopped is not None and bool(done.all()):     # ... by eos or by a stop sequence: every column's tail, once more
+            hit = torch.zeros((res.shape[1], B), dtype=torch.bool, device=dev)
+            for c in range(res.shape[1]):
+                stopped(out_buf, hit[c], n_add=c + 1)
+            fin |= hit.t().cumsum(1) > 0
+        fin = fin.all(0)
         if bool(fin.any()):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
         if ls is None:
@@ -829,7 +871,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                  prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
-                 negative_prompt_attention_mask=None, negative_inputs_embeds=None, **_):
+                 negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
+                 bad_words_ids=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -999,7 +1042,31 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         0 (not built), and for use_cache=True with fp32 parameters or a shape outside ops.decode_attn_ok when the
         assembled batch is padded (use use_cache=False).  None or 1 (default): off -- the negative prompt is ignored,
         nothing is allocated, launched or read.  What guidance does to the quality of a trained checkpoint's answers is
-        unmeasured."""
+        unmeasured.
+
+        stop_sequences and bad_words_ids, each a list of token-id lists: what TGI's stop_sequences / vLLM's stop / HF's
+        stop_strings give at token level, and HF's argument of the same name (NoBadWordsLogitsProcessor).  Both are
+        matched on the device against a table built once per call (the rules are written down in include/macaw_hip.h
+        and restated in tests/stop_ref.py).  stop_sequences: a sample that has not finished finishes at the step whose
+        token makes its GENERATED tokens end with one of the sequences -- the window never reaches into the prompt -- and
+        the finished flag then does what eos does: the matched sequence stays in the output, pad_token_id follows, the
+        loop ends once every sample has finished, and the returned width is the column at which the last one did, by
+        eos or by a sequence, on every path.  One launch (ops.stop_match) directly behind the emit and in front of the
+        log-probabilities, so the last token of a stop sequence keeps its real log-probability and the columns behind
+        it hold 0.0; min_new_tokens keeps concerning eos alone, as in HF.  bad_words_ids: the last id of a sequence of n
+        ids gets -inf when n == 1, and when the history (the processors' history: the prompt's ids where input_ids is
+        given, valid ids only under a padded mask, then the generated tokens; a match may straddle the two) ends with
+        its first n - 1 ids.  One launch (ops.seq_ban) behind ops.logits_process and in front of every selection,
+        which gives HF's chain; a sequence equal to [eos_token_id] is dropped, as in HF.  Two deliberate differences:
+        HF skips a sequence while the history is shorter than n and can therefore emit a banned n-gram as a history's
+        first n ids, here L >= n - 1 suffices and a banned sequence is never emitted (identical wherever L >= n); HF
+        adds -inf, here the column is set to -inf whatever it held.  Log-probabilities score the banned logits, under
+        guidance both see the samples' guided rows.  On the hipGraph path both launches are inside the captured step:
+        still one replay per token, the host reads nothing more.  Compose with decode_weights, kv_cache, sampling, the
+        processors, a padded mask, log-probabilities, guidance, use_cache=False (any dtype) and LoRA.  ValueError naming
+        the argument for a value that is not a non-empty list of non-empty lists of integers >= 0, more than 65536
+        sequences, a sequence longer than 64, and either argument with num_beams > 1 or prompt_lookup_num_tokens > 0
+        (not built).  None (default): nothing is allocated, launched or read."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1055,6 +1122,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 raise ValueError(f"{what} with num_beams={K}: guidance along beams is not built; use num_beams=1")
             if G:
                 raise ValueError(f"{what} with prompt_lookup_num_tokens={G}: a guided verify step is not built")
+        stop = bad = None         # stop_sequences / bad_words_ids as lists (None: off, nothing below runs)
+        if stop_sequences is not None or bad_words_ids is not None:
+            stop, bad = _stopping_check("generate", stop_sequences, bad_words_ids, eos_token_id, K, G)
         sample = None
         if do_sample:
             temperature, top_k, top_p = _sampling_check("generate", temperature, top_k, top_p)
@@ -1097,7 +1167,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if padded is not None:
                 ragged, rg_pos, rg_last = padded
         hist = hist_len = None    # the prompt's ids as history (the processors' or the lookup's): [B, P] int64, count per row
-        if proc is not None and input_ids is not None:
+        if (proc is not None or bad is not None) and input_ids is not None:
             hist_rg = ragged      # the padding the history leaves out: with guidance the caller's own, of the samples' rows
             if cfg is not None and ragged is not None:
                 own = own_mask is not None and not bool((own_mask != 0).all())
@@ -1131,10 +1201,21 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                  "there is no masked attention over a cache: pass use_cache=False")
 
         process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add)
-        if proc is not None:
-            def process(lg, gen, n_dev=None, n_add=0):
-                ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
+        if proc is not None or bad is not None:
+            bad_t = ops.SeqTable(bad, dev) if bad is not None else None
 
+            def process(lg, gen, n_dev=None, n_add=0):
+                if proc is not None:
+                    ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
+                if bad_t is not None:  # bad_words_ids: one more launch behind the processors, on the same history
+                    ops.seq_ban(lg, V, gen, bad_t, n_dev, n_add, hist, hist_len)
+        stopped = None                # stop_sequences: stopped(generated ids [B, n_max], done, n_dev, n_add) behind an emit
+        if stop is not None:
+            stop_t = ops.SeqTable(stop, dev)
+
+            def stopped(gen, done, n_dev=None, n_add=0):
+                ops.stop_match(gen, stop_t, done, n_dev, n_add)
+        if process is not None or stopped is not None:
             gen_buf = torch.full((Bs, max_new_tokens), pad, dtype=torch.long, device=dev)  # the eager loops' ids so far
         w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
 
@@ -1171,7 +1252,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 lps.append((torch.where(done, torch.zeros_like(lp), lp),
                             torch.where(done[:, None], pads[:, None], ti) if n_top else None,
                             torch.where(done[:, None], torch.zeros_like(tl), tl) if n_top else None))
-            return nxt, done | (nxt == eos_token_id)
+            done = done | (nxt == eos_token_id)
+            if stopped is not None:   # behind the log-probabilities' look at the flags: the stop token keeps its value
+                stopped(gen_buf, done, n_add=t + 1)
+            return nxt, done
 
         lps = []                      # return_logprobs in the eager loops: per new token (lp [B], top ids, top values)
 
@@ -1304,7 +1388,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                                  length_penalty, early_stopping, graph))
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
             return self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
-                                        process, n_top, feed)
+                                        process, n_top, feed, stopped)
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
         done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
@@ -1500,11 +1584,13 @@ class MM_LLMs(PreTrainedModel):
                 guide = dict(guidance_scale=GUIDANCE[0],
                              negative_inputs_embeds=ops.embedding_fwd(E, ids.reshape(-1)).view(*ids.shape, -1),
                              negative_prompt_attention_mask=inputs.get("attention_mask") if GENERATE_MASK[0] else None)
+            # stop sequences / bad words set: passed on; unset: exactly the call without them
+            stopping = {k: v for k, v in STOPPING[0].items() if v is not None}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
-                                     **guide, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
+                                     **guide, **stopping, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1604,6 +1690,17 @@ class MM_LLMs(PreTrainedModel):
         Process-wide switch, like set_sampling."""
         s = _guidance_check("set_guidance", guidance_scale)
         GUIDANCE[0] = 1.0 if s is None else s
+
+    @staticmethod
+    def set_stopping(stop_sequences=None, bad_words_ids=None):
+        """Stop sequences and banned words for `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the
+        same names): both off (None) by default.  forward passes embeddings only, so the history the banned words look at
+        is the generated tokens; a banned [2] is the call's eos and is dropped.  Validated here; what depends on the call
+        (beams, prompt lookup) is validated by generate().  No arguments: back to off.  Process-wide switch, like
+        set_logits_processors."""
+        _stopping_check("set_stopping", stop_sequences, bad_words_ids)
+        STOPPING[0] = dict(stop_sequences=None if stop_sequences is None else [list(q) for q in stop_sequences],
+                           bad_words_ids=None if bad_words_ids is None else [list(q) for q in bad_words_ids])
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

@@ -8,6 +8,7 @@ there is no eager / CPU fallback on the product path.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 from typing import Optional
 
@@ -805,6 +806,70 @@ def logits_process(logits, V, out, n_dev=None, n_add=0, prompt=None, prompt_len=
                                    float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
                                    -1 if eos is None else int(eos), dt(logits), _st()), "mk_logits_process")
     return logits
+
+
+MAX_SEQS, MAX_SEQ_LEN = 1 << 16, 64
+
+
+class SeqTable:
+    """a table of token sequences on the device (include/macaw_hip.h, "Token-sequence matching"), built once per call:
+    ids int64 [total], the sequences back to back, and off int32 [n + 1].  seqs: a non-empty list of non-empty lists of
+    ints, at most MAX_SEQS of at most MAX_SEQ_LEN ids"""
+
+    def __init__(self, seqs, dev):
+        seqs = [list(q) for q in seqs]
+        if not 1 <= len(seqs) <= MAX_SEQS or not all(1 <= len(q) <= MAX_SEQ_LEN for q in seqs):
+            raise MacawHipError(f"SeqTable: {len(seqs)} sequences of {min(map(len, seqs), default=0)} to "
+                                f"{max(map(len, seqs), default=0)} ids; expected 1 to {MAX_SEQS} of 1 to {MAX_SEQ_LEN}")
+        self.n = len(seqs)
+        self.ids = torch.tensor([c for q in seqs for c in q], dtype=torch.long).to(dev)
+        self.off = torch.tensor(list(itertools.accumulate(map(len, seqs), initial=0)), dtype=torch.int32).to(dev)
+
+
+def _gen_args(op, B, out, n_dev):
+    """the generated ids of the sequence matchers: out row-major int64 [B, n_max], n_dev int32 [>= 1] or None"""
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != B or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise MacawHipError(f"{op}: out {out.dtype} {tuple(out.shape)} {out.stride()}; expected row-major int64 [{B}, n]")
+    if n_dev is not None and (n_dev.dtype != torch.int32 or n_dev.numel() < 1):
+        raise MacawHipError(f"{op}: n_dev {n_dev.dtype} {tuple(n_dev.shape)}; expected int32 [>= 1]")
+
+
+def seq_ban(logits, V, out, table: SeqTable, n_dev=None, n_add=0, prompt=None, prompt_len=None):
+    """bad_words_ids in one launch, in place, behind logits_process and in front of a selection (see mk_seq_ban): the
+    last id of every sequence of `table` whose other ids are the tail of row b's history gets -inf.  logits [B, >= V]
+    row-major; the history is prompt[b, :prompt_len[b]] ++ out[b, :n], n = (n_dev[0] if n_dev is not None else 0) +
+    n_add, all as logits_process takes them.  Returns logits"""
+    lib = _L.load()
+    B = logits.shape[0]
+    _gen_args("seq_ban", B, out, n_dev)
+    P = p_ld = 0
+    if prompt is not None:
+        if (prompt.dtype != torch.int64 or prompt.dim() != 2 or prompt.shape[0] != B
+                or (prompt.shape[1] > 1 and prompt.stride(1) != 1)):
+            raise MacawHipError(f"seq_ban: prompt {prompt.dtype} {tuple(prompt.shape)} {prompt.stride()}; expected "
+                                f"row-major int64 [{B}, P]")
+        if (prompt_len is None or prompt_len.dtype != torch.int32 or prompt_len.numel() != B
+                or not prompt_len.is_contiguous()):
+            raise MacawHipError(f"seq_ban: prompt_len must be a contiguous int32 [{B}] next to a prompt")
+        P, p_ld = prompt.shape[1], max(prompt.stride(0), prompt.shape[1])
+    _L.check(lib.mk_seq_ban(_p(logits), _rowmajor(logits), V, B, _p(prompt), p_ld, P,
+                            _p(prompt_len) if prompt is not None else None, _p(out), max(out.stride(0), out.shape[1]),
+                            out.shape[1], _p(n_dev), int(n_add), _p(table.ids), _p(table.off), table.n, dt(logits), _st()),
+             "mk_seq_ban")
+    return logits
+
+
+def stop_match(out, table: SeqTable, done, n_dev=None, n_add=0):
+    """stop_sequences in one launch, right behind an emit (see mk_stop_match): done[b] (bool or uint8 [B], in place) is set
+    where row b has not finished and out[b, :n] ends with a sequence of `table`, n = (n_dev[0] if n_dev is not None else
+    0) + n_add -- the graph loop passes state[1:2], which the emit has advanced, a host loop its count"""
+    lib = _L.load()
+    B = out.shape[0]
+    _gen_args("stop_match", B, out, n_dev)
+    if done.dtype not in (torch.bool, torch.uint8) or done.numel() != B or not done.is_contiguous():
+        raise MacawHipError(f"stop_match: done {done.dtype} {tuple(done.shape)}; expected contiguous bool / uint8 [{B}]")
+    _L.check(lib.mk_stop_match(_p(out), max(out.stride(0), out.shape[1]), out.shape[1], B, _p(n_dev), int(n_add),
+                               _p(table.ids), _p(table.off), table.n, _p(done), _st()), "mk_stop_match")
 
 
 MAX_TOP_LOGPROBS = 20

@@ -53,6 +53,16 @@ with torch.no_grad():
 # the text-only prompt as the negative one (another length: the padded-batch path at 2B rows).  ms per token of every run, the
 # medians, guided - greedy(2B) and guided - greedy(B), the greedy run-to-run spreads, then the stand-alone time of one
 # ops.cfg_combine launch on [2B, 32000] logits against ops.decode_emit_logprobs (n = 0) and one embedding gather
+#        bench_generate.py --stop-ab [--reps R] [B ...]: greedy against stop_sequences (4 sequences) plus bad_words_ids (4
+# sequences) that never fire -- ids above the model's vocabulary V (the lm_head's rows), which it cannot emit -- so both arms run
+# the same 72 tokens and the difference is the two launches per step (ops.seq_ban in front of the emit, ops.stop_match behind
+# it), alternated the same way: ms per token of every run, the medians, their difference and the greedy run-to-run spread (the
+# difference counts only beyond it).  A third arm times the 72-token call alone with every sample stopping on a sequence at its
+# LAST column (each row's own last ids; skipped where a row's ids repeat so that it would stop earlier): against the never-fire
+# call of 72 tokens the difference is the search for the returned width behind the loop (one ops.stop_match launch per column).
+# Then the stand-alone time of one ops.seq_ban / ops.stop_match launch (tables of 4 and of 1000 sequences) against
+# ops.decode_emit on [B, V] logits with 100 generated ids
+STOP = "--stop-ab" in sys.argv
 CFG = "--cfg-ab" in sys.argv
 LOGPROBS = "--logprobs-ab" in sys.argv
 LOOKUP = "--lookup-ab" in sys.argv
@@ -67,7 +77,85 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if STOP:
+    from macaw_llm_amd import ops
+    V = model.llm.lm_head.weight.shape[0]
+    # the last id of every sequence lies above the vocabulary: no emitted tail ever equals one, no column is ever banned
+    SKW = dict(stop_sequences=[[13, 29871, V + i] for i in range(3)] + [[V + 7]],
+               bad_words_ids=[[13, V + i] for i in range(3)] + [[V + 9]])
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {"greedy": [], "stop+ban": []}
+        call72 = {"greedy": [], "stop+ban": [], "all stop at 71": []}       # the whole 72-token call, ms
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for mode in ms:                         # untimed: each mode's first call at this batch size
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=-1, **(SKW if mode != "greedy" else {}))
+            # every sample stops at column 71: each row's own last 16 ids, unless some row's ids end with a sequence earlier
+            rows = model.llm.generate(inputs_embeds=emb, max_new_tokens=72, eos_token_id=-1).tolist()
+            last = [r[56:] for r in rows]
+            early = any(r[c - 15:c + 1] == q for r in rows for q in last for c in range(15, 71))
+            LKW = None if early else dict(stop_sequences=last, bad_words_ids=SKW["bad_words_ids"])
+            if LKW is not None:
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=72, eos_token_id=-1, **LKW)
+            for rep in range(REPS):
+                for mode in ("greedy", "stop+ban"):
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        ids = model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, **(SKW if mode != "greedy" else {}))
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                        assert ids.shape[1] == new, f"stopped early at {ids.shape[1]} of {new} tokens: the timing would be of another loop"
+                    ms[mode].append((t[72] - t[8]) / 64 * 1e3)
+                    call72[mode].append(t[72] * 1e3)
+                    print(f"B={B:2d} rep {rep} {mode:8s}: decode {ms[mode][-1]:6.3f} ms/token", flush=True)
+                if LKW is not None:
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    ids = model.llm.generate(inputs_embeds=emb, max_new_tokens=72, eos_token_id=-1, **LKW)
+                    torch.cuda.synchronize(); call72["all stop at 71"].append((time.perf_counter() - t0) * 1e3)
+                    assert ids.tolist() == rows, "the samples did not all stop at the last column"
+        m72 = {k: sorted(v)[len(v) // 2] for k, v in call72.items() if v}
+        print(f"B={B:2d}: the 72-token call, prefill included: " + ", ".join(f"{k} {v:8.3f} ms" for k, v in m72.items()) +
+              (f"; all stop at 71 - stop+ban = {(m72['all stop at 71'] - m72['stop+ban']) * 1e3:+7.1f} us per call (the width search: "
+               f"72 stop_match launches and two host reads), stop+ban spread {(max(call72['stop+ban']) - min(call72['stop+ban'])) * 1e3:6.1f} us"
+               if "all stop at 71" in m72 else "; all stop at 71: not measured (a row's ids repeat)"), flush=True)
+        med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+        spread = max(ms["greedy"]) - min(ms["greedy"])
+        diff = med["stop+ban"] - med["greedy"]
+        print(f"B={B:2d}: greedy {med['greedy']:6.3f} ms/token, stop+ban {med['stop+ban']:6.3f} ms/token, stop+ban - greedy = "
+              f"{diff * 1e3:+7.1f} us ({diff / med['greedy'] * 100:+5.2f} %), greedy run-to-run spread {spread * 1e3:6.1f} us "
+              f"({spread / med['greedy'] * 100:4.1f} %): {'inside' if abs(diff) <= spread else 'OUTSIDE'} the spread", flush=True)
+        # one launch by itself: 200 back-to-back launches between two events, after 20 warm-up launches
+        x = torch.randn(B, V, device=dev).mul_(3).to(torch.bfloat16)
+        g = torch.Generator(device=dev).manual_seed(3)
+        out = torch.randint(0, V, (B, 256), generator=g, device=dev)
+        tok, done = torch.zeros(B, dtype=torch.long, device=dev), torch.zeros(B, dtype=torch.bool, device=dev)
+        out_e = torch.zeros((B, 256), dtype=torch.long, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        n_dev = torch.tensor([100], dtype=torch.int32, device=dev)
+        small = ops.SeqTable(SKW["bad_words_ids"], dev)
+        big = ops.SeqTable([[int(c) for c in torch.randint(0, V, (3,), generator=g, device=dev)] + [V + 1] for _ in range(1000)], dev)
+        us = {}
+        for name, fn in (("decode_emit", lambda: ops.decode_emit(x, V, 0, -1, tok, done, out_e, st)),
+                         ("seq_ban 4 seqs", lambda: ops.seq_ban(x, V, out, small, n_dev)),
+                         ("seq_ban 1000 seqs", lambda: ops.seq_ban(x, V, out, big, n_dev)),
+                         ("stop_match 4 seqs", lambda: ops.stop_match(out, small, done, n_dev)),
+                         ("stop_match 1000 seqs", lambda: ops.stop_match(out, big, done, n_dev))):
+            for i in range(20):
+                fn()
+            st.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
+            st.zero_()
+        assert not bool(done.any())
+        print(f"B={B:2d}: one launch on [B, {V}] bf16 logits / 100 generated ids (back to back, incl. launch gaps): " +
+              ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if CFG:
     from macaw_llm_amd import ops
     for B in [int(a) for a in _args] or [1, 8, 16]:
