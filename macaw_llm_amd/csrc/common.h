@@ -274,6 +274,23 @@ MK_DEV bool mk_keep(uint64_t seed, uint64_t idx, uint32_t keep_threshold) {
 }
 
 static inline int mk_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- what mk_decode_linear, mk_decode_linear_fp8 and mk_decode_linear_mxfp4 check and choose alike: the token side of
+// the skinny16 stream kernels does not depend on the weight format.  MK_OK with *wide and *lds set, or the code to
+// return.  kmult: the K-block of the format's kernel (16-byte loads of both operands); the weight pitch and the
+// scale / exponent operands are the caller's to check.
+static inline int mk_decode_linear_plan(const void* x, int64_t ldx, const void* W, const void* y, int M, int N, int K,
+                                        int kmult, int prologue, const void* norm_w, int dtype, bool* wide, size_t* lds) {
+  if (!x || !W || !y || M <= 0 || N <= 0 || K <= 0) return MK_ERR_BAD_ARG;
+  if (prologue < 0 || prologue > 2 || (prologue == 1 && !norm_w)) return MK_ERR_BAD_ARG;
+  if ((dtype != MK_BF16 && dtype != MK_F16) || M > (prologue ? 16 : 32) || (K % kmult) || (ldx % 8) || !aligned16(x) ||
+      !aligned16(W) || (prologue == 1 && !aligned16(norm_w)))
+    return MK_ERR_UNSUPPORTED;
+  *wide = N <= 16 * 256 && K <= 4096;                       // 16 waves where N / 16 workgroups are few
+  *lds = prologue ? (size_t)M * (K + 8) * 2 : 0;            // prepared token rows
+  return *lds > 40 * 1024 ? MK_ERR_UNSUPPORTED : MK_OK;     // (two workgroups per CU must still fit)
+}
 
 // live launch profiler (implemented in gemm.hip): see mk_prof_begin / mk_prof_sum
 namespace mkp {

@@ -1,6 +1,8 @@
 // The MXFP4 row quantiser, the MXFP4 weight-streaming kernel of mk_decode_linear_mxfp4 and its launcher, included once
 // per element type (MK_E16_T / MK_E16_NS, see decode_mxfp4.hip).  e16 = bf16 or _Float16: the type of the tokens, the
 // residual and the output, and the type the e2m1 codes are widened to in registers.
+#include "skinny16_parts.inc"   // the token prologue and the cross-wave reduction of the skinny16 stream kernels
+
 namespace {
 namespace MK_E16_NS {
 typedef MK_E16_T e16;
@@ -82,9 +84,9 @@ void launch_mxfp4_quantize_rows(const void* x, int rows, int cols, long ld, uint
 
 // decode_linear_fp8_kernel (decode_fp8_impl.inc) with the weight operand read as MXFP4: 16 weight rows per workgroup
 // (N / 16 workgroups), NW waves that split K in blocks, a ring of NBUF register buffers so that the loads of the next
-// trips are in flight under the MFMAs of this one, the same three token prologues with the same rounding points
-// (PRO 1 RMSNorm / 2 SwiGLU, token rows prepared in LDS), MT = 2 token tiles for 17 ... 32 plain rows, and the same
-// fixed-order cross-wave reduction.
+// trips are in flight under the MFMAs of this one, the same three token prologues (PRO 1 RMSNorm / 2 SwiGLU, token
+// rows prepared in LDS), MT = 2 token tiles for 17 ... 32 plain rows, and the same fixed-order cross-wave reduction:
+// the code of both is skinny16_parts.inc.
 // A K-block is 128 elements = 64 BYTES of a weight row, so one 16-byte load per lane still covers it: lane (r16, kq)
 // holds k = 32 kq ... 32 kq + 31 of weight row r16 -- exactly one MX block, one scale -- and dword j of the load
 // feeds MFMA j of the block's four.  The token operand follows: its four 16-byte loads of a block are the 64
@@ -154,46 +156,8 @@ __global__ __launch_bounds__(NW * 64) void decode_linear_mxfp4_kernel(DecodeMxfp
 #pragma unroll
   for (int i = 0; i < NBUF - 1; ++i)
     if (kb + i * STEP < nkb) load(wbuf[i], ebuf[i], xbuf[i], kb + i * STEP);
-  if constexpr (PRO != 0) {       // the token rows, prepared once per workgroup (as decode_linear_fp8_kernel)
-    e16* ts = reinterpret_cast<e16*>(sk_smem);
-    const int nch = g.K / 8;                                // 16-byte chunks per row
-    for (int m = 0; m < g.M; ++m) {
-      const e16* xr = A + (long)m * g.ldx;
-      float rstd = 1.f;
-      if constexpr (PRO == 1) {
-        float ss = 0.f;
-        for (int c = threadIdx.x; c < nch; c += NW * 64) {
-          const e16x8 xv = *reinterpret_cast<const e16x8*>(xr + c * 8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ss += (float)xv[e] * (float)xv[e];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        __syncthreads();                                    // ssq of the previous row consumed
-        if (l == 0) ssq[w][0] = ss;
-        __syncthreads();
-        float tot = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) tot += ssq[ww][0];   // fixed order: deterministic
-        rstd = rsqrtf(tot / (float)g.K + g.pro_eps);
-      }
-      for (int c = threadIdx.x; c < nch; c += NW * 64) {
-        const e16x8 av = *reinterpret_cast<const e16x8*>(xr + c * 8);
-        e16x8 bv;
-        if constexpr (PRO == 1) bv = *reinterpret_cast<const e16x8*>(reinterpret_cast<const e16*>(g.pro_w) + c * 8);
-        else bv = *reinterpret_cast<const e16x8*>(xr + g.K + c * 8);
-        e16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float a = (float)av[e], b = (float)bv[e];
-          if constexpr (PRO == 1) o[e] = (e16)(b * rnd<e16>(a * rstd));
-          else o[e] = (e16)(rnd<e16>(a / (1.f + __expf(-a))) * b);
-        }
-        *reinterpret_cast<e16x8*>(ts + m * ldt + c * 8) = o;
-      }
-    }
-    __syncthreads();
-  }
+  if constexpr (PRO != 0)         // the token rows, prepared once per workgroup
+    skinny16_stage_tokens<NW, PRO>(A, g.ldx, g.M, g.K, g.pro_w, g.pro_eps, sk_smem, ssq, l, w);
   while (kb < nkb) {
 #pragma unroll
     for (int i = 0; i < NBUF; ++i) {
@@ -204,21 +168,12 @@ __global__ __launch_bounds__(NW * 64) void decode_linear_mxfp4_kernel(DecodeMxfp
       if (kb >= nkb) break;
     }
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    red[w][e][l] = acc[e];
-    if constexpr (MT == 2) red[w][4 + e][l] = acc2[e];
-  }
-  __syncthreads();
-  // D[i = weight row][j = token]: lane holds j = l & 15, i = 4 * (l >> 4) + e
+  skinny16_reduce_put<NW, MT>(red, acc, acc2, l, w);
   e16* C = reinterpret_cast<e16*>(g.y);
   const e16* Rp = reinterpret_cast<const e16*>(g.residual);
   for (int t = threadIdx.x; t < 256 * MT; t += NW * 64) {
-    const int e = (t >> 6) & 3, ll = t & 63, mt = t >> 8;
-    float v = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < NW; ++ww) v += red[ww][4 * mt + e][ll];   // fixed order: deterministic
-    const int m = 16 * mt + (ll & 15), n = n0 + 4 * (ll >> 4) + e;
+    int m, n;
+    float v = skinny16_reduce_get<NW, MT>(red, t, n0, m, n);
     if (m >= g.M || n >= g.N) continue;
     if (Rp) v += (float)Rp[(long)m * g.ldr + n];
     C[(long)m * g.ldy + n] = (e16)v;

@@ -176,8 +176,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* in, T* out, int
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 
@@ -311,11 +309,10 @@ extern "C" int mk_decode_linear(const void* x, int64_t ldx, const void* W, int64
                                 int64_t ldy, const void* residual, int64_t ldr, int32_t M, int32_t N,
                                 int32_t K, int32_t prologue, const void* norm_w, float eps,
                                 int32_t dtype, void* stream) {
-  if (!x || !W || !y || M <= 0 || N <= 0 || K <= 0) return MK_ERR_BAD_ARG;
-  if (prologue < 0 || prologue > 2 || (prologue == 1 && !norm_w)) return MK_ERR_BAD_ARG;
-  if ((dtype != MK_BF16 && dtype != MK_F16) || M > (prologue ? 16 : 32) || (K % 64) || (ldx % 8) || (ldw % 8) ||
-      !aligned16(x) || !aligned16(W) || (prologue == 1 && !aligned16(norm_w)))
-    return MK_ERR_UNSUPPORTED;
+  bool wide;
+  size_t lds;
+  if (const int rc = mk_decode_linear_plan(x, ldx, W, y, M, N, K, 64, prologue, norm_w, dtype, &wide, &lds)) return rc;
+  if (ldw % 8) return MK_ERR_UNSUPPORTED;
   GemmArgs g{};
   g.A = x; g.B = W; g.C = y; g.R = residual;
   g.M = M; g.N = N; g.K = K;
@@ -323,9 +320,6 @@ extern "C" int mk_decode_linear(const void* x, int64_t ldx, const void* W, int64
   g.alpha = 1.f;
   g.pro_w = norm_w; g.pro_eps = eps;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool wide = N <= 16 * 256 && K <= 4096;     // as mk_gemm: 16 waves where N / 16 workgroups are few
-  const size_t lds = prologue ? (size_t)M * (K + 8) * 2 : 0;   // prepared token rows
-  if (lds > 40 * 1024) return MK_ERR_UNSUPPORTED;   // (two workgroups per CU must still fit)
   const int prof = mkp::begin(st, 0, 2.0 * M * N * K, M, N, K, 1, 0, 17 + 10 * prologue);
   if (M > 16) {                     // (no prologue: checked above) same kernels as mk_gemm's skinny path
     if (dtype == MK_F16) e_f16::launch_skinny(g, skinny32_cfg(N), N, st);

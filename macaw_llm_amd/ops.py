@@ -698,11 +698,17 @@ def decode_linear(x, W, prologue=0, norm_w=None, eps=0.0, residual=None, out=Non
     return out
 
 
+def _decode_linear_ok(x, W, K, kmult, prologue):
+    """the domain the three weight-streaming entry points share (mk_decode_linear_plan in csrc/common.h): kmult is
+    the K-block of the weight format's kernel; with a prologue the prepared token rows must fit 40 KiB of LDS"""
+    M = x.shape[0]
+    return (x.dtype in (torch.bfloat16, torch.float16) and M <= (16 if prologue else 32) and K % kmult == 0 and W.is_contiguous()
+            and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
+
+
 def decode_linear_ok(x, W, prologue=0):
     """mk_decode_linear's domain; with a prologue the prepared token rows must fit 40 KiB of LDS"""
-    M, K = x.shape[0], W.shape[1]
-    return (x.dtype in (torch.bfloat16, torch.float16) and M <= (16 if prologue else 32) and K % 64 == 0 and W.is_contiguous()
-            and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
+    return _decode_linear_ok(x, W, W.shape[1], 64, prologue)
 
 
 def decode_linear_fp8(x, Wq, s, prologue=0, norm_w=None, eps=0.0, residual=None, out=None):
@@ -749,9 +755,7 @@ def decode_linear_mxfp4(x, Wq, e, prologue=0, norm_w=None, eps=0.0, residual=Non
 def decode_linear_mxfp4_ok(x, W, prologue=0):
     """mk_decode_linear_mxfp4's domain (W: the uint8 codes [N, K / 2], or the [N, K] 16-bit weight they will be made
     from): decode_linear_ok's rule with K % 128 == 0 (a K-block is four MX blocks and one dword of exponents)"""
-    M, K = x.shape[0], (2 * W.shape[1] if W.dtype == torch.uint8 else W.shape[1])
-    return (x.dtype in (torch.bfloat16, torch.float16) and M <= (16 if prologue else 32) and K % 128 == 0 and W.is_contiguous()
-            and (prologue == 0 or M * (K + 8) * 2 <= 40 * 1024))
+    return _decode_linear_ok(x, W, 2 * W.shape[1] if W.dtype == torch.uint8 else W.shape[1], 128, prologue)
 
 
 def decode_emit(logits, V, pad, eos, tok, done, out, state):

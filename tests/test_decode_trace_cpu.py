@@ -9,8 +9,7 @@ trace), shape, stride, storage offset and dtype; a scalar as its value.  The pre
 launches (ops.decode_linear_ok, ops.decode_linear_fp8_ok, ops.decode_attn_ok, engine.flash_ok) are the real ones.
 
 One argument is recorded in a canonical form: `eps` of decode_linear / decode_linear_fp8 is None unless prologue = 1.
-The kernels read it only inside the RMSNorm prologue (csrc/gemm_impl.inc, csrc/decode_fp8_impl.inc: `if constexpr
-(PRO == 1)`), and the callers have always disagreed about what to pass where it is dead (0.0 or the layer's eps).
+The kernels read it only inside the RMSNorm prologue (csrc/skinny16_parts.inc: `if constexpr (PRO == 1)`), and the callers have always disagreed about what to pass where it is dead (0.0 or the layer's eps).
 
 The file of expected traces was written by `python tests/test_decode_trace_cpu.py --write` on the commit BEFORE the
 decode step got its single body and the streamed-linear helper, and must not be regenerated to make a change pass:

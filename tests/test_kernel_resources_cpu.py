@@ -104,7 +104,9 @@ def test_attention_and_streaming_kernels_keep_their_occupancy(ks):
         assert v["vgpr_count"] <= 256, (k, v)              # two waves per SIMD (two 4-wave workgroups or one of 8 waves)
     for k, v in _pick(ks, "adamw_multi_kernel").items():
         assert v["vgpr_count"] <= 72, (k, v)               # HBM-bound: >= 7 waves per SIMD in flight
-    for stem in ("gemm_skinny16_kernel", "gemm_skinny32p_kernel"):
+    # (the e4m3 and MXFP4 stream kernels share gemm_skinny16_kernel's token prologue and reduction, csrc/skinny16_parts.inc,
+    # and its budget: at most 114 and 110 VGPRs when they joined this list, so no instantiation needs an exception)
+    for stem in ("gemm_skinny16_kernel", "gemm_skinny32p_kernel", "decode_linear_fp8_kernel", "decode_linear_mxfp4_kernel"):
         for k, v in _pick(ks, stem).items():
             assert v["vgpr_count"] <= 128, (k, v)          # weight streaming: two 8-wave workgroups per CU
 
