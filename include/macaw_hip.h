@@ -795,6 +795,39 @@ int mk_decode_step_attn_multi(const void* q, const void* k_new, const void* v_ne
                               const void* sin_t, void* k_cache, void* v_cache, int64_t kv_ld, int64_t kv_bs, void* o,
                               int64_t o_bs, const int32_t* pos, int32_t t_max, int32_t B, int32_t Q, int32_t H,
                               int32_t hd, float scale, int32_t dtype, void* stream);
+/* Parallel sampling (generate(num_samples=n)): n samples drawn from ONE prompt.  The prompt's keys and values are stored
+ *   once per prompt, prompt cache [B][S0][2D] (p_ld the row pitch, p_bs the stride of a prompt; kp / vp its key and value
+ *   halves), and the rows' own tokens in a tail cache [B * n][Tn][2D] (t_ld, t_bs; kt / vt).  Row r = b * n + j of
+ *   q / k_new / v_new (row stride in_bs) and o (row stride o_bs) is sample j of prompt b.
+ * mk_decode_step_attn_shared: mk_decode_step_attn for those rows, one launch.  Per step:
+ *     i   = clamp(*t_dev - S0, 0, Tn - 1)                      the tail row, the same for every row of the launch
+ *     L_b = clamp(S0 + (t_off ? t_off[b] : 0), 0, S0)          the prompt's length (t_off int32 [B] on the device or null:
+ *                                                              a padded batch's compacted prompt, engine.Ragged.t_off)
+ *     p   = L_b + i                                            the row's position
+ *   q and k_new are rotated with table row p (mk_rope's rounding points); the rotated key and v_new go to tail row i of
+ *   row r; o = attention of the rotated query over prompt rows 0 ... L_b - 1 of prompt b followed by tail rows 0 ... i of
+ *   row r.  No prompt byte is written, no tail byte other than row i of each row is written, no tail row past i and no
+ *   prompt row past L_b - 1 is read.
+ *   One workgroup per (head, prompt, tile of R rows), R = 1 by default and R = 4 on request.  Each row of a tile runs through mk_decode_step_attn's own
+ *   kernel body -- the same key -> lane map, trips, online softmax and merge order, only the address of a key differs -- so
+ *   a row's output and appended key are BIT FOR BIT those of mk_decode_step_attn called for the row alone (B = 1, the
+ *   one-workgroup-per-head form) at *t_dev = p over a physically gathered cache [prompt rows 0 ... L_b - 1 | tail rows
+ *   0 ... i - 1].  The rows of a tile run one after the other in their workgroup and share the prompt's keys through the
+ *   cache hierarchy (row 0 brings a key from HBM, the others find it in L1 / L2); they do not share a register copy of it:
+ *   a body that applies one loaded key to R queries is other code, in which the compiler contracts other products and
+ *   sums, and its fp32 sums differ from the plain kernel's in their last bits.  n need not be a multiple of R.  One form at
+ *   every B * n * H (the four-heads-per-workgroup form is not tiled).  MK_SHARED_ATTN_ROWS=1 in the environment (read at
+ *   every call) selects the R = 1 instantiation (one workgroup per row, the default: the measured faster one,
+ *   profiles/decode_nsample_generate.txt), MK_SHARED_ATTN_ROWS=4 the tiled one; both give the same bits.
+ *   Domain, else MK_ERR_UNSUPPORTED and nothing is launched: that of mk_decode_step_attn (dtype bf16 / f16; hd in {16, 32,
+ *   64, 128}; alignment and strides), t_dev and t_off 4-byte aligned, n <= 32.  MK_ERR_BAD_ARG: a null pointer (t_off
+ *   excepted; kp / vp may be null when S0 == 0), B or H <= 0, n < 1, S0 < 0, Tn < 1.
+ *   Pinned by tests/test_shared_attn_gpu.py through mk_decode_step_attn, whose bits it reproduces row by row. */
+int mk_decode_step_attn_shared(const void* q, const void* k_new, const void* v_new, int64_t in_bs,
+                               const void* cos_t, const void* sin_t, const void* kp, const void* vp, int64_t p_ld,
+                               int64_t p_bs, void* kt, void* vt, int64_t t_ld, int64_t t_bs, void* o, int64_t o_bs,
+                               const int32_t* t_dev, const int32_t* t_off, int32_t S0, int32_t Tn, int32_t B, int32_t n,
+                               int32_t H, int32_t hd, float scale, int32_t dtype, void* stream);
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);

@@ -164,7 +164,10 @@ MK_DEV void rope8(const e16x8& xv, const e16x8& cv, const e16x8& sv, bool first,
 // MULTI (mk_decode_step_attn_multi): keys p0 ... p - 1 are the EARLIER rows of the same step, which other workgroups append
 // at the same time: their rotated keys come from knew (LDS, rotated by this workgroup) and their values from the step's
 // v_new rows (row 0 of the sample at element offset vn0) -- the bits the cache will hold -- and no cache row >= p0 is read.
-template <int HD, int NWV, bool BEAM, bool MULTI = false, typename A>
+// SHARED (mk_decode_step_attn_shared): b = the ROW, whose slot of a.kc / a.vc is its tail cache, p0 = the prompt's length:
+// key t < p0 is row t of the prompt cache of sample b / a.n, key p0 <= t < p tail row t - p0, and the new key goes to tail
+// row p - p0.  Only the address of a key differs.
+template <int HD, int NWV, bool BEAM, bool MULTI = false, bool SHARED = false, typename A>
 MK_DEV void decode_step_attn_body(const A& a, float (*red)[HD], float* redw, int h, int b, long in_row, long o_row, int p,
                                   int p0 = 0, const e16 (*knew)[HD] = nullptr, long vn0 = 0) {
   constexpr int LPK = HD / 8, KPW = 64 / LPK, KPP = NWV * KPW;
@@ -188,7 +191,8 @@ MK_DEV void decode_step_attn_body(const A& a, float (*red)[HD], float* redw, int
     e16x8 kb;
 #pragma unroll
     for (int e = 0; e < 8; ++e) kb[e] = (e16)kf[e];
-    const long off = (long)b * a.kv_bs + (long)p * a.kv_ld + (long)h * HD + d0;
+    long off = (long)b * a.kv_bs + (long)p * a.kv_ld + (long)h * HD + d0;
+    if constexpr (SHARED) off = (long)b * a.kv_bs + (long)(p - p0) * a.kv_ld + (long)h * HD + d0;
     *reinterpret_cast<e16x8*>(a.kc + off) = kb;
     *reinterpret_cast<e16x8*>(a.vc + off) = vnew;
   }
@@ -210,9 +214,15 @@ MK_DEV void decode_step_attn_body(const A& a, float (*red)[HD], float* redw, int
         kv[j] = *reinterpret_cast<const e16x8*>(&knew[t - p0][d0]);
         vv[j] = *reinterpret_cast<const e16x8*>(a.vn + vn0 + (long)(t - p0) * a.in_bs + (long)h * HD + d0);
       } else if (t < p) {
-        const long so = beam_slot_off<BEAM>(a, b, t);
-        kv[j] = *reinterpret_cast<const e16x8*>(K + so + (long)t * a.kv_ld);
-        vv[j] = *reinterpret_cast<const e16x8*>(V + so + (long)t * a.kv_ld);
+        if constexpr (SHARED) {
+          const long po = (long)(b / a.n) * a.p_bs + (long)t * a.p_ld + (long)h * HD + d0;
+          kv[j] = *reinterpret_cast<const e16x8*>(t < p0 ? a.kp + po : K + (long)(t - p0) * a.kv_ld);
+          vv[j] = *reinterpret_cast<const e16x8*>(t < p0 ? a.vp + po : V + (long)(t - p0) * a.kv_ld);
+        } else {
+          const long so = beam_slot_off<BEAM>(a, b, t);
+          kv[j] = *reinterpret_cast<const e16x8*>(K + so + (long)t * a.kv_ld);
+          vv[j] = *reinterpret_cast<const e16x8*>(V + so + (long)t * a.kv_ld);
+        }
       } else {
         vv[j] = vnew;
       }
@@ -567,6 +577,94 @@ int decode_step_attn_beam_impl(const void* q, const void* k_new, const void* v_n
   else if (hd == 64) MK_LAUNCH((decode_step_attn_kernel<64, 8, false, true>), grid, block, 0, st, a);
   else if (hd == 32) MK_LAUNCH((decode_step_attn_kernel<32, 8, false, true>), grid, block, 0, st, a);
   else MK_LAUNCH((decode_step_attn_kernel<16, 8, false, true>), grid, block, 0, st, a);
+  return mk_check_launch();
+}
+
+// SHARED (mk_decode_step_attn_shared): parallel sampling, n rows per sample over ONE prompt cache [B][S0] plus a tail cache
+// per row [B * n][Tn].  Row r = b * n + j is at position p = L_b + i, L_b = the sample's (compacted) prompt length and i the
+// tail row of the step: keys 0 ... L_b - 1 are prompt rows of sample b, keys L_b ... p - 1 tail rows 0 ... i - 1 of row r, key p
+// the new one.  The base's kc / vc / kv_ld / kv_bs describe the TAIL cache (one slot per row), t_max is not read.
+struct DecodeStepSharedArgs : DecodeStepArgs {
+  const e16* kp; const e16* vp; long p_ld, p_bs;            // prompt cache [S0][H * hd] per sample, read only
+  int S0, Tn, n;
+};
+
+// One workgroup per (head, sample, tile of R rows).  The rows of a tile run one after the other through
+// decode_step_attn_body -- the plain kernel's code, so its bits: the compiler decides where it contracts a product and a sum
+// inside that body, and a second formulation of the same arithmetic (one load of a key applied to R queries held in
+// registers was built first) comes out with other choices and other last bits of the fp32 sums.  The rows of a tile
+// therefore share the prompt's keys through the cache hierarchy: row 0 brings a key from HBM, rows 1 ... R - 1 of the same
+// workgroup re-read it from this CU's L1 or its XCD's L2 right behind it.  The last tile of a sample holds n - j0 < R rows.
+// R = 1 is the untiled form, one workgroup per row, and the default (shared_attn_rows below).
+template <int HD, int NWV, int R>
+__global__ __launch_bounds__(NWV * 64) void decode_step_attn_shared_kernel(DecodeStepSharedArgs a) {
+  __shared__ float red[NWV][HD];
+  __shared__ float redw[2 * NWV];
+  const int tiles = (a.n + R - 1) / R;
+  const int h = blockIdx.x, b = blockIdx.y / tiles, j0 = (blockIdx.y % tiles) * R;
+  const int nr = min(R, a.n - j0);
+  const int i = (int)min(max((long)*a.t_dev - a.S0, 0L), (long)a.Tn - 1);
+  const int L = (int)min(max((long)a.S0 + (a.t_off ? a.t_off[b] : 0), 0L), (long)a.S0);
+#pragma unroll 1
+  for (int r = 0; r < nr; ++r) {
+    const long row = (long)b * a.n + j0 + r;
+    if (r > 0) __syncthreads();          // red / redw serve the next row
+    decode_step_attn_body<HD, NWV, false, false, true>(a, red, redw, h, (int)row, row * a.in_bs, row * a.o_bs, L + i, L);
+  }
+}
+
+// rows per workgroup of the tiled form, and the instantiation MK_SHARED_ATTN_ROWS selects (read at every call, so one
+// process can measure both; a captured step keeps the one it was captured with).  The default is the untiled form: with H a
+// multiple of 8 the workgroups of a (head, sample) already share an XCD's L2, and the tile's serial rows cost more than its
+// locality returns (profiles/decode_nsample_generate.txt, 1916-row prompt: -0.3 % at (B, n) = (2, 16), +12 % at (8, 4), +59 % at (1, 4))
+constexpr int SHARED_ROWS = 4, SHARED_ROWS_DEFAULT = 1;
+inline int shared_attn_rows() {
+  const char* e = getenv("MK_SHARED_ATTN_ROWS");
+  if (e && atoi(e) == 1) return 1;
+  if (e && atoi(e) == SHARED_ROWS) return SHARED_ROWS;
+  return SHARED_ROWS_DEFAULT;
+}
+
+template <int HD>
+void decode_step_attn_shared_launch(const DecodeStepSharedArgs& a, int B, int H, hipStream_t st) {
+  const dim3 block(512);
+  if (shared_attn_rows() == 1)
+    MK_LAUNCH((decode_step_attn_shared_kernel<HD, 8, 1>), dim3(H, B * a.n), block, 0, st, a);
+  else
+    MK_LAUNCH((decode_step_attn_shared_kernel<HD, 8, SHARED_ROWS>), dim3(H, B * ((a.n + SHARED_ROWS - 1) / SHARED_ROWS)),
+              block, 0, st, a);
+}
+
+// mk_decode_step_attn_shared: the plain entry point's checks over B * n rows and two caches
+int decode_step_attn_shared_impl(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                                 const void* sin_t, const void* kp, const void* vp, int64_t p_ld, int64_t p_bs, void* kt,
+                                 void* vt, int64_t t_ld, int64_t t_bs, void* o, int64_t o_bs, const int32_t* t_dev,
+                                 const int32_t* t_off, int32_t S0, int32_t Tn, int32_t B, int32_t n, int32_t H, int32_t hd,
+                                 float scale, int32_t dtype, void* stream) {
+  if (!q || !k_new || !v_new || !cos_t || !sin_t || !kt || !vt || !o || !t_dev || B <= 0 || H <= 0 || S0 < 0 || Tn < 1 ||
+      n < 1 || (S0 > 0 && (!kp || !vp)))
+    return MK_ERR_BAD_ARG;
+  if (dtype != E16<e16>::dtype || (hd != 16 && hd != 32 && hd != 64 && hd != 128) || n > 32) return MK_ERR_UNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_new) |
+                       reinterpret_cast<uintptr_t>(v_new) | reinterpret_cast<uintptr_t>(cos_t) |
+                       reinterpret_cast<uintptr_t>(sin_t) | reinterpret_cast<uintptr_t>(kp) |
+                       reinterpret_cast<uintptr_t>(vp) | reinterpret_cast<uintptr_t>(kt) | reinterpret_cast<uintptr_t>(vt);
+  if ((al & 15) || ((reinterpret_cast<uintptr_t>(t_dev) | reinterpret_cast<uintptr_t>(t_off)) & 3) || (in_bs % 8) ||
+      (p_ld % 8) || (p_bs % 8) || (t_ld % 8) || (t_bs % 8) || (long)B * ((n + SHARED_ROWS - 1) / SHARED_ROWS) > 65535 ||
+      (long)B * n > 65535)
+    return MK_ERR_UNSUPPORTED;
+  DecodeStepSharedArgs a;
+  a.q = (const e16*)q; a.kn = (const e16*)k_new; a.vn = (const e16*)v_new; a.in_bs = in_bs;
+  a.cos_t = (const e16*)cos_t; a.sin_t = (const e16*)sin_t;
+  a.kp = (const e16*)kp; a.vp = (const e16*)vp; a.p_ld = p_ld; a.p_bs = p_bs;
+  a.kc = (e16*)kt; a.vc = (e16*)vt; a.kv_ld = t_ld; a.kv_bs = t_bs;
+  a.o = (e16*)o; a.o_bs = o_bs;
+  a.t_dev = t_dev; a.t_off = t_off; a.t_max = Tn; a.S0 = S0; a.Tn = Tn; a.n = n; a.scale = scale;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hd == 128) decode_step_attn_shared_launch<128>(a, B, H, st);
+  else if (hd == 64) decode_step_attn_shared_launch<64>(a, B, H, st);
+  else if (hd == 32) decode_step_attn_shared_launch<32>(a, B, H, st);
+  else decode_step_attn_shared_launch<16>(a, B, H, st);
   return mk_check_launch();
 }
 

@@ -691,6 +691,15 @@ class Spec(NamedTuple):
     Q: int                   # rows per sample
 
 
+class SharedPrompt(NamedTuple):
+    """a parallel-sampling step for llama_layer_cached (generate(num_samples=n)), passed IN PLACE of the cache tensor kvc:
+    the prompt's keys once per prompt and the rows' own tokens per row.  Row b * n + j is sample j of prompt b"""
+    prompt: torch.Tensor     # [B, S0, 2D]: the cache the prefill wrote at B rows (Tmax = S0); a padded batch's compacted rows
+    tail: torch.Tensor       # [B * n, Tn, 2D]: tail row i holds the row's token of step i
+    n: int                   # samples per prompt
+    S0: int                  # prompt rows per sample of `prompt`
+
+
 def ragged_from_mask(mask, B, S0):
     """The host side of generate(attention_mask=): mask [B, S0], any integer or bool dtype, non-zero = valid.
     Returns None for a mask without a zero (the unpadded path), else (Ragged, pos, last):
@@ -721,7 +730,13 @@ def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, s
     """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
     e4m3 cache, kvc its bytes) ops.decode_step_attn_kv8; with ragged (a padded batch) their per-sample-position forms;
     with beam (a Beam; B samples of beam.K rows each) ops.decode_step_attn_beam over the [B, K, Tmax, 2D] cache; with
-    spec (a Spec; B samples of spec.Q rows each) ops.decode_step_attn_multi at the per-sample positions spec.pos"""
+    spec (a Spec; B samples of spec.Q rows each) ops.decode_step_attn_multi at the per-sample positions spec.pos; with kvc
+    a SharedPrompt (B prompts of kvc.n rows each) ops.decode_step_attn_shared over its two buffers, ragged.t_off passed
+    through for a padded batch"""
+    if isinstance(kvc, SharedPrompt):
+        return ops.decode_step_attn_shared(q, k, v, in_bs, cos, sin, kvc.prompt, kvc.tail, t_dev,
+                                           ragged.t_off if ragged is not None else None, kvc.S0, B, kvc.n, H, hd, att, scale,
+                                           **off)
     if spec is not None:
         return ops.decode_step_attn_multi(q, k, v, in_bs, cos, sin, kvc, spec.pos, Tmax, B, spec.Q, H, hd, att, scale, **off)
     if beam is not None:
@@ -807,9 +822,19 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     spec (a Spec; decode steps with t_dev only, Sn = spec.Q): a prompt-lookup verify step.  x2 holds the B * spec.Q rows
     (b, g), row g of sample b at position spec.pos[b] + g; the step attention is ops.decode_step_attn_multi, which
     appends the Q new rows of a sample and lets row g attend over the cache up to its own position; every other launch
-    sees B * Q token rows and is unchanged.  Not with kv8, ragged or beam, and not with a host position."""
+    sees B * Q token rows and is unchanged.  Not with kv8, ragged or beam, and not with a host position.
+
+    kvc a SharedPrompt (decode steps with t_dev only): a parallel-sampling step.  B stays the number of PROMPTS and x2
+    holds the B * kvc.n rows; the step attention is ops.decode_step_attn_shared over kvc.prompt (stored once per prompt)
+    and kvc.tail (per row), every other launch sees B * n token rows and is unchanged.  Tmax is not read.  The prefill
+    of such a cache is an ordinary call at B rows on kvc.prompt with Tmax = S0 (with ragged: the compacting write, and
+    the steps then pass ragged.t_off on).  Not with kv8, beam or spec, and not with a host position."""
     M, D = x2.shape
     dyn = t_dev is not None
+    if isinstance(kvc, SharedPrompt) and (not dyn or kv8 is not None or beam is not None or spec is not None or
+                                          M != B * kvc.n):
+        raise ValueError("llama_layer_cached: a SharedPrompt cache takes single-position decode steps (t_dev) of B * n rows "
+                         "on the 16-bit cache, not kv8, beam, spec or a host position")
     if spec is not None:
         if not dyn or kv8 is not None or ragged is not None or beam is not None or Sn != spec.Q or M != B * spec.Q:
             raise ValueError("llama_layer_cached: spec takes decode steps at device positions (t_dev) of B * Q rows "

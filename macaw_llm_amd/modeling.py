@@ -75,6 +75,8 @@ LOGPROBS = [dict(return_logprobs=False, top_logprobs=0)]
 GUIDANCE = [1.0]
 # MM_LLMs.set_stopping: the stop_sequences and bad_words_ids MM_LLMs.forward hands to generate() (only when one is set)
 STOPPING = [dict(stop_sequences=None, bad_words_ids=None)]
+# MM_LLMs.set_parallel_samples: the num_samples MM_LLMs.forward hands to generate() (1 = off: the call without it)
+PARALLEL_SAMPLES = [1]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -184,6 +186,14 @@ def _guidance_check(where, guidance_scale):
     if isinstance(s, bool) or not isinstance(s, numbers.Real) or not math.isfinite(s):
         raise ValueError(f"{where}: guidance_scale must be None or a finite number (1 = off), got {s!r}")
     return None if s == 1 else float(s)
+
+
+def _num_samples_check(where, num_samples):
+    """the num_samples of generate() / set_parallel_samples -> n, the samples drawn per prompt (1 = off)"""
+    n = num_samples
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 1 <= n <= ops.SHARED_MAX_N:
+        raise ValueError(f"{where}: num_samples must be an integer in [1, {ops.SHARED_MAX_N}], got {n!r}")
+    return int(n)
 
 
 def _guided_batch(scale, emb, mask, neg, neg_mask):
@@ -872,7 +882,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
                  negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
-                 bad_words_ids=None, **_):
+                 bad_words_ids=None, num_samples=1, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -1066,7 +1076,28 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         processors, a padded mask, log-probabilities, guidance, use_cache=False (any dtype) and LoRA.  ValueError naming
         the argument for a value that is not a non-empty list of non-empty lists of integers >= 0, more than 65536
         sequences, a sequence longer than 64, and either argument with num_beams > 1 or prompt_lookup_num_tokens > 0
-        (not built).  None (default): nothing is allocated, launched or read."""
+        (not built).  None (default): nothing is allocated, launched or read.
+
+        num_samples=n in [1, 32] with do_sample=True: parallel sampling, n samples drawn from every prompt (vLLM's and
+        OpenAI's n; HF's num_return_sequences under do_sample, which here stays a beam argument).  Returns ids [B * n,
+        width], row b * n + j sample j of prompt b, pad_token_id behind each row's own end.  The random number of (row r,
+        new token t) is the counter hash of (seed, t, r): what a batch of B * n repeated prompts draws, so the call is that
+        batch up to the last bits of its arithmetic (the prefill's GEMMs see B rows, and the repeated batch may select
+        another attention form).  The prefill, and with MM_LLMs the towers and the alignment, run ONCE per prompt at B
+        rows into a prompt cache [B, S0, 2D] per layer; the rows' own tokens go to a tail cache [B * n, max_new_tokens,
+        2D]; the prompt's last hidden row is gathered to its n rows, and every decode step runs B * n token rows whose
+        attention (ops.decode_step_attn_shared, engine.SharedPrompt) reads the one copy of the prompt's keys -- the prompt is
+        not stored n times, and what its rows re-read comes from cache.  Still one hipGraph replay per token, and the host reads nothing
+        new; decode_graph=False, MACAW_NO_DECODE_GRAPH and max_new_tokens <= 2 run the same launches kernel by kernel at a
+        device position.  Composes with decode_weights (their limit becomes B * n <= 32), temperature / top_k / top_p,
+        the processors and bad_words_ids (the history of row r is its prompt's ids followed by its own tokens),
+        stop_sequences (each row ends by itself), log-probabilities, a padded attention_mask (the compacted prompt cache,
+        one offset per prompt), LoRA, and use_cache=False (the prompt repeated n times through the recompute loop; any
+        dtype; test reference).  ValueError naming the condition for n not an integer in [1, 32]; for n > 1 with
+        do_sample=False (n identical greedy rows: HF refuses it too), with num_beams > 1, prompt_lookup_num_tokens > 0,
+        guidance_scale or kv_cache="fp8" (not built); and for n > 1 with use_cache=True and fp32 parameters or a shape
+        outside ops.shared_attn_ok / ops.decode_attn_ok (use use_cache=False).  1 (default): today's call -- nothing is
+        allocated, gathered or launched differently."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1131,6 +1162,24 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
             sample = (temperature, top_k, top_p, int(seed))
+        N = 1                     # num_samples: the rows per prompt (1: off, nothing below runs)
+        if not (type(num_samples) is int and num_samples == 1):
+            N = _num_samples_check("generate", num_samples)
+        if N > 1:
+            what = f"generate(num_samples={N})"
+            if not do_sample:
+                raise ValueError(f"{what} with do_sample=False: greedy decoding would return {N} identical rows per prompt; "
+                                 "pass do_sample=True")
+            if K > 1:
+                raise ValueError(f"{what} with num_beams={K}: parallel samples of a beam search are not built; use "
+                                 "num_beams=1")
+            if G:
+                raise ValueError(f"{what} with prompt_lookup_num_tokens={G}: a verify step over a shared prompt cache is not "
+                                 "built")
+            if cfg is not None:
+                raise ValueError(f"{what} with guidance_scale={guidance_scale!r}: guided parallel samples are not built")
+            if kv_cache == "fp8":
+                raise ValueError(f"{what} with kv_cache='fp8': a quantised shared-prompt cache is not built")
         no_graph = _no_decode_graph(decode_graph, max_new_tokens)
         graph = no_graph is None  # the decode step is captured in a hipGraph (the greedy loop also needs decode_attn_ok)
 
@@ -1138,6 +1187,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if inputs_embeds is None:
             inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(*input_ids.shape, -1)
         _dev_check(inputs_embeds)
+        if N > 1 and not use_cache:   # the prompt repeated N times through the recompute loop: a batch of B * N rows
+            inputs_embeds = inputs_embeds.repeat_interleave(N, 0)
+            attention_mask = attention_mask.repeat_interleave(N, 0) if attention_mask is not None else None
+            input_ids = input_ids.repeat_interleave(N, 0) if input_ids is not None else None
+            N = 1
         B, S0, D = inputs_embeds.shape
         dev, dtype = inputs_embeds.device, inputs_embeds.dtype
         Bs, Sc, own_mask = B, S0, attention_mask     # the samples, their prompt's length and mask as the caller gave them
@@ -1179,8 +1233,15 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if why is not None:
                 raise ValueError(f"generate(num_beams={K}) with use_cache=True: {why}; the beam step attention takes bf16 / "
                                  "fp16 inside ops.decode_attn_ok: pass use_cache=False")
+        if N > 1:                 # (use_cache=True: the other case became a batch of B * N rows above)
+            why = _attn_refusal(dtype, hd, Tmax)
+            if why is None and not ops.shared_attn_ok(dtype, hd, N):
+                why = f"ops.shared_attn_ok is false for head size {hd} and {N} rows per prompt"
+            if why is not None:
+                raise ValueError(f"generate(num_samples={N}) with use_cache=True: {why}; the shared-prompt step attention "
+                                 "takes bf16 / fp16 inside ops.shared_attn_ok and ops.decode_attn_ok: pass use_cache=False")
         if decode_weights is not None:
-            _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, value=decode_weights, beams=K,
+            _decode_fp8_check(dtype, hd, B * N, S0, max_new_tokens, use_cache, no_graph, value=decode_weights, beams=K,
                               guided=cfg is not None)
         if kv_cache == "fp8":
             _decode_fp8_check(dtype, hd, B, S0, max_new_tokens, use_cache, no_graph, switch="kv_cache")
@@ -1200,6 +1261,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                  "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
                                  "there is no masked attention over a cache: pass use_cache=False")
 
+        if N > 1:                 # from here on the emits, the books and the processors count the B * N rows
+            Bs = B * N
+            if hist is not None:  # row r's history starts with its prompt's ids
+                hist, hist_len = hist.repeat_interleave(N, 0).contiguous(), hist_len.repeat_interleave(N).contiguous()
         process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add)
         if proc is not None or bad is not None:
             bad_t = ops.SeqTable(bad, dev) if bad is not None else None
@@ -1311,6 +1376,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             kvc, kvs = zip(*(ops.kv8_cache(B, Tmax, D // hd, hd, dev) for _ in layers))
         elif K > 1:               # one slot per beam; the prompt lives in slot 0 of its sample only
             kvc = [torch.empty((B, K, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]
+        elif N > 1:               # the prompt's rows once per prompt, the rows' own tokens per row (engine.SharedPrompt)
+            kvc = [torch.empty((B, S0, 2 * D), dtype=dtype, device=dev) for _ in layers]
+            tails = [torch.empty((B * N, max_new_tokens, 2 * D), dtype=dtype, device=dev) for _ in layers]
         else:
             kvc = [torch.empty((B, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]   # [keys | values]
 
@@ -1331,7 +1399,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
 
         w8 = None                 # decode_weights="fp8" / "mxfp4": per layer the copies of q|k|v, o, gate|up, down
         if decode_weights is not None:
-            probe = torch.empty((B * K * (G + 1), 0), dtype=dtype, device=dev)     # the token rows of a step
+            probe = torch.empty((B * N * K * (G + 1), 0), dtype=dtype, device=dev)     # the token rows of a step
 
             def q8(W, own):       # own: a stored parameter (version-keyed cache); else a merged copy of this call
                 if W is None or not ops.decode_linear_fp8_ok(probe, W):
@@ -1362,6 +1430,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 ws = merged.get(lyr, stored[i])
                 if K > 1 and beam is None:        # the prefill of a beam cache: B rows into slot 0 of every sample
                     cache_i, tmax_i = kvc[i].view(B, K * Tmax, 2 * D), K * Tmax
+                elif N > 1:                       # parallel samples: the prefill writes the prompt cache, a step reads both
+                    cache_i, tmax_i = (kvc[i], S0) if t_dev is None else (eng.SharedPrompt(kvc[i], tails[i], N, S0), Tmax)
                 else:
                     cache_i, tmax_i = kvc[i], Tmax
                 x2 = eng.llama_layer_cached(
@@ -1379,6 +1449,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0)             # prefill
             last = torch.empty((B, D), dtype=dtype, device=dev)
             ops.copy2d(h, last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
+        if N > 1:                 # the prompt's last hidden row, once per row of its samples
+            last = ops.embedding_fwd(last, torch.arange(B, device=dev).repeat_interleave(N))
         if G:
             ids, steps = self._generate_lookup(run, logits, last, emb_w, B, G, S0, max_new_tokens, eos_token_id, pad, dev,
                                                max_matching_ngram_size, hist, hist_len, graph)
@@ -1389,8 +1461,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
             return self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
                                         process, n_top, feed, stopped)
-        # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch
-        t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if ragged is not None else None
+        # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch or of
+        # parallel samples
+        dyn = ragged is not None or N > 1         # (parallel samples take the padded batch's route: a device position)
+        t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if dyn else None
         done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
         for t in range(max_new_tokens):
             nxt, done = select(last, t, done)
@@ -1398,7 +1472,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if t + 1 == max_new_tokens or bool(done.all()):
                 break
             x = ops.embedding_fwd(emb_w, nxt.contiguous()) if feed is None else feed(nxt.contiguous())   # [B, D]
-            if ragged is not None:                                         # the graph path's step launches, one by one
+            if dyn:                                                        # the graph path's step launches, one by one
                 last = run(x, 1, 0, pos=t_dev, t_dev=t_dev)
                 t_dev += 1
             else:
@@ -1586,11 +1660,14 @@ class MM_LLMs(PreTrainedModel):
                              negative_prompt_attention_mask=inputs.get("attention_mask") if GENERATE_MASK[0] else None)
             # stop sequences / bad words set: passed on; unset: exactly the call without them
             stopping = {k: v for k, v in STOPPING[0].items() if v is not None}
+            # parallel samples on: num_samples rows per prompt, the towers and the alignment above run once per prompt;
+            # off: exactly the call without it
+            par = dict(num_samples=PARALLEL_SAMPLES[0]) if PARALLEL_SAMPLES[0] != 1 else {}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
-                                     **guide, **stopping, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
+                                     **guide, **stopping, **par, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1701,6 +1778,15 @@ class MM_LLMs(PreTrainedModel):
         _stopping_check("set_stopping", stop_sequences, bad_words_ids)
         STOPPING[0] = dict(stop_sequences=None if stop_sequences is None else [list(q) for q in stop_sequences],
                            bad_words_ids=None if bad_words_ids is None else [list(q) for q in bad_words_ids])
+
+    @staticmethod
+    def set_parallel_samples(num_samples=1):
+        """Parallel sampling for `inputs["inference"] = True` (LlamaForCausalLM.generate's num_samples): off (1) by default.
+        With n > 1 forward returns ids [B * n, width], row b * n + j sample j of prompt b; the towers, the alignment and
+        the prefill run once per prompt.  It needs set_sampling(do_sample=True).  Validated here; what depends on the
+        call (sampling, beams, prompt lookup, guidance, cache format, dtype) is validated by generate().  No arguments:
+        back to off.  Process-wide switch, like set_logprobs."""
+        PARALLEL_SAMPLES[0] = _num_samples_check("set_parallel_samples", num_samples)
 
     def prepare_inputs_for_generation(self, inputs):
         """modeling.py:965-1048 — same outputs (inputs_embeds, attention_mask, labels)."""

@@ -975,6 +975,50 @@ def decode_step_attn_beam(q, k_new, v_new, in_bs, cos_t, sin_t, cache, t_dev, in
     return out
 
 
+SHARED_MAX_N = 32
+
+
+def shared_attn_ok(dtype, hd, n):
+    """mk_decode_step_attn_shared's domain: bf16 / fp16, hd in {16, 32, 64, 128}, 1 <= n <= 32 rows per sample.  The
+    kernel keeps no per-key buffer in LDS, so neither the prompt's nor the tail's length bounds it"""
+    return dtype in (torch.bfloat16, torch.float16) and hd in (16, 32, 64, 128) and 1 <= n <= SHARED_MAX_N
+
+
+def decode_step_attn_shared(q, k_new, v_new, in_bs, cos_t, sin_t, prompt, tail, t_dev, t_off, S0, B, n, H, hd, out, scale,
+                            q_off=0, k_off=0, v_off=0):
+    """decode_step_attn for the B * n rows of a parallel-sampling step (see mk_decode_step_attn_shared): row b * n + j is
+    sample j of prompt b.  prompt [B, S0, 2 * H * hd] holds each prompt's keys and values ONCE (read only; a padded
+    batch's compacted rows, t_off int32 [B] on the device = engine.Ragged.t_off, or None), tail [B * n, Tn, 2 * H * hd]
+    the rows' own tokens.  With i = clamp(*t_dev - S0, 0, Tn - 1) and L_b = clamp(S0 + t_off[b], 0, S0): RoPE at
+    position L_b + i, append to tail row i of the row, attention over prompt rows 0 ... L_b - 1 of sample b and tail
+    rows 0 ... i of the row.  out [B * n, H * hd].  Bit-identical per row to decode_step_attn on a physically gathered
+    cache; one launch, the rows of a tile run in one workgroup and find the prompt's keys in cache behind its first row"""
+    lib = _L.load()
+    es = q.element_size()
+    D = H * hd
+    if prompt.dtype != q.dtype or tuple(prompt.shape) != (B, S0, 2 * D) or not prompt.is_contiguous():
+        raise MacawHipError(f"decode_step_attn_shared: prompt {prompt.dtype} {tuple(prompt.shape)}; expected {q.dtype} "
+                            f"{(B, S0, 2 * D)}, contiguous")
+    if (tail.dtype != q.dtype or tail.dim() != 3 or tail.shape[0] != B * n or tail.shape[1] < 1 or tail.shape[2] != 2 * D
+            or not tail.is_contiguous()):
+        raise MacawHipError(f"decode_step_attn_shared: tail {tail.dtype} {tuple(tail.shape)}; expected {q.dtype} "
+                            f"[{B * n}, Tn >= 1, {2 * D}], contiguous")
+    Tn = tail.shape[1]
+    if t_off is not None:
+        _i32_check("decode_step_attn_shared", "t_off", t_off, B)
+    if out.shape[0] != B * n or q.shape[0] != B * n:
+        raise MacawHipError(f"decode_step_attn_shared: {q.shape[0]} input and {out.shape[0]} output rows for B * n = {B * n}")
+    if cos_t.shape[0] < S0 + Tn or sin_t.shape[0] < S0 + Tn:
+        raise MacawHipError(f"decode_step_attn_shared: {cos_t.shape[0]} table rows for positions up to {S0 + Tn - 1}")
+    _L.check(lib.mk_decode_step_attn_shared(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es, in_bs,
+                                            _p(cos_t), _p(sin_t), _p(prompt) if S0 else None,
+                                            _p(prompt) + D * es if S0 else None, 2 * D, S0 * 2 * D, _p(tail),
+                                            _p(tail) + D * es, 2 * D, Tn * 2 * D, _p(out), _rowmajor(out), _p(t_dev),
+                                            _p(t_off), S0, Tn, B, n, H, hd, scale, dt(q), _st()),
+             "mk_decode_step_attn_shared")
+    return out
+
+
 class BeamState:
     """the device state of a beam search (include/macaw_hip.h, "State layout"): B samples, K beams, n_max columns"""
 

@@ -62,6 +62,15 @@ with torch.no_grad():
 # call of 72 tokens the difference is the search for the returned width behind the loop (one ops.stop_match launch per column).
 # Then the stand-alone time of one ops.seq_ban / ops.stop_match launch (tables of 4 and of 1000 sequences) against
 # ops.decode_emit on [B, V] logits with 100 generated ids
+#        bench_generate.py --nsample-ab [--prompt-tokens N] [--reps R]: parallel sampling for (B, n) = (1, 4), (2, 16), (8, 4).
+# Three arms alternated in this process on this model, all with do_sample=True, top_k=50, top_p=0.9, seed 1: "repeat" = the
+# prompts repeated n times, a batch of B * n (today's way); "shared R=1" = num_samples=n at batch B (the prompt cache stored once,
+# ops.decode_step_attn_shared) under MK_SHARED_ATTN_ROWS=1, one workgroup per row; "shared R=4" = the same under
+# MK_SHARED_ATTN_ROWS=4, four rows of a prompt one after the other in one workgroup (the variable is read at every call, and the
+# step is captured anew by every generate() call).  ms per token of every run, the medians and each arm's run-to-run spread, the time to the first
+# token (the call with max_new_tokens=1: prefill + token 0), and the KV bytes each arm allocates for the 72-token call (from the
+# shapes, and the allocator's peak over the call)
+NSAMPLE = "--nsample-ab" in sys.argv
 STOP = "--stop-ab" in sys.argv
 CFG = "--cfg-ab" in sys.argv
 LOGPROBS = "--logprobs-ab" in sys.argv
@@ -77,7 +86,57 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if NSAMPLE:
+    lcfg = model.llm.config
+    NL, D = lcfg.num_hidden_layers, lcfg.hidden_size
+    SKW = dict(do_sample=True, top_k=50, top_p=0.9, seed=1, eos_token_id=-1)
+    ARMS = ("repeat", "shared R=1", "shared R=4")
+    for B, n in ((1, 4), (2, 16), (8, 4)):
+        inp = synthetic_inputs(cfg, B, PROMPT, modalities=("images", "audios"), seed=2, device=dev)
+        ms, ttft, peak = {a: [] for a in ARMS}, {a: [] for a in ARMS}, {}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            S0 = emb.shape[1]
+            emb_r = emb.repeat_interleave(n, 0)
+
+            def call(arm, new):
+                if arm == "repeat":
+                    return model.llm.generate(inputs_embeds=emb_r, max_new_tokens=new, **SKW)
+                os.environ["MK_SHARED_ATTN_ROWS"] = arm[-1]
+                try:
+                    return model.llm.generate(inputs_embeds=emb, max_new_tokens=new, num_samples=n, **SKW)
+                finally:
+                    del os.environ["MK_SHARED_ATTN_ROWS"]
+            # the KV cache of the 72-token call, all layers: [keys | values] rows of 2 D 16-bit elements
+            kvb = {"repeat": NL * B * n * (S0 + 72) * 2 * D * 2, "shared R=1": NL * (B * S0 + B * n * 72) * 2 * D * 2}
+            kvb["shared R=4"] = kvb["shared R=1"]
+            for arm in ARMS:                        # untimed: each arm's first call at this size
+                assert call(arm, 4).shape == (B * n, 4)
+            for rep in range(REPS):
+                for arm in ARMS:
+                    t = {}
+                    for new in (1, 8, 72):
+                        torch.cuda.synchronize(); base = torch.cuda.memory_allocated(); torch.cuda.reset_peak_memory_stats()
+                        t0 = time.perf_counter()
+                        ids = call(arm, new)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                        assert ids.shape == (B * n, new)
+                    peak[arm] = torch.cuda.max_memory_allocated() - base
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    ttft[arm].append(t[1] * 1e3)
+                    print(f"B={B:2d} n={n:2d} S0={S0} rep {rep} {arm:10s}: decode {ms[arm][-1]:6.3f} ms/token, first token {ttft[arm][-1]:8.2f} ms", flush=True)
+        med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+        medt = {a: sorted(v)[len(v) // 2] for a, v in ttft.items()}
+        spr = {a: max(v) - min(v) for a, v in ms.items()}
+        for a in ARMS:
+            print(f"B={B:2d} n={n:2d} S0={S0}: {a:10s} {med[a]:6.3f} ms/token (run-to-run spread {spr[a] * 1e3:6.1f} us = {spr[a] / med[a] * 100:4.1f} %), "
+                  f"first token {medt[a]:8.2f} ms, KV cache {kvb[a] / 1e9:7.3f} GB allocated (allocator peak over the call {peak[a] / 1e9:7.3f} GB)", flush=True)
+        d1 = med["shared R=4"] - med["shared R=1"]
+        print(f"B={B:2d} n={n:2d} S0={S0}: shared R=1 / repeat = {med['shared R=1'] / med['repeat']:5.3f} per token, {medt['shared R=1'] / medt['repeat']:5.3f} to the "
+              f"first token, KV {kvb['shared R=1'] / kvb['repeat']:5.3f}; tiled - untiled = {d1 * 1e3:+7.1f} us ({d1 / med['shared R=1'] * 100:+5.2f} %): "
+              f"{'inside' if abs(d1) <= max(spr['shared R=4'], spr['shared R=1']) else 'OUTSIDE'} the larger of their spreads", flush=True)
+    sys.exit(0)
 if STOP:
     from macaw_llm_amd import ops
     V = model.llm.lm_head.weight.shape[0]
