@@ -294,6 +294,34 @@ int mk_flash_attn_fwd(const void* q, const void* k, const void* v, void* o, floa
                       int64_t v_ld, int64_t v_bs, int64_t o_ld, int64_t o_bs, float scale,
                       int32_t causal, int32_t dtype, void* stream);
 
+/* mk_flash_attn_fwd, always causal, with PER-SAMPLE lengths read on the device: the prefill of several new positions
+ * per sample over a KV cache whose length differs per sample (a continued generate() call).  q_len / k_len: int32 [B]
+ * device arrays; Lq / Lk are host UPPER BOUNDS that size the grid and the key loop -- the host never synchronises for
+ * the lengths.  Addressing is mk_flash_attn_fwd's (base + b*bs + token*ld + h*hd); k and v may be the two halves of a
+ * [B][t_max][2D] cache.  The rule, with ql_b = clamp(q_len[b], 0, Lq) and kl_b = clamp(k_len[b], 0, Lk):
+ *   - query row i < ql_b of sample b sees key j iff j < kl_b and j <= i + (kl_b - ql_b);
+ *   - a row without a visible key -- every row i >= ql_b (up to Lq) and, where kl_b < ql_b, the first ql_b - kl_b rows --
+ *     gets o = 0 and lse = -inf, exactly; nothing is NaN (mk_flash_attn_fwd's rule for dead rows);
+ *   - no byte of k or v at a row >= kl_b is read, and no byte of q at a row >= ql_b influences any output (a cache with
+ *     unwritten rows behind a sample's length, and filler rows behind a sample's new tokens, are safe).
+ * A row's result does not depend on the other samples of the launch.  lse [B, H, Lq] f32 optional.
+ * Domain: bf16 or f16, hd 64 or 128, the alignment and stride conditions of mk_flash_attn_fwd; otherwise
+ * MK_ERR_UNSUPPORTED and nothing is launched.  MK_ERR_BAD_ARG for a null q, k, v, o, q_len or k_len and for B, H, Lq or
+ * Lk <= 0.  Inference only: there is no backward.  Pinned by tests/test_flash_varlen_gpu.py.
+ * The sessions built on it (generate(return_session=True) / generate(session=), modeling.GenerateSession) keep this
+ * rule: a sample's history is built turn by turn -- the valid tokens of the turn's prompt, then the turn's generated tokens
+ * up to and including the sample's final token (its eos, the last id of the stop sequence that ended it, or its last
+ * token at max_new_tokens; pads behind it never enter).  A continued call returns for every sample what a fresh call would
+ * return for that sample alone on history + valid tokens of the new prompt, positions 0 ... len - 1, up to the last bits
+ * of its arithmetic.  The final token of a turn was emitted but never fed, so its key is not in the cache: it is the
+ * session's pending token and becomes row 0 of the next call's new rows (q_len[b] = 1 + valid new tokens, k_len[b] = cached
+ * rows + q_len[b]); no extra step is run for it. */
+int mk_flash_attn_varlen_fwd(const void* q, const void* k, const void* v, void* o, float* lse /* optional */,
+                             const int32_t* q_len, const int32_t* k_len, int32_t B, int32_t H, int32_t Lq,
+                             int32_t Lk, int32_t hd, int64_t q_ld, int64_t q_bs, int64_t k_ld, int64_t k_bs,
+                             int64_t v_ld, int64_t v_bs, int64_t o_ld, int64_t o_bs, float scale, int32_t dtype,
+                             void* stream);
+
 /* Fused attention backward (recompute form): dq, dk, dv from q, k, v, o, do and the forward's
  * lse; never stores P.  dq/dk/dv/do use the geometry of q/k/v/o.  dvec: f32 [B*H*Lq] scratch. */
 int mk_flash_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,

@@ -16,6 +16,7 @@
 //   O^T[d][q]  += V^T P^T    P^T fragments are exactly the lane's own S registers (the MFMA
 //                            k-slot <-> key mapping is chosen to match, no cross-lane shuffle)
 // Row max / sum need one __shfl_xor(.., 32) with the partner half.
+#include <type_traits>
 #include <utility>
 #include "common.h"
 #include "../../include/macaw_hip.h"
@@ -56,6 +57,15 @@ extern "C" int mk_flash_attn_fwd(const void* q, const void* k, const void* v, vo
                                  void* stream) {
   if (dtype == MK_F16) return e_f16::flash_attn_fwd_impl(q, k, v, o, lse, kmask, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld, v_bs, o_ld, o_bs, scale, causal, dtype, stream);
   return e_bf16::flash_attn_fwd_impl(q, k, v, o, lse, kmask, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld, v_bs, o_ld, o_bs, scale, causal, dtype, stream);
+}
+
+extern "C" int mk_flash_attn_varlen_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
+                                        const int32_t* q_len, const int32_t* k_len, int32_t B, int32_t H,
+                                        int32_t Lq, int32_t Lk, int32_t hd, int64_t q_ld, int64_t q_bs,
+                                        int64_t k_ld, int64_t k_bs, int64_t v_ld, int64_t v_bs, int64_t o_ld,
+                                        int64_t o_bs, float scale, int32_t dtype, void* stream) {
+  if (dtype == MK_F16) return e_f16::flash_attn_varlen_fwd_impl(q, k, v, o, lse, q_len, k_len, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld, v_bs, o_ld, o_bs, scale, dtype, stream);
+  return e_bf16::flash_attn_varlen_fwd_impl(q, k, v, o, lse, q_len, k_len, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld, v_bs, o_ld, o_bs, scale, dtype, stream);
 }
 
 extern "C" int mk_flash_attn_bwd(const void* q, const void* k, const void* v, const void* o,

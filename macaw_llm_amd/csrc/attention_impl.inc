@@ -138,8 +138,19 @@ MK_DEV void softmax_block(f32x16& s, bool interior, uint32_t okbits, float c2, f
   for (int e = 0; e < 8; ++e) { pf[0][e] = (e16)s[e]; pf[1][e] = (e16)s[8 + e]; }
 }
 
-template <int HD, bool CAUSAL>
-__global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
+// The 4-wave forward, one template for two argument blocks: FlashArgs (one (Lq, Lk) for the launch) and FlashVarlenArgs
+// (VARLEN below; always causal: the lengths of sample b are read on the device, clamped to the launch's bounds a.Lq /
+// a.Lk, and take their place in the tile count, the causal shift, the interior-tile test, the key-validity bytes, the
+// K / V descriptor ranges and the stores -- mk_flash_attn_varlen_fwd in macaw_hip.h states the rule).  Every
+// `if constexpr (VARLEN)` is outside the tile loop; with FlashArgs Lq / Lk ARE a.Lq / a.Lk and the kernel compiles to
+// the code it was before the second form existed.
+struct FlashVarlenArgs : FlashArgs {
+  const int32_t* q_len; const int32_t* k_len;   // int32 [B] on the device
+};
+template <int HD, bool CAUSAL, typename Args = FlashArgs>
+__global__ __launch_bounds__(256, 2) void flash_fwd_kernel(Args a) {
+  constexpr bool VARLEN = std::is_same<Args, FlashVarlenArgs>::value;
+  static_assert(CAUSAL || !VARLEN, "the variable-length forward is causal");
   constexpr int KT = 64;                 // keys per LDS tile
   constexpr int NKD = HD / 16;           // MFMA k-steps over d for Q K^T
   constexpr int NDB = HD / 32;           // 32-wide d blocks of the output
@@ -170,6 +181,21 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
     if (bh >= a.B * a.H) return;         // (grid rounded up to 8 x nblk; whole workgroup, before any barrier)
     b = bh / a.H; h = bh - b * a.H;
   }
+  int Lq = a.Lq, Lk = a.Lk;              // the rows and keys of THIS sample (VARLEN: a.Lq / a.Lk bound them and size the grid)
+  if constexpr (VARLEN) {
+    Lq = min(max(__builtin_amdgcn_readfirstlane(a.q_len[b]), 0), a.Lq);
+    Lk = min(max(__builtin_amdgcn_readfirstlane(a.k_len[b]), 0), a.Lk);
+    if (blk * 128 >= Lq) {
+      // the whole block lies at or past the sample's last query row: its rows of o are zeros, its lse -inf, and the
+      // workgroup leaves as a whole before its first barrier (no q, k or v byte is read)
+      e16* O = a.o + (long)b * a.o_bs + (long)h * HD;
+      const int rows = min(128, a.Lq - blk * 128);
+      for (int i = threadIdx.x; i < rows * (HD / 8); i += 256)
+        *reinterpret_cast<uint4*>(O + (long)(blk * 128 + i / (HD / 8)) * a.o_ld + (i % (HD / 8)) * 8) = make_uint4(0, 0, 0, 0);
+      if (a.lse && (int)threadIdx.x < rows) a.lse[((long)b * a.H + h) * a.Lq + blk * 128 + threadIdx.x] = -INFINITY;
+      return;
+    }
+  }
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int half = l >> 5, lq = l & 31;
   const int q0 = blk * 128 + w * 32;
@@ -183,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
   e16x8 qf[NKD];
 #pragma unroll
   for (int kd = 0; kd < NKD; ++kd) {
-    qf[kd] = ld8_or_zero(Q + (long)min(qg, a.Lq - 1) * a.q_ld + 16 * kd + 8 * half, qg < a.Lq);
+    qf[kd] = ld8_or_zero(Q + (long)min(qg, Lq - 1) * a.q_ld + 16 * kd + 8 * half, qg < Lq);
   }
   f32x16 oacc[NDB];
 #pragma unroll
@@ -203,9 +229,9 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
   // on every growth (the round-2 behaviour).
 
   // keys this block has to visit (causal: up to the last query row of the block)
-  const int shift = a.Lk - a.Lq;         // query i may see keys <= i + shift
-  int k_end = a.Lk;
-  if (CAUSAL) k_end = min(a.Lk, blk * 128 + 128 + shift);
+  const int shift = Lk - Lq;             // query i may see keys <= i + shift
+  int k_end = Lk;
+  if (CAUSAL) k_end = min(Lk, blk * 128 + 128 + shift);
   const int ntiles = (k_end + KT - 1) / KT;
 
   // K / V staging is split (cdna_hip_programming.md T14, "async-STAGE"): the global loads of tile kt + 1 are
@@ -222,10 +248,14 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
   constexpr int NCH = (KT * CPR) / 256;
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   u32x4 kv4[NCH], vv4[NCH];
-  const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)K, 0, (int)min(((long)(a.Lk - 1) * a.k_ld + HD) * 2, 0x7fffffffL), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)V, 0, (int)min(((long)(a.Lk - 1) * a.v_ld + HD) * 2, 0x7fffffffL), 0x00020000);
+  // (VARLEN: the range ends behind row Lk - 1 of THIS sample -- no byte of a later row is read; Lk = 0: an empty range)
+  auto range = [&](long ld) {
+    long n = ((long)(Lk - 1) * ld + HD) * 2;
+    if constexpr (VARLEN) n = max(n, 0L);
+    return (int)min(n, 0x7fffffffL);
+  };
+  const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc((void*)K, 0, range(a.k_ld), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)V, 0, range(a.v_ld), 0x00020000);
   const int srow = threadIdx.x / CPR, sch = threadIdx.x % CPR;        // chunk i of this thread: row srow + i * 256 / CPR
   const int kvo = (int)(((long)srow * a.k_ld + sch * 8) * 2), vvo = (int)(((long)srow * a.v_ld + sch * 8) * 2);
   const int k_step = (int)((256 / CPR) * a.k_ld * 2), v_step = (int)((256 / CPR) * a.v_ld * 2);   // bytes per chunk index
@@ -250,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
     }
     if (threadIdx.x < KT) {
       const int kg = kb + threadIdx.x;
-      lds[bufoff + 2 * KT * HD * 2 + threadIdx.x] = ((kg < a.Lk) && (!km || km[kg] != 0)) ? 1 : 0;
+      lds[bufoff + 2 * KT * HD * 2 + threadIdx.x] = ((kg < Lk) && (!km || km[kg] != 0)) ? 1 : 0;
     }
   };
   if (ntiles > 0) { issue_tile(0); write_tile(0, 0); }
@@ -270,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
     // block need one of its two key tiles)
     const bool need0 = !(CAUSAL && kbase > q0 + 31 + shift);
     const bool need1 = !(CAUSAL && kbase + 32 > q0 + 31 + shift);
-    if (q0 < a.Lq && need0) {            // (a wave without rows still stages and takes part in the barriers)
+    if (q0 < Lq && need0) {            // (a wave without rows still stages and takes part in the barriers)
     // Interior tile: every key of the tile is valid and visible to every query row of this wave --
     // no mask arithmetic at all (at S = 2048 all but the last two tiles of a block).  Wave-uniform.
     bool interior = (__builtin_amdgcn_ballot_w64(ldsM[l] != 0) == ~0ull);
@@ -386,6 +416,17 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FlashArgs a) {
   int tid_e = threadIdx.x;
   asm volatile("" : "+v"(tid_e));
   const int half_e = (tid_e >> 5) & 1, qg_e = blk * 128 + (tid_e >> 6) * 32 + (tid_e & 31);
+  if constexpr (VARLEN) {
+    // rows [Lq, a.Lq) of a live block are stored too, as exact zeros and -inf: a wave past Lq computed nothing, a row
+    // past Lq inside a live wave ran on a zero q -- its sums are dropped here, not scaled (0 x inf would be NaN)
+    if (qg_e >= Lq) {
+      l_run = 0.f;
+#pragma unroll
+      for (int d = 0; d < NDB; ++d)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) oacc[d][e] = 0.f;
+    }
+  }
   const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
   e16* O = a.o + (long)b * a.o_bs + (long)min(qg_e, a.Lq - 1) * a.o_ld + (long)h * HD;
   store_row16<NDB>(O, oacc, inv, half_e, qg_e < a.Lq);
@@ -1384,6 +1425,40 @@ int flash_attn_fwd_impl(const void* q, const void* k, const void* v, void* o, fl
     if (causal) MK_LAUNCH((flash_fwd_kernel<64, true>), grid, block, 0, st, a);
     else MK_LAUNCH((flash_fwd_kernel<64, false>), grid, block, 0, st, a);
   }
+  mkp::end(prof, st);
+  return mk_check_launch();
+}
+
+// The causal forward with per-sample lengths read on the device (macaw_hip.h: mk_flash_attn_varlen_fwd).  Always the
+// 4-wave kernel: Lq / Lk are upper bounds, the grid is sized by Lq and a block past its sample's q_len leaves at once.
+int flash_attn_varlen_fwd_impl(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* q_len,
+                               const int32_t* k_len, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
+                               int64_t q_ld, int64_t q_bs, int64_t k_ld, int64_t k_bs, int64_t v_ld, int64_t v_bs,
+                               int64_t o_ld, int64_t o_bs, float scale, int32_t dtype, void* stream) {
+  if (!q || !k || !v || !o || !q_len || !k_len || B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return MK_ERR_BAD_ARG;
+  if (dtype != E16<e16>::dtype || (hd != 64 && hd != 128)) return MK_ERR_UNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) |
+                       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o);
+  if ((al & 15) || (q_ld % 8) || (k_ld % 8) || (v_ld % 8) || (o_ld % 8) || (q_bs % 8) ||
+      (k_bs % 8) || (v_bs % 8) || (o_bs % 8))
+    return MK_ERR_UNSUPPORTED;
+  FlashVarlenArgs a;
+  a.q = (const e16*)q; a.k = (const e16*)k; a.v = (const e16*)v; a.o = (e16*)o;
+  a.lse = lse; a.kmask = nullptr;
+  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
+  a.q_ld = q_ld; a.q_bs = q_bs; a.k_ld = k_ld; a.k_bs = k_bs; a.v_ld = v_ld; a.v_bs = v_bs;
+  a.o_ld = o_ld; a.o_bs = o_bs;
+  a.scale = scale;
+  a.nblk = 0;
+  a.rcos = nullptr; a.rsin = nullptr; a.rpos = nullptr;
+  a.q_len = q_len; a.k_len = k_len;
+  dim3 grid(H, B, mk_cdiv(Lq, 128)), block(256);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // (the lengths live on the device: the FLOP figure is the bound's, every sample at (Lq, Lk))
+  const double pairs = (double)Lq * Lk - 0.5 * (double)min(Lq, Lk) * (min(Lq, Lk) - 1);
+  const int prof = mkp::begin(st, 1, 4.0 * pairs * hd * B * H, Lq, Lk, hd, B * H, 1, 0);
+  if (hd == 128) MK_LAUNCH((flash_fwd_kernel<128, true, FlashVarlenArgs>), grid, block, 0, st, a);
+  else MK_LAUNCH((flash_fwd_kernel<64, true, FlashVarlenArgs>), grid, block, 0, st, a);
   mkp::end(prof, st);
   return mk_check_launch();
 }

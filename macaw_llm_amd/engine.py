@@ -725,6 +725,50 @@ def ragged_from_mask(mask, B, S0):
     return rg, pos.to(torch.int32).reshape(-1).contiguous(), last.contiguous()
 
 
+class Chunk(NamedTuple):
+    """the prefill of a CONTINUED call for llama_layer_cached (chunk_layout): q_len[b] new rows of sample b, left-compacted
+    in its Sc rows, behind the k_len[b] - q_len[b] rows its compacted cache already holds"""
+    q_len: torch.Tensor      # int32 [B]: n_b, the new rows of sample b (its pending token, then its valid new tokens)
+    k_len: torch.Tensor      # int32 [B]: C_b + n_b, the rows of sample b's cache once the new ones are appended
+    slot: torch.Tensor       # int32 [B, Sc]: cache row of new row (b, j) = C_b + j; -1 for a filler row (j >= n_b)
+    Lk: int                  # max k_len: the host bound of the key loop
+    q_host: tuple            # q_len and k_len once more on the host, for the per-sample attention where the
+    k_host: tuple            # variable-length kernel does not take the head size
+
+
+def chunk_layout(cached, n_valid, device=None):
+    """The host side of generate(session=): cached[b] = C_b rows in sample b's compacted cache, n_valid[b] = v_b >= 1 valid
+    tokens in its new prompt (sequences of int).  The new rows of a sample are LEFT-COMPACTED: row 0 is the session's
+    pending token (emitted by the last turn, never fed), rows 1 ... v_b its valid new tokens in order, n_b = 1 + v_b,
+    Sc = max n_b; the rows behind n_b are filler that repeats the sample's last row and is never appended or attended.
+    Returns (Chunk, pos, last, S0n, t_off), tensors on `device` (None: the CPU):
+      pos   int32 [B * Sc]  RoPE position of row (b, j): C_b + min(j, n_b - 1)
+      last  int64 [B]       flat row b * Sc + n_b - 1: the hidden row that predicts token 0
+      S0n   int             max_b k_len[b]: where the decode steps' common counter starts
+      t_off int32 [B]       k_len[b] - S0n: Ragged.t_off, the step of sample b runs at row *t_dev + t_off[b]
+    ValueError for lists of different lengths, a negative C_b and a sample without a valid token."""
+    cached, n_valid = [int(c) for c in cached], [int(v) for v in n_valid]
+    if len(cached) != len(n_valid) or not cached:
+        raise ValueError(f"chunk_layout: {len(cached)} cached counts for {len(n_valid)} samples")
+    if min(cached) < 0:
+        raise ValueError(f"chunk_layout: negative cached row count in {cached}")
+    if min(n_valid) < 1:
+        raise ValueError(f"sample(s) {[b for b, v in enumerate(n_valid) if v < 1]} have no valid token")
+    B = len(cached)
+    n = torch.tensor(n_valid, dtype=torch.int64) + 1
+    C = torch.tensor(cached, dtype=torch.int64)
+    Sc = int(n.max())
+    j = torch.arange(Sc, dtype=torch.int64).expand(B, Sc)
+    pos = C[:, None] + torch.minimum(j, n[:, None] - 1)
+    slot = torch.where(j < n[:, None], C[:, None] + j, torch.full_like(j, -1))
+    k_len = C + n
+    S0n = int(k_len.max())
+    i32 = lambda t: t.to(torch.int32).contiguous().to(device) if device is not None else t.to(torch.int32).contiguous()  # noqa: E731
+    last = torch.arange(B, dtype=torch.int64) * Sc + n - 1
+    chunk = Chunk(i32(n), i32(k_len), i32(slot), S0n, tuple(n.tolist()), tuple(k_len.tolist()))
+    return chunk, i32(pos.reshape(-1)), (last.to(device) if device is not None else last), S0n, i32(k_len - S0n)
+
+
 def _step_attn(q, k, v, in_bs, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged=None, beam=None, spec=None,
                **off):
     """the attention block of a decode step: ops.decode_step_attn on the 16-bit cache, or (kv8 = the scales of an
@@ -828,9 +872,27 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     holds the B * kvc.n rows; the step attention is ops.decode_step_attn_shared over kvc.prompt (stored once per prompt)
     and kvc.tail (per row), every other launch sees B * n token rows and is unchanged.  Tmax is not read.  The prefill
     of such a cache is an ordinary call at B rows on kvc.prompt with Tmax = S0 (with ragged: the compacting write, and
-    the steps then pass ragged.t_off on).  Not with kv8, beam or spec, and not with a host position."""
+    the steps then pass ragged.t_off on).  Not with kv8, beam or spec, and not with a host position.
+
+    ragged a Chunk (chunk_layout; passed IN PLACE of a Ragged, as a SharedPrompt is of the cache, so that the signature
+    every other caller binds to stays what it is; Sn = its Sc, t0 is ignored, `pos` its positions): the prefill of a
+    continued call,
+    chunk.q_len[b] new positions of sample b over the chunk.k_len[b] - chunk.q_len[b] rows its compacted cache holds.
+    The new keys / values go into the cache first (ops.kv_append_rows at chunk.slot), then ops.flash_attn_varlen_fwd
+    attends over the cache's two halves with the lengths read on the device; where that kernel does not take the head
+    size (ops.flash_varlen_ok), the samples run one by one through attention_fwd at their host lengths.  Filler rows
+    come out as zeros.  The decode steps that follow are the ragged batch's (Ragged.t_off = chunk_layout's t_off).  Not
+    with kv8, beam, spec, a SharedPrompt or t_dev."""
     M, D = x2.shape
     dyn = t_dev is not None
+    chunk = None
+    if isinstance(ragged, Chunk):
+        chunk, ragged = ragged, None
+        if (kv8 is not None or beam is not None or spec is not None or dyn or
+                isinstance(kvc, SharedPrompt) or M != B * Sn or tuple(chunk.slot.shape) != (B, Sn)):
+            raise ValueError("llama_layer_cached: a Chunk takes the B * Sc new rows of a continued prefill on the 16-bit "
+                             "compacted cache, not kv8, beam, spec, a SharedPrompt or t_dev")
+        t0 = 0
     if isinstance(kvc, SharedPrompt) and (not dyn or kv8 is not None or beam is not None or spec is not None or
                                           M != B * kvc.n):
         raise ValueError("llama_layer_cached: a SharedPrompt cache takes single-position decode steps (t_dev) of B * n rows "
@@ -887,6 +949,20 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         ropes, appends = ((q, H), (k, H)), ((k, D, 0, 0), (v, D, 0, D))
     if dyn:     # RoPE + cache append + attention of the new position: one launch
         _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, spec, **off)
+    elif chunk is not None:
+        # a continued prefill: the new rows join the compacted cache, then every row attends over its sample's cache
+        for t, heads in ropes:
+            ops.rope_(t, cos, sin, pos, heads, hd)
+        ops.kv_append_rows(k, v, ldq, Sn * ldq, kvc, chunk.slot, Sn, Tmax, B, H, hd)
+        if ops.flash_varlen_ok(x2.dtype, hd):
+            ops.flash_attn_varlen_fwd(q, kvc, kvc, att, chunk.q_len, chunk.k_len, B, H, Sn, chunk.Lk, hd, ldq, Sn * ldq,
+                                      ldc, Tmax * ldc, ldc, Tmax * ldc, D, Sn * D, scale, v_off=D)
+        else:           # (a head size outside the kernel: sample by sample at the host lengths; the filler rows zeroed)
+            ops.fill_(att, 0.0)
+            for b, (nq, nk) in enumerate(zip(chunk.q_host, chunk.k_host)):
+                attention_fwd(TDesc(q, ldq, Sn * ldq, b * Sn * ldq), TDesc(kvc, ldc, Tmax * ldc, b * Tmax * ldc),
+                              TDesc(kvc, ldc, Tmax * ldc, b * Tmax * ldc + D), TDesc(att, D, Sn * D, b * Sn * D),
+                              1, H, nq, nk, hd, scale, causal=True)
     else:
         for t, heads in ropes:
             ops.rope_(t, cos, sin, pos, heads, hd)

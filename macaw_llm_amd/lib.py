@@ -102,6 +102,7 @@ SIGNATURES = {
     "mk_softmax_bwd": [_vp, _vp, _i32, _i32, _i32, _i64, _f32, _f32, _u64, _i32, _vp],
     "mk_flash_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64,
                           _i64, _i64, _i64, _i64, _i64, _f32, _i32, _i32, _vp],
+    "mk_flash_attn_varlen_fwd": [_vp] * 7 + [_i32] * 5 + [_i64] * 8 + [_f32, _i32, _vp],
     "mk_flash_attn_bwd": [_vp] * 11 + [_i32] * 5 + [_i64] * 8 + [_f32, _i32, _i32, _vp],
     "mk_flash_attn_rope_fwd": [_vp] * 9 + [_i32] * 5 + [_i64] * 8 + [_f32, _i32, _i32, _vp],
     "mk_flash_attn_rope_bwd": [_vp] * 14 + [_i32] * 5 + [_i64] * 8 + [_f32, _i32, _i32, _i32, _vp],

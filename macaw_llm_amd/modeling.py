@@ -77,6 +77,8 @@ GUIDANCE = [1.0]
 STOPPING = [dict(stop_sequences=None, bad_words_ids=None)]
 # MM_LLMs.set_parallel_samples: the num_samples MM_LLMs.forward hands to generate() (1 = off: the call without it)
 PARALLEL_SAMPLES = [1]
+# MM_LLMs.set_session: whether MM_LLMs.forward asks generate() for the call's GenerateSession (return_session=True)
+SESSION = [False]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -226,6 +228,93 @@ def _guided_batch(scale, emb, mask, neg, neg_mask):
 
 # ---------------------------------------------------------------- the helpers of generate()'s decode loops -----
 _16BIT = (torch.bfloat16, torch.float16)
+
+
+def _session_final(row, eos, stop):
+    """c: the generated tokens of one sample (row: its ids of one call, pads behind its end included) up to and including
+    its FINAL token -- its eos, the last id of the stop sequence that ended it (stop: lists of ids, or None), or its last
+    token when neither came.  Pads behind the final token never count."""
+    for t, tok in enumerate(row):
+        if eos is not None and tok == eos:
+            return t + 1
+        for q in stop or ():
+            if t + 1 >= len(q) and list(row[t + 1 - len(q):t + 1]) == list(q):
+                return t + 1
+    return len(row)
+
+
+class GenerateSession:
+    """A multi-turn conversation of LlamaForCausalLM.generate: the KV caches of a batch kept alive between calls
+    (generate(return_session=True) makes one, generate(session=s) continues it in place).
+
+    The rule.  A sample's history is built turn by turn: the valid tokens of the turn's prompt, then the turn's generated
+    tokens up to and including the sample's final token (its eos, the last id of the stop sequence that ended it, or its
+    last token at max_new_tokens; pads behind it never enter).  A continued call returns for every sample what a fresh
+    call would return for that sample alone on history + valid tokens of the new prompt, positions 0 ... len - 1, up to
+    the last bits of its arithmetic.  The final token of a turn was emitted but never fed, so its key is not in the
+    cache: it is the session's pending token and becomes row 0 of the next call's prefill.
+
+    Read-only: batch, lengths (tokens of each sample's history), capacity (rows of the caches), turns, ids (per sample
+    the KNOWN token ids of its history: a turn given as embeddings contributes its generated tokens only)."""
+
+    def __init__(self, kvc, cached, pending, ids, hidden, dev):
+        self._kvc = list(kvc)                    # per layer [B, capacity, 2D]: the compacted [keys | values] rows
+        self._cached_host = [int(c) for c in cached]       # rows of each sample's cache = lengths - 1
+        self._cached = torch.tensor(self._cached_host, dtype=torch.int32, device=dev)
+        self._pending = pending.to(dev).long().contiguous()     # int64 [B]: each sample's final token, not yet fed
+        self._ids = [list(r) for r in ids]
+        self._hidden, self._dtype, self._device, self._turns = hidden, kvc[0].dtype, dev, 1
+
+    batch = property(lambda self: len(self._cached_host))
+    lengths = property(lambda self: [c + 1 for c in self._cached_host])
+    capacity = property(lambda self: self._kvc[0].shape[1])
+    turns = property(lambda self: self._turns)
+    ids = property(lambda self: [list(r) for r in self._ids])
+
+    @staticmethod
+    def book(start, prompt_ids, rows, eos, stop):
+        """the bookkeeping of one turn on the host, per sample: start[b] = the rows of its cache behind the turn's prefill
+        (its history's length up to the prompt's last valid token), prompt_ids[b] = the prompt's valid ids (prompt_ids
+        None: a turn given as embeddings), rows[b] = the ids the call returned for it, eos / stop = the call's.  With c_b
+        the generated tokens up to the final token: -> (cached [B] = start + c - 1, the fed tokens; pending [B] = the
+        final tokens; the known ids the turn adds [B])"""
+        cached, pending, added = [], [], []
+        for b, row in enumerate(rows):
+            c = _session_final(row, eos, stop)
+            cached.append(start[b] + c - 1)
+            pending.append(int(row[c - 1]))
+            added.append(([int(i) for i in prompt_ids[b]] if prompt_ids is not None else []) + [int(i) for i in row[:c]])
+        return cached, pending, added
+
+    def _advance(self, cached, pending, added):
+        self._cached_host = [int(c) for c in cached]
+        self._cached.copy_(torch.tensor(self._cached_host, dtype=torch.int32))
+        self._pending.copy_(torch.tensor(pending, dtype=torch.long))
+        for r, a in zip(self._ids, added):
+            r.extend(a)
+        self._turns += 1
+
+
+def _session_refusal(session, return_session, use_cache, K, N, G, cfg, kv_cache):
+    """generate(session=) / generate(return_session=True), stage (a): what the arguments alone refuse; None: nothing"""
+    if session is None and not return_session:
+        return None
+    what = "generate(session=)" if session is not None else "generate(return_session=True)"
+    if session is not None and not isinstance(session, GenerateSession):
+        return f"{what}: session must be a GenerateSession (generate(return_session=True) returns one), got {type(session).__name__}"
+    if not use_cache:
+        return f"{what} with use_cache=False: a session is its KV cache"
+    if K > 1:
+        return f"{what} with num_beams={K}: sessions along beams are not built; use num_beams=1"
+    if N > 1:
+        return f"{what} with num_samples={N}: a session over parallel samples is not built; use num_samples=1"
+    if G:
+        return f"{what} with prompt_lookup_num_tokens={G}: a verify step over a session's ragged cache is not built"
+    if cfg is not None:
+        return f"{what} with guidance_scale={cfg!r}: a guided session is not built"
+    if kv_cache == "fp8":
+        return f"{what} with kv_cache='fp8': there is no quantised attention over several new positions"
+    return None
 
 
 def _no_decode_graph(decode_graph, max_new_tokens):
@@ -882,7 +971,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
                  negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
-                 bad_words_ids=None, num_samples=1, **_):
+                 bad_words_ids=None, num_samples=1, session=None, return_session=False, session_capacity=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -1097,7 +1186,38 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         do_sample=False (n identical greedy rows: HF refuses it too), with num_beams > 1, prompt_lookup_num_tokens > 0,
         guidance_scale or kv_cache="fp8" (not built); and for n > 1 with use_cache=True and fp32 parameters or a shape
         outside ops.shared_attn_ok / ops.decode_attn_ok (use use_cache=False).  1 (default): today's call -- nothing is
-        allocated, gathered or launched differently."""
+        allocated, gathered or launched differently.
+
+        return_session=True and session=s: multi-turn sessions over a kept KV cache (GenerateSession states the rule; it
+        is written down in include/macaw_hip.h next to mk_flash_attn_varlen_fwd).  A sample's history is built turn by
+        turn: the valid tokens of the turn's prompt, then the turn's generated tokens up to and including the sample's
+        final token -- its eos, the last id of the stop sequence that ended it, or its last token at max_new_tokens; pads
+        behind it never enter.  A continued call returns for every sample what a fresh call would return for that sample
+        alone on history + valid tokens of the new prompt, positions 0 ... len - 1, up to the last bits of its arithmetic
+        (other GEMM row counts, another attention form).  The final token of a turn was emitted but never fed: it is the
+        session's pending token and becomes row 0 of the next prefill; no extra step is run for it.
+        return_session=True: the result becomes (result, session).  A first call runs exactly today's launches and hands
+        over its caches instead of dropping them (session_capacity: the cache rows to allocate, at least today's S0 +
+        max_new_tokens; more avoids a later regrowth).  Steps that run past a sample's end (a finished sample inside a live
+        batch, up to 7 replayed steps) write rows behind its history; they are never read and are overwritten later.
+        session=s: input_ids [B, Sn] or inputs_embeds [B, Sn, D], Sn >= 1, optionally attention_mask [B, Sn] with any
+        padding pattern (every sample needs a valid token).  The valid rows are left-compacted behind the embedding of the
+        pending token (engine.chunk_layout), the caches grow when S0' + max_new_tokens exceeds the capacity (S0' = the
+        longest history; ops.copy2d of the valid rows), the new rows run through the layers once -- ops.kv_append_rows into
+        the compacted cache, then ops.flash_attn_varlen_fwd over it with the per-sample lengths read on the device (head
+        sizes outside that kernel: sample by sample on the host lengths) -- and the existing decode loops follow at one
+        device counter plus a per-sample offset, as for a padded batch: still one hipGraph replay per token, and the host
+        reads nothing new per token.  s is updated IN PLACE (and returned as well under return_session=True).  Composes with
+        decode_weights, sampling, the logits processors and bad_words_ids (their history is s.ids[b] followed by this
+        call's valid input_ids; a turn given as embeddings contributes its generated tokens only), stop_sequences (the
+        window never reaches in front of this call's generated tokens), log-probabilities and LoRA.  The sampler's counter
+        hash uses this call's output column: pass another seed per turn for fresh randomness.  ValueError naming the
+        condition, before anything is allocated, for either argument with use_cache=False, num_beams > 1, num_samples > 1,
+        prompt_lookup_num_tokens > 0, guidance_scale, kv_cache="fp8" (no quantised attention over several new positions),
+        fp32 parameters or a shape outside ops.decode_attn_ok (the continuation needs the per-sample-position step
+        kernels); with session= also for a batch, hidden size, dtype, device or layer count that does not match the
+        session, Sn < 1, a sample without a valid token and an object that is no GenerateSession.  Defaults (None, False,
+        None): not one launch differs."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1180,6 +1300,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 raise ValueError(f"{what} with guidance_scale={guidance_scale!r}: guided parallel samples are not built")
             if kv_cache == "fp8":
                 raise ValueError(f"{what} with kv_cache='fp8': a quantised shared-prompt cache is not built")
+        sess = session is not None or bool(return_session)      # sessions (False: nothing below runs for them)
+        if sess:
+            why = _session_refusal(session, return_session, use_cache, K, N, G, cfg, kv_cache)
+            if why is not None:
+                raise ValueError(why)
+            if session_capacity is not None and (isinstance(session_capacity, bool) or
+                                                 not isinstance(session_capacity, numbers.Integral) or session_capacity < 1):
+                raise ValueError(f"generate: session_capacity must be None or an integer >= 1, got {session_capacity!r}")
         no_graph = _no_decode_graph(decode_graph, max_new_tokens)
         graph = no_graph is None  # the decode step is captured in a hipGraph (the greedy loop also needs decode_attn_ok)
 
@@ -1194,6 +1322,40 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             N = 1
         B, S0, D = inputs_embeds.shape
         dev, dtype = inputs_embeds.device, inputs_embeds.dtype
+        chunk = None              # session=: the continued prefill's layout (None: a first call, nothing below runs)
+        prompt_ids = None         # sessions: per sample the valid ids of this call's prompt (None: embeddings)
+        if session is not None:
+            what, Sn = "generate(session=)", S0
+            mine = dict(batch=B, hidden=D, dtype=dtype, device=dev, layers=len(self.model.layers))
+            theirs = dict(batch=session.batch, hidden=session._hidden, dtype=session._dtype, device=session._device,
+                          layers=len(session._kvc))
+            for k in mine:
+                if mine[k] != theirs[k]:
+                    raise ValueError(f"{what}: {k} {mine[k]} of this call does not match the session's ({theirs[k]})")
+            if Sn < 1:
+                raise ValueError(f"{what}: the new prompt needs at least one token (Sn >= 1), got {Sn}")
+            valid = torch.ones((B, Sn), dtype=torch.bool)
+            if attention_mask is not None:
+                if tuple(attention_mask.shape) != (B, Sn):
+                    raise ValueError(f"{what}: attention_mask should be of size {(B, Sn)}, but is {tuple(attention_mask.shape)}")
+                valid = attention_mask.cpu() != 0
+            try:
+                chunk, ck_pos, ck_last, S0, ck_off = eng.chunk_layout(session._cached_host, valid.sum(1).tolist(), dev)
+            except ValueError as e:
+                raise ValueError(f"{what}: attention_mask: {e}") from None
+            Sq = chunk.slot.shape[1]
+            # row (b, j) of the prefill out of [pending's embeddings (B rows); the prompt's (B * Sn rows)]: the pending token,
+            # the valid rows in order, then the last of them again as filler
+            src = [torch.cat([torch.tensor([b]), torch.nonzero(valid[b]).flatten() + B + b * Sn]) for b in range(B)]
+            ck_src = torch.stack([torch.cat([r, r[-1:].expand(Sq - r.numel())]) for r in src]).reshape(-1).to(dev)
+            if input_ids is not None and tuple(input_ids.shape) == (B, Sn):
+                prompt_ids = [input_ids[b].cpu()[valid[b]].tolist() for b in range(B)]
+            attention_mask = None     # (consumed: from here on S0 = S0', the longest history, where the step counter starts)
+        elif return_session and input_ids is not None:
+            if attention_mask is not None and tuple(input_ids.shape) == tuple(attention_mask.shape):
+                prompt_ids = [input_ids[b].cpu()[attention_mask[b].cpu() != 0].tolist() for b in range(B)]
+            else:
+                prompt_ids = input_ids.cpu().tolist()
         Bs, Sc, own_mask = B, S0, attention_mask     # the samples, their prompt's length and mask as the caller gave them
         if cfg is not None:       # ONE batch of B = 2 Bs token rows under one key mask: the padded-batch path from here on
             neg = negative_inputs_embeds
@@ -1212,6 +1374,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         V = self.lm_head.weight.shape[0]
         hd = D // layers[0].self_attn.num_heads
         Tmax = S0 + max_new_tokens + G        # rows of the KV cache (prompt lookup: the G draft rows behind the last token)
+        if sess:                  # a session's caches: the capacity asked for, or the one it has while that suffices
+            need = Tmax
+            if session_capacity is not None and session_capacity < need and session is None:
+                raise ValueError(f"generate(return_session=True): session_capacity={session_capacity} is below the {need} "
+                                 f"rows this call needs (S0 + max_new_tokens = {S0} + {max_new_tokens})")
+            Tmax = max(need, session_capacity or 0)
+            if session is not None and need <= session.capacity:
+                Tmax = session.capacity
 
         # ---- refusals (b): what needs the shapes, the dtype, the head size or the mask, before anything is allocated
         # a padded batch: engine.Ragged, the prefill's positions, the flat index of each sample's last valid row
@@ -1221,7 +1391,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if padded is not None:
                 ragged, rg_pos, rg_last = padded
         hist = hist_len = None    # the prompt's ids as history (the processors' or the lookup's): [B, P] int64, count per row
-        if (proc is not None or bad is not None) and input_ids is not None:
+        if (proc is not None or bad is not None) and session is not None:
+            # the session's known ids, then this call's valid input_ids
+            rows = [r + (prompt_ids[b] if prompt_ids is not None else []) for b, r in enumerate(session._ids)]
+            hist = torch.zeros((B, max(1, max(len(r) for r in rows))), dtype=torch.long)
+            for b, r in enumerate(rows):
+                hist[b, :len(r)] = torch.tensor(r, dtype=torch.long)
+            hist, hist_len = hist.to(dev), torch.tensor([len(r) for r in rows], dtype=torch.int32, device=dev)
+        elif (proc is not None or bad is not None) and input_ids is not None:
             hist_rg = ragged      # the padding the history leaves out: with guidance the caller's own, of the samples' rows
             if cfg is not None and ragged is not None:
                 own = own_mask is not None and not bool((own_mask != 0).all())
@@ -1252,6 +1429,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                  "for it")
             if input_ids is not None:
                 hist, hist_len = _prompt_history(input_ids, B, dev, "the lookup history")
+        if sess:
+            why = _attn_refusal(dtype, hd, Tmax)
+            if why is not None:
+                raise ValueError(f"generate({'session=' if session is not None else 'return_session=True'}): {why}; a "
+                                 "continued call needs the per-sample-position decode kernels, which take bf16 / fp16 inside "
+                                 "ops.decode_attn_ok")
         if ragged is not None and use_cache:
             why = _attn_refusal(dtype, hd, Tmax)
             if why is not None:
@@ -1379,8 +1562,15 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         elif N > 1:               # the prompt's rows once per prompt, the rows' own tokens per row (engine.SharedPrompt)
             kvc = [torch.empty((B, S0, 2 * D), dtype=dtype, device=dev) for _ in layers]
             tails = [torch.empty((B * N, max_new_tokens, 2 * D), dtype=dtype, device=dev) for _ in layers]
+        elif session is not None and Tmax == session.capacity:
+            kvc = session._kvc
         else:
             kvc = [torch.empty((B, Tmax, 2 * D), dtype=dtype, device=dev) for _ in layers]   # [keys | values]
+            if session is not None:   # regrowth: the rows the histories hold move over, the session keeps the new caches
+                for old, new in zip(session._kvc, kvc):
+                    ops.copy2d(old, new, max(session._cached_host), 2 * D, 2 * D, 2 * D, batch=B,
+                               s_src=session.capacity * 2 * D, s_dst=Tmax * 2 * D)
+                session._kvc = kvc
 
         if getattr(self, "_lora", None) is not None:
             # LoRA adapters: the decode path runs on MERGED copies of the adapted weights (W + s B A, csrc/lora.hip),
@@ -1423,7 +1613,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 w8.append((ql(ws.wqkv, own.wqkv), ql(ws.wo, own.wo), ql(ws.wgu, own.wgu), ql(ws.wd, own.wd)))
             w8_head = q8(self.lm_head.weight, self.lm_head.weight)
 
-        def run(x2, Sn, t0, pos=None, t_dev=None, beam=None, spec=None):
+        def run(x2, Sn, t0, pos=None, t_dev=None, beam=None, spec=None, chunk=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
             for i, lyr in enumerate(layers):
@@ -1439,10 +1629,28 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
                     lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
                     w8=w8[i] if w8 is not None and t_dev is not None else None,
-                    kv8=kvs[i] if kvs is not None else None, ragged=ragged, beam=beam, spec=spec)
+                    kv8=kvs[i] if kvs is not None else None, ragged=ragged if chunk is None else chunk, beam=beam,
+                    spec=spec)
             return x2
 
-        if ragged is not None:    # prefill over the padded rows; token 0 comes from each sample's last valid row
+        def hand_over(res):       # sessions: the books behind the loop -> what generate returns
+            rows = (res.ids if n_top is not None else res).cpu().tolist()
+            if chunk is not None:
+                start = chunk.k_host
+            else:
+                start = ragged.kmask.sum(1).cpu().tolist() if ragged is not None else [S0] * B
+            books = GenerateSession.book(start, prompt_ids, rows, eos_token_id, stop)
+            if session is not None:
+                session._advance(*books)
+            s = session if session is not None else GenerateSession(kvc, books[0], torch.tensor(books[1]), books[2], D, dev)
+            return (res, s) if return_session else res
+
+        if chunk is not None:     # a continued call: the pending token and the new prompt over the kept cache ...
+            table = torch.cat([ops.embedding_fwd(emb_w, session._pending), inputs_embeds.reshape(B * Sn, D)])
+            h = run(ops.embedding_fwd(table, ck_src), Sq, 0, pos=ck_pos, chunk=chunk)
+            last = ops.embedding_fwd(h, ck_last)
+            ragged = eng.Ragged(None, None, ck_off)       # ... then the padded batch's steps at S0' + t + t_off[b]
+        elif ragged is not None:  # prefill over the padded rows; token 0 comes from each sample's last valid row
             h = run(eng._c2(inputs_embeds, B * S0, D), S0, 0, pos=rg_pos)
             last = ops.embedding_fwd(h.view(B * S0, D), rg_last)
         else:
@@ -1459,8 +1667,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             return beam_out(*self._generate_beam(run, logits, last, emb_w, B, K, S0, max_new_tokens, eos_token_id, pad, dev,
                                                  length_penalty, early_stopping, graph))
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
-            return self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
-                                        process, n_top, feed, stopped)
+            res = self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
+                                       process, n_top, feed, stopped)
+            return hand_over(res) if sess else res
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch or of
         # parallel samples
         dyn = ragged is not None or N > 1         # (parallel samples take the padded batch's route: a device position)
@@ -1477,7 +1686,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 t_dev += 1
             else:
                 last = run(x, 1, S0 + t)                                   # decode step
-        return with_logprobs(torch.stack(out, dim=1))
+        res = with_logprobs(torch.stack(out, dim=1))
+        return hand_over(res) if sess else res
 
 
 # ---------------------------------------------------------- multimodal ------
@@ -1640,7 +1850,24 @@ class MM_LLMs(PreTrainedModel):
     # ------------------------------------------------------------ forward ---
     def forward(self, inputs=None):
         _dtype_check(self._param_dtype())
-        text_embeddings, attention_mask, labels = self.prepare_inputs_for_generation(inputs)
+        turn = {}                   # set_session / inputs["session"]: the session arguments of the generate() call
+        if inputs.get("session") is not None:
+            # a follow-up turn: no tower, no alignment, no bos and no modal prefix -- the text ids as they are, over the
+            # session's kept cache
+            given = [k for k in ("images", "audios", "videos") if inputs.get(k) is not None]
+            if given:
+                raise ValueError(f"MM_LLMs.forward: {', '.join(given)} next to inputs['session']: modal rows in a follow-up "
+                                 "turn are not built")
+            ids = inputs["input_ids"]
+            _dev_check(ids)
+            E = self.llm.model.embed_tokens.weight
+            text_embeddings = ops.embedding_fwd(E, ids.long().reshape(-1)).view(*ids.shape, -1)
+            attention_mask, labels = inputs.get("attention_mask"), None
+            turn = dict(session=inputs["session"])
+        else:
+            text_embeddings, attention_mask, labels = self.prepare_inputs_for_generation(inputs)
+        if SESSION[0]:
+            turn["return_session"] = True
         lora = getattr(self.llm, "_lora", None)
         if lora is not None:        # the adapters' dropout follows this model's step seeds (slot 41)
             lora.ext_seed = self._dropout_seed(lora.SLOT)
@@ -1667,7 +1894,7 @@ class MM_LLMs(PreTrainedModel):
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
-                                     **guide, **stopping, **par, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
+                                     **turn, **guide, **stopping, **par, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
     @staticmethod
@@ -1778,6 +2005,17 @@ class MM_LLMs(PreTrainedModel):
         _stopping_check("set_stopping", stop_sequences, bad_words_ids)
         STOPPING[0] = dict(stop_sequences=None if stop_sequences is None else [list(q) for q in stop_sequences],
                            bad_words_ids=None if bad_words_ids is None else [list(q) for q in bad_words_ids])
+
+    @staticmethod
+    def set_session(on=False):
+        """Multi-turn sessions for `inputs["inference"] = True` (LlamaForCausalLM.generate's return_session): off by
+        default.  With it on forward returns (result, session); `inputs["session"] = s` then continues s -- forward runs
+        no tower and no alignment, embeds inputs["input_ids"] as they are (no bos, no modal prefix), passes
+        inputs.get("attention_mask") under set_generate_mask as a first call does, and updates s in place.  images, audios
+        or videos next to a session raise ValueError (modal rows in a follow-up turn are not built).  What depends on the
+        call (beams, parallel samples, prompt lookup, guidance, cache format, dtype) is validated by generate().
+        Process-wide switch, like set_generate_mask."""
+        SESSION[0] = bool(on)
 
     @staticmethod
     def set_parallel_samples(num_samples=1):

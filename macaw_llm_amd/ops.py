@@ -1370,6 +1370,28 @@ def flash_attn_fwd(q, k, v, o, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld, v
     return o
 
 
+def flash_varlen_ok(dtype, hd) -> bool:
+    """the domain of flash_attn_varlen_fwd (besides the 16-byte alignment and the strides % 8 of flash_attn_fwd)"""
+    return dtype in (torch.bfloat16, torch.float16) and hd in (64, 128)
+
+
+def flash_attn_varlen_fwd(q, k, v, o, q_len, k_len, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld, v_bs, o_ld, o_bs,
+                          scale, lse=None, q_off=0, k_off=0, v_off=0, o_off=0):
+    """the causal fused forward with per-sample lengths on the device (q_len / k_len int32 [B]; Lq / Lk host upper
+    bounds): row i < q_len[b] of sample b sees key j iff j < k_len[b] and j <= i + (k_len[b] - q_len[b]); every other
+    row gets o = 0 and lse = -inf; k / v rows >= k_len[b] are never read (macaw_hip.h: mk_flash_attn_varlen_fwd).
+    k and v may be the two halves of a [B, t_max, 2D] cache (k_ld = v_ld = 2D, v_off = D)"""
+    lib = _L.load()
+    es = q.element_size()
+    _i32_check("flash_attn_varlen_fwd", "q_len", q_len, B)
+    _i32_check("flash_attn_varlen_fwd", "k_len", k_len, B)
+    _L.check(lib.mk_flash_attn_varlen_fwd(_p(q) + q_off * es, _p(k) + k_off * es, _p(v) + v_off * es,
+                                          _p(o) + o_off * es, _p(lse), _p(q_len), _p(k_len), B, H, Lq, Lk, hd, q_ld,
+                                          q_bs, k_ld, k_bs, v_ld, v_bs, o_ld, o_bs, float(scale), dt(q), _st()),
+             "mk_flash_attn_varlen_fwd")
+    return o
+
+
 def flash_attn_bwd(q, k, v, o, dout, lse, dq, dk, dv, B, H, Lq, Lk, hd, q_ld, q_bs, k_ld, k_bs, v_ld,
                    v_bs, o_ld, o_bs, scale, kmask=None, causal=False, rope=None, qk_rotated=False):
     """rope = (cos_t, sin_t, pos): dq / dk come back as gradients of the UNROTATED q, k; q and k themselves are

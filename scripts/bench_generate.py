@@ -70,6 +70,14 @@ with torch.no_grad():
 # step is captured anew by every generate() call).  ms per token of every run, the medians and each arm's run-to-run spread, the time to the first
 # token (the call with max_new_tokens=1: prefill + token 0), and the KV bytes each arm allocates for the 72-token call (from the
 # shapes, and the allocator's peak over the call)
+#        bench_generate.py --session-ab [--prompt-tokens N] [--reps R] [B ...]: a second turn over a kept KV cache (default
+# B = 1, 8; N = 1900: a 1916-row first prompt).  Turn 1 = the image + audio + text prompt plus 64 new tokens; turn 2 = 32 prompt
+# tokens plus new tokens.  Two arms alternated in this process on this model: "session" = generate(session=s) on the session
+# turn 1 returned (a fresh, untimed turn 1 in front of every timed call: a call advances its session) and "fresh" = today's only
+# way, one call on the concatenated history [turn 1's prompt | its 64 tokens | turn 2's prompt].  Time to the first token of
+# turn 2 (the call with max_new_tokens=1) and ms per token ((72 - 8 tokens) / 64), each with its run-to-run spread; then what a
+# follow-up turn through MM_LLMs skips on top: the towers and the alignment (prepare_inputs_for_generation), timed alone
+SESSION = "--session-ab" in sys.argv
 NSAMPLE = "--nsample-ab" in sys.argv
 STOP = "--stop-ab" in sys.argv
 CFG = "--cfg-ab" in sys.argv
@@ -84,9 +92,92 @@ SAMPLE = "--sample-ab" in sys.argv
 KV8 = "--kv8-ab" in sys.argv
 _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
-PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED else 128)
+PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if SESSION:
+    from macaw_llm_amd import ops
+    E = model.llm.model.embed_tokens.weight
+    V = model.llm.lm_head.weight.shape[0]
+    ARMS = ("session", "fresh")
+    for B in [int(a) for a in _args] or [1, 8]:
+        inp = synthetic_inputs(cfg, B, PROMPT, modalities=("images", "audios"), seed=2, device=dev)
+        ids2 = torch.randint(3, V, (B, 32), generator=torch.Generator().manual_seed(3)).to(dev)
+        first, ms, tower = {a: [] for a in ARMS}, {a: [] for a in ARMS}, []
+        with torch.no_grad():
+            for rep in range(REPS + 1):             # what a follow-up turn through MM_LLMs also skips (rep 0 untimed)
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                emb1 = model.prepare_inputs_for_generation(inp)[0]
+                torch.cuda.synchronize(); tower.append((time.perf_counter() - t0) * 1e3)
+            S0 = emb1.shape[1]
+            emb2 = ops.embedding_fwd(E, ids2.reshape(-1)).view(B, 32, -1)
+
+            def turn1():                            # rows for both turns: no regrowth inside the timed call
+                return model.llm.generate(inputs_embeds=emb1, max_new_tokens=64, eos_token_id=-1, return_session=True,
+                                          session_capacity=S0 + 64 + 33 + 72)
+            out1 = turn1()[0]
+            cat = torch.cat([emb1, ops.embedding_fwd(E, out1.reshape(-1)).view(B, 64, -1), emb2], dim=1).contiguous()
+
+            def call(arm, new):                     # -> (ids, seconds)
+                s = turn1()[1] if arm == "session" else None
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                if arm == "session":
+                    ids = model.llm.generate(session=s, inputs_embeds=emb2, max_new_tokens=new, eos_token_id=-1)
+                else:
+                    ids = model.llm.generate(inputs_embeds=cat, max_new_tokens=new, eos_token_id=-1)
+                torch.cuda.synchronize()
+                return ids, time.perf_counter() - t0
+            for arm in ARMS:                                # untimed: each arm's first calls at this size
+                call(arm, 1)
+            same = [call(arm, 8)[0] for arm in ARMS]
+            print(f"B={B:2d} S0={S0}: the arms' first 8 ids agree in {int((same[0] == same[1]).sum())} of {same[0].numel()} places "
+                  "(equal up to the last bits of their arithmetic: other GEMM row counts, another attention form)", flush=True)
+            for rep in range(REPS):
+                for arm in ARMS:
+                    t = {}
+                    for new in (1, 8, 72):
+                        ids, t[new] = call(arm, new)
+                        assert ids.shape == (B, new)
+                    first[arm].append(t[1] * 1e3)
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} S0={S0} rep {rep} {arm:8s}: first token of turn 2 {first[arm][-1]:8.2f} ms, decode {ms[arm][-1]:6.3f} ms/token",
+                          flush=True)
+        med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+        spr = lambda v: max(v) - min(v)  # noqa: E731
+        for a in ARMS:
+            print(f"B={B:2d} S0={S0}: {a:8s} first token of turn 2 {med(first[a]):8.2f} ms (run-to-run spread {spr(first[a]):6.2f} ms), "
+                  f"{med(ms[a]):6.3f} ms/token (spread {spr(ms[a]) * 1e3:6.1f} us = {spr(ms[a]) / med(ms[a]) * 100:4.1f} %)", flush=True)
+        d = med(ms["session"]) - med(ms["fresh"])
+        print(f"B={B:2d} S0={S0}: session / fresh = {med(first['session']) / med(first['fresh']):5.3f} to the first token of turn 2 "
+              f"({med(first['fresh']) - med(first['session']):+8.2f} ms saved), session - fresh = {d * 1e3:+7.1f} us per token "
+              f"({d / med(ms['fresh']) * 100:+5.2f} %): {'inside' if abs(d) <= max(spr(ms['session']), spr(ms['fresh'])) else 'OUTSIDE'} "
+              f"the larger of the two spreads; towers + alignment of the first turn, skipped by a follow-up turn through MM_LLMs: "
+              f"{med(tower[1:]):8.2f} ms (spread {spr(tower[1:]):6.2f} ms)", flush=True)
+        # the variable-length launch of turn 2's prefill by itself: 200 back-to-back launches between two events, after 20
+        # warm-up launches, at the continued call's shape (33 new rows per sample over S0 + 64 + 32 keys)
+        lcfg = model.llm.config
+        H, D = lcfg.num_attention_heads, lcfg.hidden_size
+        hd, Lq, Lk, cap = D // H, 33, S0 + 64 + 32, S0 + 64 + 33 + 72
+        g = torch.Generator(device=dev).manual_seed(4)
+        q = torch.randn((B * Lq, 3 * D), generator=g, device=dev).to(torch.bfloat16)
+        kv = torch.randn((B, cap, 2 * D), generator=g, device=dev).to(torch.bfloat16)
+        o = torch.empty((B * Lq, D), dtype=torch.bfloat16, device=dev)
+        ql = torch.full((B,), Lq, dtype=torch.int32, device=dev)
+        kl = torch.full((B,), Lk, dtype=torch.int32, device=dev)
+        fn = lambda: ops.flash_attn_varlen_fwd(q, kv, kv, o, ql, kl, B, H, Lq, Lk, hd, 3 * D, Lq * 3 * D, 2 * D, cap * 2 * D,  # noqa: E731
+                                               2 * D, cap * 2 * D, D, Lq * D, hd ** -0.5, v_off=D)
+        for i in range(20):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(200):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) / 200 * 1e3
+        print(f"B={B:2d}: one mk_flash_attn_varlen_fwd launch at H={H}, {Lq} query rows over {Lk} keys, hd={hd} (back to back, incl. launch "
+              f"gaps): {us:7.1f} us; x {lcfg.num_hidden_layers} layers = {us * lcfg.num_hidden_layers / 1e3:6.2f} ms of the "
+              f"{med(first['session']):6.2f} ms to the first token of turn 2", flush=True)
+    sys.exit(0)
 if NSAMPLE:
     lcfg = model.llm.config
     NL, D = lcfg.num_hidden_layers, lcfg.hidden_size
