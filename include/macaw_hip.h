@@ -995,6 +995,27 @@ int mk_lora_bwd_x(const void* X, int64_t ldx, int32_t M, int32_t K, const void* 
 int mk_lora_merge(void* W, int64_t ldw, int32_t N, int32_t K, const void* A, const void* B, int32_t r,
                   float s, void* ws, int64_t ws_bytes, int32_t dtype, void* stream);
 
+/* Mixed-adapter LoRA of a decode step (csrc/lora_bgmv.hip; generate(adapter_names=), lora.AdapterBank): token row m
+ * uses adapter idx[m] (DEVICE int32 [M], read by the kernels: hipGraph-replayable).  A [n_adapters, G r, K] and
+ * B [n_adapters, G N, r] stack the group's matrices row-concatenated, one slab per adapter; s: DEVICE f32 [n_adapters].
+ *  - mk_lora_bgmv_shrink: U[m, c] = rnd16(sum_k p(X)[m, k] A[idx[m]][c, k]), c < G r, U [M, G r] at pitch ldu.
+ *    p = the token prologue of mk_decode_linear with ITS rounding points (0 none; 1 RMSNorm(X; norm_w, eps),
+ *    w * rnd16(x * rstd) as mk_rmsnorm_fwd; 2 SwiGLU of X = [gate | up] [M, 2 K], rnd16(rnd16(silu(gate)) * up) as
+ *    mk_swiglu2d_fwd): prologue 1 / 2 on X gives the bits of prologue 0 on the prepared rows.
+ *  - mk_lora_bgmv_expand: Y[m, i N + n] = rnd16(Y[m, i N + n] + s[idx[m]] sum_j U[m, i r + j] B[idx[m]][i N + n, j]),
+ *    Y [M, >= G N] at pitch ldy, one rounding; a column whose sum is exactly 0 (zero-filled rank / module) is not written.
+ * Accumulation is fp32 in an order fixed by (K, r): a row's bits do not depend on M or on the other rows, a row computed
+ * in a batch equals the row computed alone, no float atomics.  A row with idx[m] outside [0, n_adapters) reads no adapter
+ * memory: shrink writes it as a zero row of U, expand does not touch its row of Y.
+ * Domain: bf16 / f16, M <= 32, K % 8 == 0 (K <= 30712: the prepared row sits in LDS), N % 8 == 0, r % 8 == 0 in [8, 128], G in [1, 3], pitches
+ * multiples of 8, 16-byte aligned pointers; else MK_ERR_UNSUPPORTED.  Launch kind 4 of the in-library profiler. */
+int mk_lora_bgmv_shrink(const void* X, int64_t ldx, int32_t M, int32_t K, const void* A, int32_t n_adapters,
+                        int32_t G, int32_t r, const int32_t* idx, int32_t prologue, const void* norm_w, float eps,
+                        void* U, int64_t ldu, int32_t dtype, void* stream);
+int mk_lora_bgmv_expand(const void* U, int64_t ldu, int32_t M, int32_t G, int32_t r, const void* B, const float* s,
+                        int32_t n_adapters, const int32_t* idx, void* Y, int64_t ldy, int32_t N, int32_t dtype,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -700,6 +700,56 @@ class SharedPrompt(NamedTuple):
     S0: int                  # prompt rows per sample of `prompt`
 
 
+class AdapterGroup(NamedTuple):
+    """the stacks of one LORA_GROUPS entry of one layer in a lora.AdapterBank, one slab per adapter: the group's G
+    modules row-concatenated, ranks below r (the bank's largest) and untargeted modules zero-filled"""
+    A: torch.Tensor          # [n, G r, K]
+    B: torch.Tensor          # [n, G N, r]
+    s: torch.Tensor          # f32 [n]: lora_alpha / r of each adapter
+    G: int
+
+
+class Adapters(NamedTuple):
+    """mixed-adapter LoRA for llama_layer_cached (generate(adapter_names=)), passed IN PLACE of w8, whose copies it carries,
+    so that the signature every other caller binds to stays what it is.  A decode step reads idx on the device (the
+    mk_lora_bgmv kernels around each streamed linear: _stream_linear); the prefill walks `runs` on the host"""
+    idx: torch.Tensor        # int32 [rows of a step]: the adapter of each row, -1 = the base model
+    runs: tuple              # ((b0, b1, a), ...): the maximal runs of consecutive samples [b0, b1) with the same adapter a >= 0
+    s_host: tuple            # lora_alpha / r per adapter, once more on the host for the prefill's launches
+    qkv: Optional[AdapterGroup]      # this layer's stacks, in LORA_GROUPS order (None: no adapter targets the group here)
+    o: Optional[AdapterGroup]
+    gu: Optional[AdapterGroup]
+    down: Optional[AdapterGroup]
+    w8: Optional[tuple] = None       # what w8 would have carried
+
+
+class Adapted(NamedTuple):
+    """_stream_linear's q8 argument for a group that carries adapters: the rows' adapters, the group's stacks and the
+    quantised copy (or None) that q8 would have been"""
+    idx: torch.Tensor
+    group: AdapterGroup
+    q8: Optional[tuple]
+
+
+def _adapted(ad, group, q8):
+    return Adapted(ad.idx, group, q8) if ad is not None and group is not None else q8
+
+
+def _lora_runs(ad, name, x, ys, Sn):
+    """the prefill's adapters of the group `name` (ad: an Adapters or None): per run of samples with one adapter,
+    ys_i[rows] += s U_i B_i^T on the run's contiguous row slice with the MFMA kernels of csrc/lora.hip (p = 0); base
+    runs are skipped"""
+    group = getattr(ad, name) if ad is not None else None
+    if group is None:
+        return
+    G = group.G
+    r, N = group.A.shape[1] // G, group.B.shape[1] // G
+    for b0, b1, a in ad.runs:
+        r0, r1 = b0 * Sn, b1 * Sn
+        U, _ = ops.lora_down(x[r0:r1], [group.A[a, i * r:(i + 1) * r] for i in range(G)])
+        ops.lora_up_add_(U, [group.B[a, i * N:(i + 1) * N] for i in range(G)], [y[r0:r1] for y in ys], ad.s_host[a])
+
+
 def ragged_from_mask(mask, B, S0):
     """The host side of generate(attention_mask=): mask [B, S0], any integer or bool dtype, non-zero = valid.
     Returns None for a mask without a zero (the unpadded path), else (Ragged, pos, last):
@@ -805,21 +855,35 @@ def _stream_linear(x, W, q8, pro, w_ln, eps, residual, FF):
     separate RMSNorm / SwiGLU kernel runs first and the PLAIN launch follows, so every batch size up to 32 streams
     the bytes it was given.  A 16-bit weight outside ops.decode_linear's domain goes through ops.linear_fwd.
     A copy whose second member is uint8 is an MXFP4 copy (codes uint8 [N, K / 2], block exponents uint8 [N, K / 32]:
-    ops.mxfp4_weight) and streams through ops.decode_linear_mxfp4 under the same rule."""
+    ops.mxfp4_weight) and streams through ops.decode_linear_mxfp4 under the same rule.
+    q8 an Adapted (the rows' adapters and the group's stacks around the copy, or None, that q8 would have been): the
+    16-bit adapters go on top of whichever base launch runs.  ops.lora_bgmv_shrink takes the (x, prologue) the base
+    launch takes, or the prepared x of the fallback branch -- the same bits either way --, the base launch is unchanged,
+    and ops.lora_bgmv_expand_ adds into its output (behind the residual, where LlamaLayerFn adds the adapter)."""
+    ad = None
+    if isinstance(q8, Adapted):
+        ad, q8 = q8, q8.q8
+
+    def around(base, xs, p):    # shrink, the base launch, expand
+        if ad is None:
+            return base()
+        U = ops.lora_bgmv_shrink(xs, ad.group.A, ad.idx, ad.group.G, p, w_ln if p == 1 else None, eps)
+        return ops.lora_bgmv_expand_(U, ad.group.B, ad.group.s, ad.idx, base(), ad.group.G)
+
     if q8 is not None:      # the kind of a copy, per entry: uint8 block exponents = MXFP4, f32 channel scales = e4m3
         mx = q8[1].dtype == torch.uint8
         lin, ok = (ops.decode_linear_mxfp4, ops.decode_linear_mxfp4_ok) if mx else (ops.decode_linear_fp8, ops.decode_linear_fp8_ok)
         if ok(x, q8[0], pro):
-            return lin(x, q8[0], q8[1], pro, w_ln, eps, residual)
+            return around(lambda: lin(x, q8[0], q8[1], pro, w_ln, eps, residual), x, pro)
     elif ops.decode_linear_ok(x, W, pro):
-        return ops.decode_linear(x, W, pro, w_ln, eps, residual)
+        return around(lambda: ops.decode_linear(x, W, pro, w_ln, eps, residual), x, pro)
     if pro == 1:
         x = ops.rmsnorm_fwd(x, w_ln, eps)[1]
     elif pro == 2:
         x = ops.swiglu2d_fwd(x, FF)
     if q8 is not None:
-        return lin(x, q8[0], q8[1], residual=residual)
-    return ops.linear_fwd(x, W, residual=residual)
+        return around(lambda: lin(x, q8[0], q8[1], residual=residual), x, 0)
+    return around(lambda: ops.linear_fwd(x, W, residual=residual), x, 0)
 
 
 def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq, wk, wv, wo, wg, wu,
@@ -882,9 +946,21 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     attends over the cache's two halves with the lengths read on the device; where that kernel does not take the head
     size (ops.flash_varlen_ok), the samples run one by one through attention_fwd at their host lengths.  Filler rows
     come out as zeros.  The decode steps that follow are the ragged batch's (Ragged.t_off = chunk_layout's t_off).  Not
-    with kv8, beam, spec, a SharedPrompt or t_dev."""
+    with kv8, beam, spec, a SharedPrompt or t_dev.
+
+    w8 an Adapters (passed IN PLACE of the copies, which it carries in its own w8 field): mixed-adapter LoRA, row m of a
+    step using adapter ad.idx[m] of the layer's stacks (-1: the base model).  A step must be the five-launch one (t_dev,
+    fused storage, 16-bit, at most 32 rows: ValueError otherwise) and wraps each streamed linear in the mk_lora_bgmv pair
+    (_stream_linear); the prefill adds the adapters per run of samples with the MFMA kernels (_lora_runs) at the four
+    points where LlamaLayerFn adds them, fused storage or not.  Not with beam, spec, a SharedPrompt or a Chunk."""
     M, D = x2.shape
     dyn = t_dev is not None
+    ad = None
+    if isinstance(w8, Adapters):
+        ad, w8 = w8, w8.w8
+        if beam is not None or spec is not None or isinstance(kvc, SharedPrompt) or isinstance(ragged, Chunk):
+            raise ValueError("llama_layer_cached: Adapters map rows to samples one to one: not with beam, spec, a "
+                             "SharedPrompt or a Chunk")
     chunk = None
     if isinstance(ragged, Chunk):
         chunk, ragged = ragged, None
@@ -917,6 +993,9 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     if w8 is not None and not step:
         raise ValueError("llama_layer_cached: w8 is for the five-launch decode step (t_dev, fused q|k|v and "
                          "gate|up storage, at most 32 rows)")
+    if ad is not None and dyn and not (step and ad.idx.numel() == M):
+        raise ValueError("llama_layer_cached: a decode step with Adapters is the five-launch one (t_dev, fused q|k|v and "
+                         "gate|up storage, bf16 / fp16, at most 32 rows, one adapter index per row)")
     H, hd = n_heads, D // n_heads
     FF = wg.shape[0]
     att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
@@ -926,6 +1005,9 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         # 16-bit or (w8) its e4m3 copy: _stream_linear.  o asks ops.decode_linear_ok like the other three, with or
         # without w8; under the gate above that matters only for a non-contiguous wo, which takes ops.linear_fwd.
         q_qkv, q_o, q_gu, q_d = w8 if w8 is not None else (None,) * 4
+        if ad is not None:      # each group's adapters ride in front of its copy (Adapted)
+            q_qkv, q_o = _adapted(ad, ad.qkv, q_qkv), _adapted(ad, ad.o, q_o)
+            q_gu, q_d = _adapted(ad, ad.gu, q_gu), _adapted(ad, ad.down, q_d)
         qkv = _stream_linear(x2, wqkv, q_qkv, 1, ln1, eps, None, FF)
         _step_attn(qkv, qkv, qkv, 3 * D, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, spec, k_off=D,
                    v_off=2 * D)
@@ -947,6 +1029,7 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         ldq = D
         new, off = (q, k, v), {}
         ropes, appends = ((q, H), (k, H)), ((k, D, 0, 0), (v, D, 0, D))
+    _lora_runs(ad, "qkv", y1, (q, k, v), Sn)
     if dyn:     # RoPE + cache append + attention of the new position: one launch
         _step_attn(*new, ldq, cos, sin, kvc, kv8, t_dev, Tmax, B, H, hd, att, scale, ragged, beam, spec, **off)
     elif chunk is not None:
@@ -990,12 +1073,19 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
         elif kv8 is not None:
             ops.kv_quant_append(k, v, ldq, Sn * ldq, kvc, kv8, 0, Sn, Tmax, B, H, hd)
     h1 = ops.linear_fwd(att, wo, residual=x2)
+    _lora_runs(ad, "o", att, (h1,), Sn)
     _, y2, _ = ops.rmsnorm_fwd(h1, ln2, eps)
     if wgu is not None:
-        a = ops.swiglu2d_fwd(ops.linear_fwd(y2, wgu), FF)
+        gu = ops.linear_fwd(y2, wgu)
+        _lora_runs(ad, "gu", y2, (gu[:, :FF], gu[:, FF:]), Sn)
+        a = ops.swiglu2d_fwd(gu, FF)
     else:
-        a = ops.swiglu_fwd(ops.linear_fwd(y2, wg), ops.linear_fwd(y2, wu))
-    return ops.linear_fwd(a, wd, residual=h1)
+        g, u = ops.linear_fwd(y2, wg), ops.linear_fwd(y2, wu)
+        _lora_runs(ad, "gu", y2, (g, u), Sn)
+        a = ops.swiglu_fwd(g, u)
+    out = ops.linear_fwd(a, wd, residual=h1)
+    _lora_runs(ad, "down", a, (out,), Sn)
+    return out
 
 
 # =========================================================================

@@ -174,6 +174,8 @@ SIGNATURES = {
     "mk_lora_bwd_x": [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f32, _u64, _vp, _vp, _i64, _vp,
                       _vp, _vp, _vp, _i64, _i32, _vp],
     "mk_lora_merge": [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _f32, _vp, _i64, _i32, _vp],
+    "mk_lora_bgmv_shrink": [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _vp, _i64, _i32, _vp],
+    "mk_lora_bgmv_expand": [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp],
 }
 
 _lib = None

@@ -15,6 +15,10 @@ The products run in csrc/lora.hip, called by engine.LlamaLayerFn at four points 
 RoPE, o after its residual GEMM, gate|up before SwiGLU, down after its residual GEMM).  Masks are regenerated
 from a counter hash of (step seed, layer, module, element), never stored.  generate() merges the adapters
 into temporary copies of the targeted weights for the duration of the call (see LlamaForCausalLM.generate).
+
+Several frozen adapters of one base model decode in ONE batch through AdapterBank (below) and
+generate(adapter_names=[...]): nothing is merged, every row names its adapter ("__base__" for none), and the decode
+step adds it with the mk_lora_bgmv kernels of csrc/lora_bgmv.hip.
 """
 from __future__ import annotations
 
@@ -284,3 +288,128 @@ def merge_and_unload(model):
     if hasattr(model, "peft_config"):
         del model.peft_config
     return model
+
+
+# =========================================================================
+# Mixed-adapter decoding: generate(adapter_names=[...])
+# =========================================================================
+BASE = "__base__"       # the name of "no adapter" in generate(adapter_names=), as in peft's mixed adapter batches
+
+
+class AdapterBank:
+    """Frozen, inference-only adapters of one LlamaForCausalLM for generate(adapter_names=[...]), kept next to the model
+    (model._lora_bank), never inside it: the model's own parameters and modules stay what they are.
+
+        bank = AdapterBank(model.llm)
+        bank.add("image", "out/lora_image")                      # a save_lora / peft directory
+        bank.add("live", state_dict=lora_state_dict(m), config=m._lora.config)
+        model.llm.generate(..., adapter_names=["image", "__base__", "live", "image"])
+
+    Adapters may differ in rank and in target modules.  Per (layer, group of engine.LORA_GROUPS) the bank keeps the
+    stacks the mk_lora_bgmv kernels index by a row's adapter: A [n, G r_max, K], B [n, G N, r_max] and s [n] =
+    lora_alpha / r of each adapter, the group's modules row-concatenated; a smaller rank and an untargeted module are
+    zero-filled, which is exact (their products are zeros).  A group no adapter targets at a layer has no stack, and no
+    launch.  The stacks are built on first use and rebuilt after an add()."""
+
+    def __init__(self, model):
+        self.model = _llama_causal(model)
+        self.names: List[str] = []      # adapter i is names[i]
+        self.configs: List[LoraConfig] = []
+        self._weights = []              # per adapter {(layer, module index): (A [r, K], B [N, r])}
+        self._stacks = None
+        self.model._lora_bank = self
+
+    def add(self, name: str, directory: Optional[str] = None, *, state_dict: Optional[dict] = None,
+            config: Optional[LoraConfig] = None):
+        """add the adapter saved in `directory` (save_lora's / peft's adapter_config.json + adapter_model.bin), or the
+        given state_dict (lora_state_dict's keys) with its LoraConfig, under `name`; returns the bank"""
+        if name == BASE:
+            raise ValueError(f"AdapterBank.add: {BASE!r} names the base model in adapter_names; choose another name")
+        if name in self.names:
+            raise ValueError(f"AdapterBank.add: the bank already has an adapter {name!r}")
+        if (directory is None) == (state_dict is None) or (state_dict is not None and config is None):
+            raise ValueError("AdapterBank.add: pass a directory, or state_dict= with its config=")
+        if directory is not None:
+            with open(os.path.join(directory, "adapter_config.json")) as f:
+                config = LoraConfig.from_dict(json.load(f))
+            state_dict = torch.load(os.path.join(directory, "adapter_model.bin"), map_location="cpu")
+        elif isinstance(config, dict):
+            config = LoraConfig.from_dict(config)
+        _check(config)
+        tg = _targets(self.model, config)
+        want = {f"base_model.model.{key}.lora_{ab}.weight" for key, _, _, _ in tg for ab in "AB"}
+        if set(state_dict) != want:
+            raise KeyError(f"adapter file does not match the model: missing {sorted(want - set(state_dict))[:4]}, "
+                           f"unexpected {sorted(set(state_dict) - want)[:4]}")
+        ws = {}
+        for key, li, mi, lin in tg:
+            w = lin.weight
+            A = state_dict[f"base_model.model.{key}.lora_A.weight"].detach().to(device=w.device, dtype=w.dtype)
+            B = state_dict[f"base_model.model.{key}.lora_B.weight"].detach().to(device=w.device, dtype=w.dtype)
+            if tuple(A.shape) != (config.r, lin.in_features) or tuple(B.shape) != (lin.out_features, config.r):
+                raise KeyError(f"adapter file does not match the model: {key} has A {tuple(A.shape)}, B {tuple(B.shape)} "
+                               f"for r = {config.r} on a [{lin.out_features}, {lin.in_features}] projection")
+            ws[(li, mi)] = (A.clone(), B.clone())
+        self.names.append(name)
+        self.configs.append(config)
+        self._weights.append(ws)
+        self._stacks = None
+        return self
+
+    def indices(self, names) -> List[int]:
+        """adapter_names -> the index of each in the bank, -1 for "__base__"; ValueError for an unknown name"""
+        lut = {n: i for i, n in enumerate(self.names)}
+        unknown = [n for n in names if n != BASE and n not in lut]
+        if unknown:
+            raise ValueError(f"generate(adapter_names=): unknown adapter name(s) {unknown[:4]}; the bank has "
+                             f"{self.names} and {BASE!r} for none")
+        return [-1 if n == BASE else lut[n] for n in names]
+
+    @staticmethod
+    def runs(indices):
+        """((b0, b1, a), ...): the maximal runs of consecutive samples [b0, b1) with the same adapter a >= 0"""
+        out, b0 = [], 0
+        for b in range(1, len(indices) + 1):
+            if b == len(indices) or indices[b] != indices[b0]:
+                if indices[b0] >= 0:
+                    out.append((b0, b, indices[b0]))
+                b0 = b
+        return tuple(out)
+
+    def scalings(self):
+        return tuple(float(c.scaling) for c in self.configs)
+
+    @torch.no_grad()
+    def stacks(self):
+        """per layer the four engine.AdapterGroup (or None) in engine.LORA_GROUPS order"""
+        if self._stacks is not None:
+            return self._stacks
+        n = len(self.names)
+        rmax = max((c.r for c in self.configs), default=0)
+        out = []
+        for li, layer in enumerate(self.model.model.layers):
+            a, m = layer.self_attn, layer.mlp
+            lins = (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj)
+            groups = []
+            for _, members in eng.LORA_GROUPS:
+                if not any((li, mi) in ws for ws in self._weights for mi in members):
+                    groups.append(None)
+                    continue
+                G, w0 = len(members), lins[members[0]].weight
+                N, K = w0.shape
+                if any(tuple(lins[mi].weight.shape) != (N, K) for mi in members):
+                    raise NotImplementedError("AdapterBank: the projections of a group differ in shape (grouped-query "
+                                              "attention is not built)")
+                A = torch.zeros((n, G * rmax, K), dtype=w0.dtype, device=w0.device)
+                B = torch.zeros((n, G * N, rmax), dtype=w0.dtype, device=w0.device)
+                for ai, ws in enumerate(self._weights):
+                    for i, mi in enumerate(members):
+                        if (li, mi) in ws:
+                            Aa, Ba = ws[(li, mi)]
+                            A[ai, i * rmax:i * rmax + Aa.shape[0]] = Aa
+                            B[ai, i * N:(i + 1) * N, :Ba.shape[1]] = Ba
+                s = torch.tensor(self.scalings(), dtype=torch.float32, device=w0.device)
+                groups.append(eng.AdapterGroup(A, B, s, G))
+            out.append(tuple(groups))
+        self._stacks = out
+        return out

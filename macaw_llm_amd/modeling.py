@@ -79,6 +79,8 @@ STOPPING = [dict(stop_sequences=None, bad_words_ids=None)]
 PARALLEL_SAMPLES = [1]
 # MM_LLMs.set_session: whether MM_LLMs.forward asks generate() for the call's GenerateSession (return_session=True)
 SESSION = [False]
+# MM_LLMs.set_adapters: the adapter_names MM_LLMs.forward hands to generate() (None = off: the call without them)
+ADAPTERS = [None]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -971,7 +973,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
                  negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
-                 bad_words_ids=None, num_samples=1, session=None, return_session=False, session_capacity=None, **_):
+                 bad_words_ids=None, num_samples=1, session=None, return_session=False, session_capacity=None,
+                 adapter_names=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -1217,7 +1220,24 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         fp32 parameters or a shape outside ops.decode_attn_ok (the continuation needs the per-sample-position step
         kernels); with session= also for a batch, hidden size, dtype, device or layer count that does not match the
         session, Sn < 1, a sample without a valid token and an object that is no GenerateSession.  Defaults (None, False,
-        None): not one launch differs."""
+        None): not one launch differs.
+
+        adapter_names=[...] (peft's mixed adapter batches, vLLM's per-request LoRA): one name per sample out of the model's
+        lora.AdapterBank (model._lora_bank), "__base__" for none, so one batch serves several fine-tuned adapters of the
+        base model, or an adapter next to it.  Nothing is merged: the base launches stream the STORED weights -- with
+        decode_weights their cached quantised copies, made once -- and the 16-bit adapters go on top.  The prefill adds them
+        per run of consecutive samples with the same adapter (the MFMA kernels of csrc/lora.hip on the run's rows); a decode
+        step wraps each of its four streamed linears in ops.lora_bgmv_shrink / ops.lora_bgmv_expand_ (csrc/lora_bgmv.hip),
+        which read each row's adapter index on the device, so a step still is one hipGraph replay -- of 5 + 8 launches per
+        layer.  Those small launches are latency: for ONE adapter the merged path (a live get_peft_model / load_lora adapter
+        and no adapter_names) stays the faster one and the default (profiles/decode_adapters_generate.txt).  A row's
+        tokens do not depend on the other rows' adapters, bit for bit.  Composes with greedy and sampling, attention_mask,
+        decode_weights, kv_cache="fp8", the logits processors, stop sequences, bad words and log-probabilities; the eager
+        loop (decode_graph=False) runs the same step launches one by one.  ValueError naming the condition for an unknown
+        name, a wrong count of names, a model without a bank or with a live adapter as well, fp32, use_cache=False, unfused
+        storage, more than 32 rows, a shape outside ops.decode_attn_ok, num_beams > 1, num_samples > 1,
+        prompt_lookup_num_tokens > 0, guidance_scale and sessions (each maps rows to samples in its own way: not built).
+        None (the default): not one launch differs."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1308,6 +1328,30 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if session_capacity is not None and (isinstance(session_capacity, bool) or
                                                  not isinstance(session_capacity, numbers.Integral) or session_capacity < 1):
                 raise ValueError(f"generate: session_capacity must be None or an integer >= 1, got {session_capacity!r}")
+        bank = None               # adapter_names: the model's AdapterBank (None: off, nothing below runs)
+        if adapter_names is not None:
+            what = "generate(adapter_names=)"
+            bank = getattr(self, "_lora_bank", None)
+            why = None
+            if bank is None:
+                why = "the model has no adapter bank (lora.AdapterBank(model).add(name, directory))"
+            elif getattr(self, "_lora", None) is not None:
+                why = ("the model also carries a live adapter (get_peft_model / load_lora), which generate() merges; "
+                       "merge_and_unload() it or put it into the bank")
+            elif K > 1:
+                why = f"num_beams={K} > 1 (adapters along beams are not built)"
+            elif N > 1:
+                why = f"num_samples={N} > 1 (adapters over a shared prompt cache are not built)"
+            elif G:
+                why = f"prompt_lookup_num_tokens={G} (an adapted verify step is not built)"
+            elif cfg is not None:
+                why = f"guidance_scale={guidance_scale!r} (adapters on the guided pair of rows are not built)"
+            elif sess:
+                why = "session= / return_session=True (a session does not keep its rows' adapters: not built)"
+            elif not use_cache:
+                why = "use_cache=False (the recompute loop runs the training layer, which has no per-row adapters)"
+            if why is not None:
+                raise ValueError(f"{what}: {why}")
         no_graph = _no_decode_graph(decode_graph, max_new_tokens)
         graph = no_graph is None  # the decode step is captured in a hipGraph (the greedy loop also needs decode_attn_ok)
 
@@ -1435,6 +1479,23 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 raise ValueError(f"generate({'session=' if session is not None else 'return_session=True'}): {why}; a "
                                  "continued call needs the per-sample-position decode kernels, which take bf16 / fp16 inside "
                                  "ops.decode_attn_ok")
+        ad_idx = None             # adapter_names: per sample its adapter's index in the bank, -1 for "__base__"
+        if bank is not None:
+            what = "generate(adapter_names=)"
+            names = list(adapter_names)
+            if len(names) != B:
+                raise ValueError(f"{what}: {len(names)} names for {B} samples (one per sample, '__base__' for none)")
+            ad_idx = bank.indices(names)          # (ValueError for an unknown name)
+            why = _attn_refusal(dtype, hd, Tmax)
+            if dtype not in _16BIT:
+                why = f"fp32 parameters ({dtype}): the adapter kernels of a decode step take bf16 / fp16"
+            elif any(w is None for lyr in layers for w in lyr.fused_weights()):
+                why = ("unfused q/k/v or gate/up storage (the adapted decode step is the five-launch one on the fused "
+                       "q|k|v and gate|up weights: fuse_projections())")
+            elif B > 32:
+                why = f"{B} rows: an adapted decode step takes at most 32"
+            if why is not None:
+                raise ValueError(f"{what}: {why}")
         if ragged is not None and use_cache:
             why = _attn_refusal(dtype, hd, Tmax)
             if why is not None:
@@ -1613,11 +1674,22 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 w8.append((ql(ws.wqkv, own.wqkv), ql(ws.wo, own.wo), ql(ws.wgu, own.wgu), ql(ws.wd, own.wd)))
             w8_head = q8(self.lm_head.weight, self.lm_head.weight)
 
+        adapt = None              # adapter_names: adapt(layer, copies) -> what travels in llama_layer_cached's w8
+        if ad_idx is not None:
+            ad_dev = torch.tensor(ad_idx, dtype=torch.int32, device=dev)
+            ad_runs, ad_s, ad_groups = bank.runs(ad_idx), bank.scalings(), bank.stacks()
+
+            def adapt(i, copies):
+                return eng.Adapters(ad_dev, ad_runs, ad_s, *ad_groups[i], copies)
+
         def run(x2, Sn, t0, pos=None, t_dev=None, beam=None, spec=None, chunk=None):
             if pos is None:
                 pos = (torch.arange(t0, t0 + Sn, dtype=torch.int32, device=dev)).repeat(B)
             for i, lyr in enumerate(layers):
                 ws = merged.get(lyr, stored[i])
+                w8_i = w8[i] if w8 is not None and t_dev is not None else None
+                if adapt is not None:
+                    w8_i = adapt(i, w8_i)
                 if K > 1 and beam is None:        # the prefill of a beam cache: B rows into slot 0 of every sample
                     cache_i, tmax_i = kvc[i].view(B, K * Tmax, 2 * D), K * Tmax
                 elif N > 1:                       # parallel samples: the prefill writes the prompt cache, a step reads both
@@ -1628,7 +1700,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                     x2, B, Sn, t0, cache_i, tmax_i, pos, cos, sin, lyr.self_attn.num_heads,
                     lyr.input_layernorm.variance_epsilon, ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd,
                     lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, t_dev=t_dev,
-                    w8=w8[i] if w8 is not None and t_dev is not None else None,
+                    w8=w8_i,
                     kv8=kvs[i] if kvs is not None else None, ragged=ragged if chunk is None else chunk, beam=beam,
                     spec=spec)
             return x2
@@ -1672,7 +1744,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             return hand_over(res) if sess else res
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch or of
         # parallel samples
-        dyn = ragged is not None or N > 1         # (parallel samples take the padded batch's route: a device position)
+        # (parallel samples and adapters take the padded batch's route: a device position)
+        dyn = ragged is not None or N > 1 or adapt is not None
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if dyn else None
         done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
         for t in range(max_new_tokens):
@@ -1890,6 +1963,9 @@ class MM_LLMs(PreTrainedModel):
             # parallel samples on: num_samples rows per prompt, the towers and the alignment above run once per prompt;
             # off: exactly the call without it
             par = dict(num_samples=PARALLEL_SAMPLES[0]) if PARALLEL_SAMPLES[0] != 1 else {}
+            # adapters set: one name per sample out of the LLM's bank; unset: exactly the call without them
+            if ADAPTERS[0] is not None:
+                par["adapter_names"] = ADAPTERS[0]
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
@@ -2016,6 +2092,19 @@ class MM_LLMs(PreTrainedModel):
         call (beams, parallel samples, prompt lookup, guidance, cache format, dtype) is validated by generate().
         Process-wide switch, like set_generate_mask."""
         SESSION[0] = bool(on)
+
+    @staticmethod
+    def set_adapters(names=None):
+        """Mixed-adapter LoRA for `inputs["inference"] = True` (LlamaForCausalLM.generate's adapter_names): off (None) by
+        default.  names: one adapter name per sample out of the LLM's lora.AdapterBank (`AdapterBank(model.llm)`),
+        "__base__" for none.  Only the form is validated here (a list / tuple of str); the names, their count and what the
+        call composes with are validated by generate().  No arguments: back to off.  Process-wide switch, like
+        set_parallel_samples."""
+        if names is not None:
+            if isinstance(names, str) or not isinstance(names, (list, tuple)) or not all(isinstance(n, str) for n in names):
+                raise ValueError(f"set_adapters: names must be None or a list of adapter names (str), got {names!r}")
+            names = list(names)
+        ADAPTERS[0] = names
 
     @staticmethod
     def set_parallel_samples(num_samples=1):

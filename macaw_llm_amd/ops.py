@@ -1568,3 +1568,42 @@ def lora_merge_(W, A, B, s):
     _L.check(_L.load().mk_lora_merge(_p(W), _rowmajor(W), N, K, _p(A), _p(B), r, float(s), _p(ws), ws.numel(), dt(W),
                                      _st()), "mk_lora_merge")
     return W
+
+
+# csrc/lora_bgmv.hip: mixed-adapter LoRA of a decode step.  Row m of the batch uses adapter idx[m] of the bank's
+# stacks A [n, G r, K] / B [n, G N, r] / s [n]; an idx outside [0, n) is a base row (zero row of U, Y untouched).
+def lora_bgmv_ok(x, A, prologue=0):
+    """mk_lora_bgmv_shrink / _expand's domain on the token side: 16-bit rows, M <= 32, 16-byte rows of K <= 30712"""
+    K = A.shape[2]
+    return (x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 2 and x.shape[0] <= 32 and K % 8 == 0 and
+            K <= 30712 and x.shape[1] == (2 * K if prologue == 2 else K) and x.stride(1) == 1 and x.stride(0) % 8 == 0 and
+            x.data_ptr() % 16 == 0)
+
+
+def lora_bgmv_shrink(x, A, idx, G, prologue=0, norm_w=None, eps=0.0, out=None):
+    """U[m] = rnd16(prologue(x)[m] A[idx[m]]^T) [M, G r] (out: a [M, G r] view, pitched rows allowed); prologue as
+    decode_linear (1 = RMSNorm(x; norm_w, eps), 2 = SwiGLU of x = [gate | up] [M, 2 K]) with the same rounding points"""
+    M = x.shape[0]
+    n, GR, K = A.shape
+    if GR % G or not A.is_contiguous() or idx.dtype != torch.int32 or idx.numel() != M or not idx.is_contiguous():
+        raise MacawHipError(f"lora_bgmv_shrink: stack {tuple(A.shape)} for G = {G}, idx {idx.dtype} {tuple(idx.shape)}")
+    if out is None:
+        out = torch.empty((M, GR), dtype=x.dtype, device=x.device)
+    _L.check(_L.load().mk_lora_bgmv_shrink(_p(x), _rowmajor(x), M, K, _p(A), n, G, GR // G, _p(idx), prologue,
+                                           _p(norm_w), eps, _p(out), _rowmajor(out), dt(x), _st()), "mk_lora_bgmv_shrink")
+    return out
+
+
+def lora_bgmv_expand_(U, B, s, idx, Y, G):
+    """Y[m, :G N] = rnd16(Y[m, :G N] + s[idx[m]] U[m] (x) B[idx[m]]) in place, module i of the group on columns
+    [i N, (i + 1) N) with its r columns of U; Y [M, >= G N] (pitched rows allowed)"""
+    M = U.shape[0]
+    n, GN, r = B.shape
+    if (GN % G or U.shape[1] != G * r or not B.is_contiguous() or s.dtype != torch.float32 or s.numel() != n or
+            not s.is_contiguous() or idx.dtype != torch.int32 or idx.numel() != M or not idx.is_contiguous() or
+            Y.shape[0] != M or Y.shape[1] < GN):
+        raise MacawHipError(f"lora_bgmv_expand_: U {tuple(U.shape)}, stack {tuple(B.shape)} for G = {G}, s {s.dtype} "
+                            f"{tuple(s.shape)}, idx {idx.dtype} {tuple(idx.shape)}, Y {tuple(Y.shape)}")
+    _L.check(_L.load().mk_lora_bgmv_expand(_p(U), _rowmajor(U), M, G, r, _p(B), _p(s), n, _p(idx), _p(Y), _rowmajor(Y),
+                                           GN // G, dt(U), _st()), "mk_lora_bgmv_expand")
+    return Y

@@ -77,6 +77,14 @@ with torch.no_grad():
 # way, one call on the concatenated history [turn 1's prompt | its 64 tokens | turn 2's prompt].  Time to the first token of
 # turn 2 (the call with max_new_tokens=1) and ms per token ((72 - 8 tokens) / 64), each with its run-to-run spread; then what a
 # follow-up turn through MM_LLMs skips on top: the towers and the alignment (prepare_inputs_for_generation), timed alone
+#        bench_generate.py --adapters-ab [--reps R] [B ...]: mixed-adapter LoRA decoding (default B = 1, 8, 32), r = 16 on all seven
+# projections.  Four greedy arms alternated in this process on this model: "base" = no adapter; "merged" = today's single-adapter
+# call, a live adapter that generate() merges into temporary copies of the weights; "names x1" = adapter_names with one adapter
+# for every row; "names x4" = adapter_names cycling over four distinct adapters (and the same rows through the mk_lora_bgmv
+# kernels: 8 more launches per layer and token, 256 for the model).  ms per token of every run ((72 - 8 tokens) / 64), the
+# medians and each arm's run-to-run spread, and the time to the first token (the call with max_new_tokens=1: for "merged" it
+# holds the merge, for the names arms the prefill's per-run adapter launches)
+ADAPTERS = "--adapters-ab" in sys.argv
 SESSION = "--session-ab" in sys.argv
 NSAMPLE = "--nsample-ab" in sys.argv
 STOP = "--stop-ab" in sys.argv
@@ -94,7 +102,70 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if ADAPTERS:
+    from macaw_llm_amd import lora
+    llm = model.llm
+    targets = ["q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj"]
+    lora.get_peft_model(llm, lora.LoraConfig(r=16, lora_alpha=32, target_modules=targets))
+    with torch.no_grad():
+        for n, q in llm.named_parameters():
+            if ".lora_B." in n:
+                q.copy_(torch.randn_like(q.float()) * 0.02)
+    live = llm._lora
+    bank = lora.AdapterBank(llm)
+    sd0 = lora.lora_state_dict(llm)
+    bank.add("a0", state_dict=sd0, config=live.config)
+    for i in (1, 2, 3):                             # three more adapters of the same form with other weights
+        g = torch.Generator(device=dev).manual_seed(10 + i)
+        sd = {k: (torch.randn(v.shape, generator=g, device=dev) * (0.02 if ".lora_B." in k else 0.01)).to(v.dtype) for k, v in sd0.items()}
+        bank.add(f"a{i}", state_dict=sd, config=live.config)
+    bank.stacks()                                   # built once, outside the timed calls
+    ARMS = ("base", "merged", "names x1", "names x4")
+
+    def call(arm, emb, new):
+        B = emb.shape[0]
+        # the live adapter is what "merged" measures; the other arms run on the stored weights, so it is set aside for them
+        llm._lora = live if arm == "merged" else None
+        try:
+            names = None if arm in ("base", "merged") else [f"a{b % 4}" if arm == "names x4" else "a0" for b in range(B)]
+            return llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, adapter_names=names)
+        finally:
+            llm._lora = live
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, PROMPT, modalities=("images", "audios"), seed=2, device=dev)
+        ms, ttft = {a: [] for a in ARMS}, {a: [] for a in ARMS}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            S0 = emb.shape[1]
+            for arm in ARMS:                        # untimed: each arm's first call at this size
+                assert call(arm, emb, 4).shape == (B, 4)
+            agree = int((call("merged", emb, 8) == call("names x1", emb, 8)).sum())
+            print(f"B={B:2d} S0={S0}: merged and names x1 (the same adapter) agree in {agree} of {B * 8} of their first 8 ids "
+                  "(one rounding of W + s B A against two roundings of the 16-bit adapter)", flush=True)
+            for rep in range(REPS):
+                for arm in ARMS:
+                    t = {}
+                    for new in (1, 8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        ids = call(arm, emb, new)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                        assert ids.shape == (B, new)
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    ttft[arm].append(t[1] * 1e3)
+                    print(f"B={B:2d} S0={S0} rep {rep} {arm:9s}: decode {ms[arm][-1]:7.3f} ms/token, first token {ttft[arm][-1]:8.2f} ms", flush=True)
+        med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+        spr = lambda v: max(v) - min(v)  # noqa: E731
+        for a in ARMS:
+            print(f"B={B:2d} S0={S0}: {a:9s} {med(ms[a]):7.3f} ms/token (run-to-run spread {spr(ms[a]) * 1e3:6.1f} us = "
+                  f"{spr(ms[a]) / med(ms[a]) * 100:4.1f} %), first token {med(ttft[a]):8.2f} ms (spread {spr(ttft[a]):6.2f} ms)", flush=True)
+        for a in ("names x1", "names x4"):
+            d = med(ms[a]) - med(ms["merged"])
+            print(f"B={B:2d} S0={S0}: {a} - merged = {d * 1e3:+8.1f} us per token ({d / med(ms['merged']) * 100:+6.2f} %, "
+                  f"{d * 1e3 / (8 * llm.config.num_hidden_layers):5.2f} us per extra launch): "
+                  f"{'inside' if abs(d) <= max(spr(ms[a]), spr(ms['merged'])) else 'OUTSIDE'} the larger of the two spreads; "
+                  f"first token {med(ttft[a]) - med(ttft['merged']):+8.2f} ms", flush=True)
+    sys.exit(0)
 if SESSION:
     from macaw_llm_amd import ops
     E = model.llm.model.embed_tokens.weight
