@@ -99,7 +99,9 @@ typedef struct mk_gemm_desc {
 int mk_gemm(const mk_gemm_desc* d, void* stream);
 /* Tuning / A-B hook: force the bf16 kernel configuration of the following mk_gemm calls
  * (11 = 256x256 v7 with eight waves, 15 = 256x256 v9: four waves, one per SIMD, hand-placed inline-asm K loop (whole tiles
- * only), 14 = its hipcc-scheduled predecessor v8 (experiment builds only), 5 = 128x128 v2, 7 = v2 BK32, 0 = generic;
+ * only), 21 = v9's 288x256 tile: both operands K-major, M % 288 == 0, N % 256 == 0, K % 64 == 0, K >= 128, alpha
+ * (+ R) only, C / R rows 8-byte aligned -- the same bits as 11 and 15; anywhere else it runs what 11 would,
+ * 14 = its hipcc-scheduled predecessor v8 (experiment builds only), 5 = 128x128 v2, 7 = v2 BK32, 0 = generic;
  * -1 = automatic).  A forced configuration is still replaced where it is not legal for the problem.
  * Replaces cuBLAS behind nn.Linear of /root/reference/modeling.py:134-140,159-162,597. */
 int mk_gemm_set_cfg(int cfg);

@@ -287,7 +287,7 @@ extern "C" int mk_gemm_has_cfg(int cfg) {
 #ifdef MK_WITH_V8
   if (cfg == 14) return 1;
 #endif
-  return cfg == 0 || cfg == 5 || cfg == 7 || cfg == 11 || cfg == 15;
+  return cfg == 0 || cfg == 5 || cfg == 7 || cfg == 11 || cfg == 15 || cfg == 21;
 }
 namespace { int g_plan_cus = 0; }
 extern "C" int mk_gemm_set_cus(int n) { const int prev = g_plan_cus; g_plan_cus = n > 0 ? n : 0; return prev; }
@@ -300,6 +300,7 @@ int launch_v8(const GemmArgs& g, bool a_red, bool b_red, dim3 grid, hipStream_t 
 int launch_v9(const GemmArgs& g, bool a_red, bool b_red, dim3 grid, hipStream_t st, bool f16);            // gemm_v9.hip
 int v9_mfma16_layouts();                                                                                        // gemm_v9.hip
 int launch_grp(const GrpArgs& g, bool has_main, int n_wg, hipStream_t st, bool f16);                            // gemm_v9.hip
+int launch_tile288(const GemmArgs& g, dim3 grid, hipStream_t st, bool f16);                                     // gemm_v9.hip
 }
 
 // y[M <= 16, N] = prologue(x) W^T (+ residual): the linear layers of one decode position per sample
@@ -330,6 +331,12 @@ extern "C" int mk_decode_linear(const void* x, int64_t ldx, const void* W, int64
   return mk_check_launch();
 }
 namespace {
+// the 288 x 256 tile's price in pick_cfg: microseconds per K-tile and per launch or tile.  Measured with scripts/gemm_bench.cpp
+// on cold operands (scripts/gemm_shapes_tile288.txt, profiles/fwd_tile288_cfg3.txt section 1): 4608 x 4096 x K = one round of
+// 256 tiles takes 38.5 / 66.5 / 130.7 / 312.2 us at 16 / 32 / 64 / 172 K-tiles (the line through the ends: 1.75 us per K-tile
+// + 10.4 us; the middle lies 6 % above it), 4608 x 12288 x 4096 = three walked rounds 343 us.
+constexpr double MK_T288_KTILE_US = 1.75, MK_T288_FIXED_US = 10.4;
+constexpr int MK_GEMM_TILE288_DEFAULT = 1;
 // Default kernel choice: a small cost model fitted to scripts/gemm_bench.cpp measurements on
 // MI355X (microseconds; round 4 re-fit on COLD operands -- as inside a training step -- from
 // profiles/r04_gemm_enc_cold.csv, r04_gemm_kslope.csv).  v7: one 256x256 tile per CU and round,
@@ -400,8 +407,32 @@ int pick_cfg(const mk_gemm_desc* d, int nbatch, bool v7_ok, int n_cus) {
   // q|k|v +2.5 %, gate|up +0.7 %, down +3.3 %, but o_proj (288 tiles, K = 4096) -5 %: v9 runs a tail as a SECOND launch
   // behind its whole rounds, which one short round of short tiles does not amortise
   const bool nt16 = m16 && layout == 0 && !(R > 0 && full < 2 && nk < 128);
-  if (v9_legal && (v9_mode == 2 || (v9_mode == 1 && (layout == 3 || layout == 1 || nk >= 256 || nt16)))) return 15;
-  return 11;
+  const bool v9 = v9_legal && (v9_mode == 2 || (v9_mode == 1 && (layout == 3 || layout == 1 || nk >= 256 || nt16)));
+  // The 288 x 256 tile (configuration 21, gemm_bf16_tile288_kernel): forward layout, whole tiles, alpha (+ residual).  A
+  // partial last round of 256 x 256 tiles costs a v7 sub-tile launch behind the whole rounds (`sub7` per sub-round, above);
+  // where M is a multiple of 288 the taller tile may need fewer rounds (M = 4608 x N = 4096: 256 tiles instead of 288).
+  // Priced with its own constants (MK_T288_*, above): whole rounds are walked, so the fixed cost is paid once; a partial
+  // last round is priced as gemm_v7's is above (a partly filled chip runs its K-tiles faster).  v9's whole rounds at 1.38 us
+  // per K-tile + 9.4 us (profiles/r06_gemm_v9_mfma16.txt).  Measured in the harness, 15 -> 21: 4608 x 4096 x 4096 137 -> 131 us,
+  // 4608 x 4096 x 11008 332 -> 312, 4608 x 12288 x 4096 378 -> 343, but gate|up 4608 x 22016 x 4096 (5.375 rounds) 633 -> 647:
+  // the model keeps that one on 15.  MK_GEMM_TILE288: 0 = never, 1 = this policy.
+  static const int t288_mode = [] { const char* e = getenv("MK_GEMM_TILE288"); return e ? atoi(e) : MK_GEMM_TILE288_DEFAULT; }();
+  if (t288_mode == 1 && v9_mode >= 1 && m16 && layout == 0 && d->dtype != MK_F32 && d->dtype != MK_FP8 && d->M % 288 == 0 &&
+      d->N % 256 == 0 && d->K % 64 == 0 && !d->scale_a && !d->scale_b && d->bias_mode == 0 && d->act == 0 && !d->accumulate) {
+    const long T288 = (long)(d->M / 288) * (d->N / 256);
+    const long full288 = T288 / n_cus, R288 = T288 % n_cus;
+    const double t288 = R288 == 0 ? full288 * nk * MK_T288_KTILE_US + MK_T288_FIXED_US
+                                  : full288 * (nk * MK_T288_KTILE_US + MK_T288_FIXED_US) +
+                                        nk * MK_T288_KTILE_US * (0.55 + 0.45 * R288 / n_cus) + MK_T288_FIXED_US;
+    double t_now = t7;
+    if (v9) {
+      t_now = full * (nk * 1.38 + 9.4);
+      if (R > 0) t_now += (4 * R <= 2 * n_cus) ? (double)mk_cdiv((int)(4 * R), n_cus) * sub7
+                                                : nk * a7 * (0.55 + 0.45 * R / n_cus) + 11.5;
+    }
+    if (T288 >= n_cus && t288 < 0.97 * t_now) return 21;
+  }
+  return v9 ? 15 : 11;
 }
 }  // namespace
 
@@ -509,6 +540,18 @@ extern "C" int mk_gemm(const mk_gemm_desc* d_in, void* stream) {
 #ifndef MK_WITH_V8
     if (cfg == 14) cfg = 11;              // gemm_v8 is not part of the shipped library (build.py MK_EXPERIMENTS)
 #endif
+    // the 288 x 256 tile (gemm_bf16_tile288_kernel): whole tiles, both operands K-major, alpha (+ residual) only, 8-byte
+    // aligned C / R rows; anything else goes where configuration 11 would
+    if (cfg == 21) {
+      const auto al8 = [&](const void* p, long ld, long s1, long s2) {
+        return (reinterpret_cast<uintptr_t>(p) & 7) == 0 && ld % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0;
+      };
+      const bool ok = !fp8 && v2_ok && mkg::v9_mfma16_layouts() == 15 && d->M % 288 == 0 && d->N % 256 == 0 && d->K % 64 == 0 &&
+                      d->K >= 128 && !d->a_red_major && !d->b_red_major && d->bias_mode == 0 && d->act == 0 && !d->accumulate &&
+                      !d->scale_a && !d->scale_b && fits(false, d->lda, 288) && fits(false, d->ldb, 256) &&
+                      al8(d->C, d->ldc, d->sC1, d->sC2) && (!d->R || al8(d->R, d->ldr, d->sR1, d->sR2));
+      if (!ok) cfg = 11;
+    }
     if ((cfg == 11 || cfg == 14 || cfg == 15) && !v7_ok) cfg = 5;
     if ((cfg == 14 || cfg == 15) && fp8) cfg = 11;       // (v8 / v9 have no e4m3 instantiation)
     // v9 (hand-placed K loop, gemm_v9.hip) takes whole 256 x 256 x 64 tiles only
@@ -517,7 +560,7 @@ extern "C" int mk_gemm(const mk_gemm_desc* d_in, void* stream) {
     if (cfg == 15 && ((mkg::v9_mfma16_layouts() >> ((d->a_red_major ? 2 : 0) + (d->b_red_major ? 1 : 0))) & 1) &&
         (d->bias_mode != 0 || d->act != 0 || d->accumulate || d->scale_a || d->scale_b))
       cfg = 11;
-    if (cfg != 0 && cfg != 5 && cfg != 7 && cfg != 11 && cfg != 14 && cfg != 15) cfg = 5;
+    if (cfg != 0 && cfg != 5 && cfg != 7 && cfg != 11 && cfg != 14 && cfg != 15 && cfg != 21) cfg = 5;
     if (cfg >= 5 && !v2_ok) cfg = 0;
     if (fp8 && cfg != 5 && cfg != 11) return MK_ERR_UNSUPPORTED;
     // Measured (profiles/): with BOTH operands reduction-major (dW = dy^T x) the global rows are
@@ -529,8 +572,9 @@ extern "C" int mk_gemm(const mk_gemm_desc* d_in, void* stream) {
     const bool v8 = cfg == 14;            // 256 x 256 tile, one wave per SIMD (gemm_v8.hip)
     const bool v9 = cfg == 15;            // the same with the K loop placed by hand (gemm_v9.hip)
     const bool t256 = cfg == 11 || v8 || v9;
-    const int bm = t256 ? 256 : 128;
-    const int bn = t256 ? 256 : BN;
+    const bool t288 = cfg == 21;          // 288 x 256 tile on the same pieces (gemm_v9.hip)
+    const int bm = t288 ? 288 : t256 ? 256 : 128;
+    const int bn = t256 || t288 ? 256 : BN;
     g.tiles_m = mk_cdiv(d->M, bm);
     g.tiles_n = mk_cdiv(d->N, bn);
     g.a_vec = aligned16(d->A) && (d->lda % 8 == 0) && (d->sA1 % 8 == 0) && (d->sA2 % 8 == 0);
@@ -606,6 +650,15 @@ extern "C" int mk_gemm(const mk_gemm_desc* d_in, void* stream) {
         grid.x = n_cus + (grid.x - g.dp_tiles);
         g.walkers = n_cus;
       }
+    }
+    if (t288) {
+      // whole tiles only: one workgroup per tile, or -- whole rounds of the planned CUs -- one WALKING workgroup per CU
+      static const bool no_walk288 = getenv("MK_GEMM_NO_WALK") != nullptr;
+      dim3 g288(g.dp_tiles, 1, nbatch);
+      if (!no_walk288 && nbatch == 1 && n_cus % 8 == 0 && g.dp_tiles > n_cus && g.dp_tiles % n_cus == 0) g288.x = n_cus;
+      const int rc = mkg::launch_tile288(g, g288, st, f16);
+      mkp::end(prof, st);
+      return rc;
     }
 #ifdef MK_WITH_V8
     if (v8) {

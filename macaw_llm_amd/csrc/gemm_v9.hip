@@ -23,10 +23,15 @@
 //
 // Whole tiles only (M % 256 == N % 256 == 0, K % 64 == 0): the launcher in gemm.hip sends everything else to v7.
 //
+// The 288 x 256 x 64 tile (gemm_bf16_tile288_kernel, configuration 21): the same kernel pieces at a tile height that divides
+// M = 4608 into whole rounds of tiles, for the forward layout only; its loop is gemm_v9_loop288.inc (scripts/gen_v9_loop.py
+// --tile288: 144 MFMAs per K-tile and wave, two LDS slots per operand).
+//
 // Replaces the nn.Linear matmuls of /root/reference/modeling.py:134-140,159-162,597 and their gradients (same
 // contract as gemm_v7.hip).
 #include "gemm_common.h"
 #include "gemm_v9_loop.inc"
+#include "gemm_v9_loop288.inc"
 
 #define MK_E16_T bf16
 #define MK_E16_NS e_bf16
@@ -40,9 +45,11 @@
 #define MK_V9_SFX "f16"
 #define gemm_bf16_v9_kernel gemm_f16_v9_kernel
 #define gemm_bf16_grp_kernel gemm_f16_grp_kernel
+#define gemm_bf16_tile288_kernel gemm_f16_tile288_kernel
 #include "gemm_v9_impl.inc"
 #undef gemm_bf16_v9_kernel
 #undef gemm_bf16_grp_kernel
+#undef gemm_bf16_tile288_kernel
 #undef MK_E16_T
 #undef MK_E16_NS
 #undef MK_V9_SFX
@@ -68,6 +75,10 @@ int launch_v9(const GemmArgs& g, bool a_red, bool b_red, dim3 grid, hipStream_t 
   if (!a_red && b_red) return e_bf16::launch_v9<false, true>(g, grid, st);
   if (a_red && !b_red) return e_bf16::launch_v9<true, false>(g, grid, st);
   return e_bf16::launch_v9<true, true>(g, grid, st);
+}
+// the 288 x 256 tile (both operands K-major; configuration 21 in gemm.hip)
+int launch_tile288(const GemmArgs& g, dim3 grid, hipStream_t st, bool f16) {
+  return f16 ? e_f16::launch_tile288(g, grid, st) : e_bf16::launch_tile288(g, grid, st);
 }
 // the grouped launch (mk_gemm_grouped in gemm.hip): n_wg persistent workgroups over g's work lists
 int launch_grp(const GrpArgs& g, bool has_main, int n_wg, hipStream_t st, bool f16) {

@@ -12,6 +12,10 @@ constexpr int HALF_BYTES = 128 * BK7 * 2;        // 16 KiB: 128 rows x 64 k
 constexpr int A_SLOT = 2 * HALF_BYTES;           // 32 KiB
 constexpr int B_BASE9 = 3 * A_SLOT;              // A: 3 slots, then B: 2 slots
 constexpr int LDS9 = 5 * A_SLOT;                 // 163,840 B
+// the 288 x 256 x 64 tile (gemm_bf16_tile288_kernel below; the slots are the generator's: gemm_v9_loop288.inc): A two slots
+// of 288 rows, then B two slots
+constexpr int BM288 = 288, A_SLOT288 = V9_A_SLOT288, B_BASE288 = V9_B_BASE288, LDS288 = V9_LDS288;
+static_assert(A_SLOT288 == BM288 * BK7 * 2 && LDS288 == B_BASE288 + 2 * A_SLOT && LDS288 <= LDS9, "gemm_v9_loop288.inc");
 
 #include "gemm_lds_image.inc"
 
@@ -19,14 +23,18 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Whole tiles only (M % 256 == N % 256 == K % 64 == 0, K >= 128: the launcher checks): the asm derives every LDS-DMA
 // voffset from piece 0's by adding strides, which is the C++ formula without its edge clamp.
-// everything of one tile that the LDS-DMA requests and the asm block need
+// everything of one tile that the LDS-DMA requests and the asm block need.  A wave owns the 1-KiB pieces w + 4 i of an
+// operand's tile image: i < BM / 32 of A (8 rows of a K-major image each; a half-tile of 128 rows is 16 pieces), i < 8 of B.
+// (ONE struct for both tile heights, the 256-row tile leaves voA[8] unused: as a class template it would be instantiated in
+// the host pass as well, where a member of the buffer resource type is ill-formed -- hipcc then drops every kernel that
+// uses it from the host object without a diagnostic.)
 struct V9Tile {
   int m0, n0;
   e16* C;
   const e16* Rp;
   __amdgpu_buffer_rsrc_t rsA, rsB;
   u32x4 dA, dB;
-  int voA[2][4], voB[2][4];
+  int voA[BM288 / 32], voB[8];
 };
 
 #ifndef V9_MFMA16
@@ -68,14 +76,15 @@ MK_DEV int v9_read_offset16(int l) {
 // panels of the tile at (m0, n0) (the compiler's form and four scalar words each for the asm block) and the lane's LDS-DMA
 // voffsets.  P: the problem (GemmArgs or GrpProb: M, N, K, lda, ldb); A, B: its operands.  CLAMP: a K-major panel's record
 // ends at the matrix edge when fewer than 256 rows are left (a launch of whole tiles needs no clamp).
-template <bool A_RED, bool B_RED, bool CLAMP, typename P>
+template <bool A_RED, bool B_RED, bool CLAMP, int BM = BM9, typename P>
 MK_DEV void v9_operand_setup(const P& g, const e16* A, const e16* B, int m0, int n0, int w, int l, V9Tile& t) {
+  static_assert(BM == BM9 || !A_RED, "a taller tile exists for a K-major A only (its image is one run of 8-row pieces)");
   constexpr bool M16 = ((V9_MFMA16 >> (2 * (A_RED ? 1 : 0) + (B_RED ? 1 : 0))) & 1) != 0;
   t.m0 = m0; t.n0 = n0;
   const e16* abase = uniform_ptr(A_RED ? A + m0 : A + (long)m0 * g.lda);
   const e16* bbase = uniform_ptr(B_RED ? B + n0 : B + (long)n0 * g.ldb);
   const long a_bytes = A_RED ? ((long)(g.K - 1) * g.lda + ((g.M - m0 + 1) & ~1)) * 2
-                             : ((long)((CLAMP ? min(g.M - m0, BM9) : BM9) - 1) * g.lda + ((g.K + 1) & ~1)) * 2;
+                             : ((long)((CLAMP ? min(g.M - m0, BM) : BM) - 1) * g.lda + ((g.K + 1) & ~1)) * 2;
   const long b_bytes = B_RED ? ((long)(g.K - 1) * g.ldb + ((g.N - n0 + 1) & ~1)) * 2
                              : ((long)((CLAMP ? min(g.N - n0, BN9) : BN9) - 1) * g.ldb + ((g.K + 1) & ~1)) * 2;
   const int a_rec = __builtin_amdgcn_readfirstlane((int)min(a_bytes, 0x7fffffffL));
@@ -92,13 +101,16 @@ MK_DEV void v9_operand_setup(const P& g, const e16* A, const e16* B, int m0, int
   t.dB[1] = __builtin_amdgcn_readfirstlane((uint32_t)(pb >> 32) & 0xffffu);
   t.dB[2] = (uint32_t)b_rec;
   t.dB[3] = 0x00020000u;
+  // piece w + 4 i = piece w + 4 (i & 3) of half-tile i >> 2
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      t.voA[h][i] = v9_voffset<A_RED, M16>(m0, g.M, g.lda, h, w + 4 * i, l);
-      t.voB[h][i] = v9_voffset<B_RED, M16>(n0, g.N, g.ldb, h, w + 4 * i, l);
+      t.voA[4 * h + i] = v9_voffset<A_RED, M16>(m0, g.M, g.lda, h, w + 4 * i, l);
+      t.voB[4 * h + i] = v9_voffset<B_RED, M16>(n0, g.N, g.ldb, h, w + 4 * i, l);
     }
+#pragma unroll
+  for (int i = 8; i < BM / 32; ++i) t.voA[i] = v9_voffset<A_RED, M16>(m0, g.M, g.lda, i >> 2, w + 4 * (i & 3), l);
 }
 
 // element (z1, z2) of a batched operand.  (A function on purpose: as a call it stays beside the tile index until the
@@ -109,7 +121,7 @@ MK_DEV T* v9_batch_elem(T* p, long z1, long s1, long z2, long s2) {
   return p + z1 * s1 + z2 * s2;
 }
 // mk_gemm's tile: the XCD-aware tile order, the batch element of blockIdx.z, the residual
-template <bool A_RED, bool B_RED>
+template <bool A_RED, bool B_RED, int BM = BM9>
 MK_DEV void v9_tile_setup(const GemmArgs& g, int tile, int w, int l, V9Tile& t) {
   int tm, tn;
   tile_from_index(xcd_remap(tile, g.dp_tiles), g.tiles_m, g.tiles_n, tm, tn, 8);
@@ -118,30 +130,32 @@ MK_DEV void v9_tile_setup(const GemmArgs& g, int tile, int w, int l, V9Tile& t) 
   const e16* B = v9_batch_elem(reinterpret_cast<const e16*>(g.B), z1, g.sB1, z2, g.sB2);
   t.C = v9_batch_elem(reinterpret_cast<e16*>(g.C), z1, g.sC1, z2, g.sC2);
   t.Rp = g.R ? v9_batch_elem(reinterpret_cast<const e16*>(g.R), z1, g.sR1, z2, g.sR2) : nullptr;
-  v9_operand_setup<A_RED, B_RED, true>(g, A, B, tm * BM9, tn * BN9, w, l, t);
+  v9_operand_setup<A_RED, B_RED, true, BM>(g, A, B, tm * BM, tn * BN9, w, l, t);
 }
 
-// the first LDS-DMA requests of a tile (as gemm_v8): tile 0 (A, B piece by piece), A(1), half 0 of B(1) -- 28 pieces
-// per wave; the wait for tile 0 is the asm block's
+// the first LDS-DMA requests of a tile (as gemm_v8).  256 rows: tile 0 (A, B piece by piece), A(1), half 0 of B(1) -- 28
+// pieces per wave.  288 rows (two slots per operand): tile 0, A(1) -- 26 pieces.  The wait for tile 0 is the asm block's
+template <int BM = BM9>
 MK_DEV void v9_tile_request(const V9Tile& t, char* smem, int w, int stepA, int stepB) {
-#define V9_DMA_A(DST, H, I, KO)                                                                   \
+  constexpr int NPA = BM / 32, A_SLOT_ = BM * BK7 * 2, B_BASE_ = BM == BM9 ? B_BASE9 : B_BASE288;
+#define V9_DMA_A(DST, I, KO)                                                                      \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                       \
-      t.rsA, (__attribute__((address_space(3))) void*)(smem + (DST) + (H) * HALF_BYTES + (w + 4 * (I)) * 1024), \
-      16, t.voA[H][I], KO, 0, 0)
-#define V9_DMA_B(DST, H, I, KO)                                                                   \
+      t.rsA, (__attribute__((address_space(3))) void*)(smem + (DST) + ((I) >> 2) * HALF_BYTES + (w + 4 * ((I) & 3)) * 1024), \
+      16, t.voA[I], KO, 0, 0)
+#define V9_DMA_B(DST, I, KO)                                                                      \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                       \
-      t.rsB, (__attribute__((address_space(3))) void*)(smem + (DST) + (H) * HALF_BYTES + (w + 4 * (I)) * 1024), \
-      16, t.voB[H][I], KO, 0, 0)
+      t.rsB, (__attribute__((address_space(3))) void*)(smem + (DST) + ((I) >> 2) * HALF_BYTES + (w + 4 * ((I) & 3)) * 1024), \
+      16, t.voB[I], KO, 0, 0)
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
+  for (int i = 0; i < 8; ++i) { V9_DMA_A(0, i, 0); V9_DMA_B(B_BASE_, i, 0); }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { V9_DMA_A(0, h, i, 0); V9_DMA_B(B_BASE9, h, i, 0); }
+  for (int i = 8; i < NPA; ++i) V9_DMA_A(0, i, 0);
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
+  for (int i = 0; i < NPA; ++i) V9_DMA_A(A_SLOT_, i, stepA);
+  if constexpr (BM == BM9) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) V9_DMA_A(A_SLOT, h, i, stepA);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) V9_DMA_B(B_BASE9 + A_SLOT, 0, i, stepB);
+    for (int i = 0; i < 4; ++i) V9_DMA_B(B_BASE9 + A_SLOT, i, stepB);
+  }
 #undef V9_DMA_A
 #undef V9_DMA_B
 }
@@ -149,12 +163,16 @@ MK_DEV void v9_tile_request(const V9Tile& t, char* smem, int w, int stepA, int s
 // ---- shared by gemm_bf16_v9_kernel and gemm_bf16_grp_kernel (#undef'd at the end of this file).
 // The K loop (it names the kernel's locals t, adA, adB, iA, iB, stepA, stepB, nk, wv): ONE asm statement around a generated text (scripts/gen_v9_loop.py: register map, placement rule and the
 // slot / wait protocol there) with that text's clobber list.
-#define V9_ASM(TEXT, CLOBBERS)                                                                    \
+#define V9_ASM_IN                                                                                 \
+  [voA] "v"(t.voA[0]), [voB] "v"(t.voB[0]), [adA] "v"(adA), [adB] "v"(adB), [rsA] "s"(t.dA), [rsB] "s"(t.dB),       \
+      [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA), [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)
+#define V9_ASM(TEXT, CLOBBERS) asm volatile(TEXT : : V9_ASM_IN : CLOBBERS)
+// the 288-row tile's loop: its ninth fragment row accumulates in eight VGPR quadruples of the compiler's (c8_0 .. c8_7)
+#define V9_ASM288(TEXT, CLOBBERS)                                                                 \
   asm volatile(TEXT                                                                               \
-               :                                                                                  \
-               : [voA] "v"(t.voA[0][0]), [voB] "v"(t.voB[0][0]), [adA] "v"(adA), [adB] "v"(adB),   \
-                 [rsA] "s"(t.dA), [rsB] "s"(t.dB), [iA] "s"(iA), [iB] "s"(iB), [stA] "s"(stepA),   \
-                 [stB] "s"(stepB), [nk] "s"(nk), [wv] "s"(wv)                                      \
+               : [c0] "+v"(c8_0), [c1] "+v"(c8_1), [c2] "+v"(c8_2), [c3] "+v"(c8_3), [c4] "+v"(c8_4), [c5] "+v"(c8_5),  \
+                 [c6] "+v"(c8_6), [c7] "+v"(c8_7)                                                  \
+               : V9_ASM_IN                                                                        \
                : CLOBBERS)
 #if V9_MFMA16
 // Register epilogue of the 16 x 16 fragments: D[n = 4 (l >> 4) + e][m = l & 15] of fragment (i, j) -> a lane owns 4
@@ -174,6 +192,46 @@ typedef unsigned int v9_u32x2 __attribute__((ext_vector_type(2)));
     V9_ACC16_READ_##I##_##J(t_);                                                                  \
     e16x4 o_;                                                                                     \
     _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * (ALPHA));           \
+    V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
+  } while (0)
+#define V9_F16R(I, J, CROW, LDC, ALPHA)   /* + residual (requested for the whole tile up front: the kernel's rv_) */ \
+  do {                                                                                            \
+    float t_[4];                                                                                  \
+    V9_ACC16_READ_##I##_##J(t_);                                                                  \
+    e16x4 o_;                                                                                     \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * (ALPHA) + (float)rv_[I][J][e_]); \
+    V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
+  } while (0)
+// The same two with gemm_v7's arithmetic (gemm_common.h wave_epilogue16), rounding for rounding: the product with alpha is
+// rounded to fp32, then the residual is added and rounded to fp32, then the sum is rounded to 16 bits.  In the two forms
+// above hipcc contracts the first two steps into one fma and, for fp16, the product and the conversion into
+// v_fma_mixlo_f16 (one rounding instead of two): whenever alpha is no power of two they differ from v7 in the last bit of
+// about one output in 10^4.  The 288-row tile uses these (tests/test_gemm_tile288_gpu.py pins it to v7 bit for bit at such an
+// alpha); the 256-row kernels keep their code.  V9_FP32 holds a fragment's four values in fp32 registers between two steps;
+// it emits nothing.
+#define V9_FP32(X) asm("" : "+v"(X))
+#define V9_F16PS(I, J, CROW, LDC, ALPHA)                                                          \
+  do {                                                                                            \
+    float t_[4];                                                                                  \
+    V9_ACC16_READ_##I##_##J(t_);                                                                  \
+    f32x4 p_ = {t_[0], t_[1], t_[2], t_[3]};                                                      \
+    p_ *= (ALPHA);                                                                                \
+    V9_FP32(p_);                                                                                  \
+    e16x4 o_;                                                                                     \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)p_[e_];                        \
+    V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
+  } while (0)
+#define V9_F16RS(I, J, CROW, LDC, ALPHA)                                                          \
+  do {                                                                                            \
+    float t_[4];                                                                                  \
+    V9_ACC16_READ_##I##_##J(t_);                                                                  \
+    f32x4 p_ = {t_[0], t_[1], t_[2], t_[3]};                                                      \
+    p_ *= (ALPHA);                                                                                \
+    V9_FP32(p_);                                                                                  \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) p_[e_] += (float)rv_[I][J][e_];              \
+    V9_FP32(p_);                                                                                  \
+    e16x4 o_;                                                                                     \
+    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)p_[e_];                        \
     V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
   } while (0)
 // (a scheduling fence per fragment row: without it hipcc hoists all 256 accumulator reads and spills)
@@ -283,14 +341,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
       const int mrow = m0 + wm0 + (l & 15), ncol = n0 + wn0 + 4 * (l >> 4);
       e16* crow = C + (long)mrow * g.ldc + ncol;
       const e16* rrow = Rp ? Rp + (long)mrow * g.ldr + ncol : nullptr;
-#define V9_F16R(I, J, CROW, LDC, ALPHA)   /* + residual (requested for the whole tile up front: rv_) */ \
-  do {                                                                                            \
-    float t_[4];                                                                                  \
-    V9_ACC16_READ_##I##_##J(t_);                                                                  \
-    e16x4 o_;                                                                                     \
-    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) o_[e_] = (e16)(t_[e_] * (ALPHA) + (float)rv_[I][J][e_]); \
-    V9_ST8((CROW) + (long)(16 * (I)) * (LDC) + 16 * (J), o_);                                     \
-  } while (0)
       if (rrow == nullptr) {
         V9_EPI16(V9_F16P, crow, g.ldc, alpha);
       } else {
@@ -306,7 +356,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_v9_kernel(GemmArgs g) {
         __builtin_amdgcn_sched_barrier(0);
         V9_EPI16(V9_F16R, crow, g.ldc, alpha);
       }
-#undef V9_F16R
     } else
 #endif
     if (plain) {
@@ -515,6 +564,108 @@ int launch_grp(const GrpArgs& g, bool has_main, int n_wg, hipStream_t st) {
 }
 #endif  // V9_MFMA16 == 15
 
+#if V9_MFMA16 == 15
+// ---- the 288 x 256 x 64 tile: forward projections whose M is a multiple of 288 and not of 256 rounds of tiles (M = 4608 =
+// 16 x 288: o_proj / down_proj are exactly 256 tiles, q|k|v 768).  Both operands K-major, alpha (+ residual) only, whole
+// tiles only (M % 288 == N % 256 == K % 64 == 0, K >= 128: the launcher checks).  It is gemm_bf16_v9_kernel's protocol on the
+// shared pieces at BM = 288: v9_tile_setup / v9_operand_setup, v9_tile_request, the generated loop inside V9_ASM288
+// (gemm_v9_loop288.inc: 4 waves of 144 x 128 = 9 x 8 fragments, two LDS slots per operand) and V9_EPI16 plus a ninth
+// fragment row, whose accumulators are VGPRs (a[0:255] hold rows 0 .. 7 as on the 256 tile).  Every element sees the K order
+// and the MFMA of the 256 tile's loop, and the epilogue rounds as gemm_v7's does (V9_F16PS / V9_F16RS): the results are
+// configuration 11's bits (tests/test_gemm_tile288_gpu.py).
+#define V9_C8_READ(X, C) do { (X)[0] = (C)[0]; (X)[1] = (C)[1]; (X)[2] = (C)[2]; (X)[3] = (C)[3]; } while (0)
+#define V9_ACC16_READ_8_0(X) V9_C8_READ(X, c8_0)
+#define V9_ACC16_READ_8_1(X) V9_C8_READ(X, c8_1)
+#define V9_ACC16_READ_8_2(X) V9_C8_READ(X, c8_2)
+#define V9_ACC16_READ_8_3(X) V9_C8_READ(X, c8_3)
+#define V9_ACC16_READ_8_4(X) V9_C8_READ(X, c8_4)
+#define V9_ACC16_READ_8_5(X) V9_C8_READ(X, c8_5)
+#define V9_ACC16_READ_8_6(X) V9_C8_READ(X, c8_6)
+#define V9_ACC16_READ_8_7(X) V9_C8_READ(X, c8_7)
+__global__ __launch_bounds__(256, 1) void gemm_bf16_tile288_kernel(GemmArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int l = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr = w >> 1, wc = w & 1;      // this wave's 144 rows of A / B half
+  const int wm0 = wr * (BM288 / 2), wn0 = wc * 128;
+  const int stepA = BK7 * 2, stepB = BK7 * 2;          // bytes per K-tile
+  const int iA = (int)(32 * g.lda * 2), iB = (int)(32 * g.ldb * 2);      // bytes between a wave's consecutive pieces
+  const int nk = __builtin_amdgcn_readfirstlane(g.K / BK7);
+  const uint32_t lds0 = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(size_t)((__attribute__((address_space(3))) char*)smem));
+  const uint32_t wv = lds0 + (uint32_t)w * 1024u;
+  const uint32_t adA = lds0 + wr * (A_SLOT288 / 2) + v9_read_offset16<false>(l);
+  const uint32_t adB = lds0 + B_BASE288 + wc * HALF_BYTES + v9_read_offset16<false>(l);
+  int tile = blockIdx.x;
+  const int stride = (int)gridDim.x;
+  V9Tile t;
+  v9_tile_setup<false, false, BM288>(g, tile, w, l, t);
+  v9_tile_request<BM288>(t, smem, w, stepA, stepB);
+  bool first = true;
+  for (;;) {
+    f32x4 c8_0 = 0.f, c8_1 = 0.f, c8_2 = 0.f, c8_3 = 0.f, c8_4 = 0.f, c8_5 = 0.f, c8_6 = 0.f, c8_7 = 0.f;
+    __builtin_amdgcn_sched_barrier(0);
+    if (first) V9_ASM288(V9_LOOP288_TEXT_00, V9_LOOP288_CLOBBERS);
+    else V9_ASM288(V9_LOOP288_TEXT_00_W, V9_LOOP288_CLOBBERS);
+    __builtin_amdgcn_sched_barrier(0);
+    // this tile's output position, then (walking) the next tile: its requests go out BEFORE the epilogue
+    const int m0 = t.m0, n0 = t.n0;
+    e16* C = t.C;
+    const e16* Rp = t.Rp;
+    const int ntile = tile + stride;
+    const bool more = ntile < g.dp_tiles;      // (wave-uniform: kernel arguments and blockIdx only)
+    if (more) {
+      v9_tile_setup<false, false, BM288>(g, ntile, w, l, t);
+      __builtin_amdgcn_s_barrier();            // every wave has read its last fragments: the slots may be refilled
+      v9_tile_request<BM288>(t, smem, w, stepA, stepB);
+    }
+    const float alpha = g.alpha;
+    const int mrow = m0 + wm0 + (l & 15), ncol = n0 + wn0 + 4 * (l >> 4);
+    e16* crow = C + (long)mrow * g.ldc + ncol;
+    const e16* rrow = Rp ? Rp + (long)mrow * g.ldr + ncol : nullptr;
+    if (rrow == nullptr) {
+      V9_EPI16(V9_F16PS, crow, g.ldc, alpha);
+      V9_R16(V9_F16PS, 8, crow, g.ldc, alpha);
+    } else {
+      // the lane's 72 residual fragments up front, as on the 256 tile
+      e16x4 rv_[9][8];
+#pragma unroll
+      for (int i_ = 0; i_ < 9; ++i_)
+#pragma unroll
+        for (int j_ = 0; j_ < 8; ++j_)
+          rv_[i_][j_] = *reinterpret_cast<const e16x4*>(rrow + (long)(16 * i_) * g.ldr + 16 * j_);
+      __builtin_amdgcn_sched_barrier(0);
+      V9_EPI16(V9_F16RS, crow, g.ldc, alpha);
+      V9_R16(V9_F16RS, 8, crow, g.ldc, alpha);
+    }
+    if (!more) break;
+    tile = ntile;
+    first = false;
+  }
+}
+#undef V9_C8_READ
+#undef V9_ACC16_READ_8_0
+#undef V9_ACC16_READ_8_1
+#undef V9_ACC16_READ_8_2
+#undef V9_ACC16_READ_8_3
+#undef V9_ACC16_READ_8_4
+#undef V9_ACC16_READ_8_5
+#undef V9_ACC16_READ_8_6
+#undef V9_ACC16_READ_8_7
+
+int launch_tile288(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_tile288_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS288) != hipSuccess)
+      return MK_ERR_LAUNCH;
+    attr_done = true;
+  }
+  MK_LAUNCH(gemm_bf16_tile288_kernel, grid, dim3(256), LDS288, st, g);
+  return mk_check_launch();
+}
+#endif  // V9_MFMA16 == 15
+
 template <bool A_RED, bool B_RED>
 int launch_v9(const GemmArgs& g, dim3 grid, hipStream_t st) {
   static bool attr_done = false;
@@ -530,9 +681,15 @@ int launch_v9(const GemmArgs& g, dim3 grid, hipStream_t st) {
 }  // namespace MK_E16_NS
 }  // namespace
 #undef V9_ASM
+#undef V9_ASM288
+#undef V9_ASM_IN
 #if V9_MFMA16
 #undef V9_EPI16
 #undef V9_R16
 #undef V9_F16P
+#undef V9_F16R
+#undef V9_F16PS
+#undef V9_F16RS
+#undef V9_FP32
 #undef V9_ST8
 #endif

@@ -21,6 +21,9 @@ Register map of the asm block (fixed physical registers, all in the clobber list
 Round 6: the loops that ship run on v_mfma_f32_16x16x32 (MFMA16 mask; functions *16 below: `loop_text16`, `body16`, `quarter`);
 the round-5 loops on v_mfma_f32_32x32x16 (`loop_text`, `body`, `kstep`) are still generated with --no-mfma16 and still
 simulated by the tests.
+
+--tile288 writes macaw_llm_amd/csrc/gemm_v9_loop288.inc instead: the loop of the 288 x 256 x 64 tile (functions *288 below, with
+their own register map, LDS slots and wait protocol; tests/test_v9_gen288_cpu.py).  gemm_v9_loop.inc does not depend on it.
 """
 import sys
 
@@ -429,6 +432,178 @@ def acc_read_macros16():
     return "\n".join(out)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# The 288 x 256 x 64 tile (--tile288 -> gemm_v9_loop288.inc): the forward layout only (both operands K-major), on
+# v_mfma_f32_16x16x32.  4 waves as 2 x 2, wave tile 144 x 128 = 9 x 8 fragments: per K-tile 144 MFMAs in four quarters of 36
+# (quarter q = B fragments 4 (q & 1) .. + 3 x all nine A fragments of k32-step q >> 1), 34 ds_read_b128, 17 LDS-DMA pieces
+# (the A tile is 36 pieces of 1 KiB = 8 rows: wave w owns pieces w + 4 i, i = 0 .. 8, 32 rows apart, ONE linear image with no
+# halves; B as on the 256 tile, pieces w + 4 i, i = 0 .. 7).  Every element is summed over K in the order of the 256 tile's
+# loop by the same MFMA, so the results are the same bits.
+#
+# LDS: TWO A slots of 36,864 B and TWO B slots of 32,768 B = 139,264 B.  With ONE barrier per K-tile both halves of B(T) are
+# released by the same barrier that publishes B(T + 1), so a B ring needs four half-slots whatever their order: three A slots
+# + three B halves (159,744 B) would need a second barrier per K-tile, and three A + two B slots are 176,128 B.  Protocol
+# of tile T (slot T & 1):   quarter 0: LDS-DMA B(T + 1) -> the other B slot (free since barrier T - 1), reads A k32-step 1;
+# quarter 1: reads B k32-step 1;   quarter 2: the read addresses move to the other slots;   s_waitcnt vmcnt(0) lgkmcnt(0) +
+# s_barrier: tile T + 1 has landed (A(T + 1) was requested in quarter 3 of T - 1), nobody reads tile T any more;
+# quarter 3: reads k32-step 0 of T + 1, LDS-DMA A(T + 2) -> A(T)'s slot.  Every request has >= 5/8 of a K-tile to land,
+# which is what the 256 tile's shortest one (B half 1) has.
+# Register map:  accumulator (i, j): i < 8 in a[(8 i + j) * 4 ..] (the 256 tile's map: the epilogue shares its read macros),
+# fragment row 8 in eight 4-register VGPR operands %[c0] .. %[c7] the compiler allocates (zeroed by it, read back by it);
+# set s: A fragments v[68 s + 4 i ..], B fragments v[68 s + 36 + 4 j ..];  v[136:144] / v[145:152] LDS-DMA voffsets of A / B;
+# v[153:154] / v[155:156] LDS read addresses of A / B per k32-step.
+# s64 A slot of T (0 / 36864)   s65 B slot of T (0 / 32768)   s66 K-tile byte offset of A(T + 2)   s67 of B(T + 1)   s68 counter
+# s69 M0 base   s70 / s72 A / B slot of T + 1   s73 / s74 slot deltas
+A_SLOT288, B_SLOT288 = 36864, 32768
+B_BASE288 = 2 * A_SLOT288
+LDS288 = B_BASE288 + 2 * B_SLOT288
+SA288, SB288 = [0, 68], [36, 104]
+VOA288, VOB288, ADA288, ADB288 = 136, 145, 153, 155
+NV288 = 157
+
+
+def frag_reads288(op, s, h):
+    base, ad, n = (SA288[s], ADA288, 9) if op == "A" else (SB288[s], ADB288, 8)
+    return [f"ds_read_b128 v[{base + 4 * f}:{base + 4 * f + 3}], v{ad + h}" + (f" offset:{f * 2048}" if f else "")
+            for f in range(n)]
+
+
+def mfmas288(q):
+    s = q >> 1
+    out = []
+    for j in range(4 * (q & 1), 4 * (q & 1) + 4):
+        for i in range(9):
+            acc = f"a[{(8 * i + j) * 4}:{(8 * i + j) * 4 + 3}]" if i < 8 else f"%[c{j}]"
+            out.append(f"v_mfma_f32_16x16x32_@SFX@ {acc}, v[{SB288[s] + 4 * j}:{SB288[s] + 4 * j + 3}], "
+                       f"v[{SA288[s] + 4 * i}:{SA288[s] + 4 * i + 3}], {acc}")
+    return out
+
+
+def quarter288(e, q, reads, dma, late, wait):
+    """36 MFMAs, gap g follows MFMA g.  Reads are spread evenly over the gaps; LDS-DMA piece k has its M0 write in gap 2 k and
+    its load in gap 2 k + 1 (an MFMA between them is the wait state M0 needs); `late` entries follow, one per gap, from gap
+    2 len(dma) + 1 on (they may overwrite what the pieces read).  At most 3 entries per gap."""
+    gaps = [[] for _ in range(36)]
+    if NO_READ:
+        reads = []
+    if NO_DMA:
+        dma = []
+    for k, r in enumerate(reads):
+        gaps[k * 36 // len(reads)].append(r)
+    for k, (m0w, ld) in enumerate(dma):
+        gaps[2 * k].append(m0w)
+        gaps[2 * k + 1].append(ld)
+    for k, ins in enumerate(late):
+        gaps[2 * len(dma) + 1 + k].append(ins)
+    ms = mfmas288(q)
+    if wait:
+        e("s_waitcnt lgkmcnt(0)")
+    for g in range(36):
+        assert len(gaps[g]) <= 3, (q, g, gaps[g])
+        e(ms[g])
+        for ins in gaps[g]:
+            e(ins)
+
+
+def dma_group288(op, soff):
+    rs, vo, n = ("%[rsA]", VOA288, 9) if op == "A" else ("%[rsB]", VOB288, 8)
+    return [(f"s_add_u32 m0, s69, {i * 4096}" if i else "s_mov_b32 m0, s69",
+             f"buffer_load_dwordx4 v{vo + i}, {rs}, {soff} offen lds") for i in range(n)]
+
+
+def body288(e, mode):
+    nxt = mode != "LAST"
+    full = mode == "FULL"
+    late = []
+    if nxt:
+        e(f"s_xor_b32 s72, s65, {B_SLOT288}")
+        e("s_add_u32 s69, %[wv], s72")
+        e(f"s_add_u32 s69, s69, {B_BASE288}")
+        late = ["s_add_u32 s67, s67, %[stB]", f"s_sub_u32 s70, {A_SLOT288}, s64", "s_sub_u32 s73, s70, s64",
+                "s_sub_u32 s74, s72, s65"]
+    quarter288(e, 0, frag_reads288("A", 1, 1), dma_group288("B", "s67") if nxt else [], late, wait=True)
+    quarter288(e, 1, frag_reads288("B", 1, 1), [], [], wait=False)
+    late = []
+    if nxt:     # the read addresses move to tile T + 1's slots (their last reads of tile T were issued in quarters 0 / 1)
+        late = [f"v_add_u32 v{ADA288 + k}, s73, v{ADA288 + k}" for k in range(2)] + \
+               [f"v_add_u32 v{ADB288 + k}, s74, v{ADB288 + k}" for k in range(2)]
+    quarter288(e, 2, [], [], late, wait=True)
+    if nxt:
+        e("s_waitcnt vmcnt(0) lgkmcnt(0)")
+        if not NO_BAR:
+            e("s_barrier")
+    if full:
+        e("s_add_u32 s69, %[wv], s64")
+    late = (["s_add_u32 s66, s66, %[stA]"] if full else []) + (["s_mov_b32 s64, s70", "s_mov_b32 s65, s72"] if nxt else [])
+    reads = (frag_reads288("A", 0, 0) + frag_reads288("B", 0, 0)) if nxt else []
+    quarter288(e, 3, reads, dma_group288("A", "s66") if full else [], late, wait=False)
+
+
+def prologue288(e, walk):
+    e(f"v_mov_b32 v{VOA288}, %[voA]")
+    e(f"v_mov_b32 v{VOB288}, %[voB]")
+    for i in range(1, 9):
+        e(f"v_add_u32 v{VOA288 + i}, %[iA], v{VOA288 + i - 1}")
+    for i in range(1, 8):
+        e(f"v_add_u32 v{VOB288 + i}, %[iB], v{VOB288 + i - 1}")
+    for op, ad in (("A", ADA288), ("B", ADB288)):
+        e(f"v_mov_b32 v{ad}, %[ad{op}]")
+        e(f"v_xor_b32 v{ad + 1}, 0x40, v{ad}")                          # k32-step 1: 16-byte chunk + 4
+    e("s_mov_b32 s64, 0")
+    e("s_mov_b32 s65, 0")
+    e("s_lshl_b32 s66, %[stA], 1")
+    e("s_mov_b32 s67, %[stB]")
+    e("s_sub_u32 s68, %[nk], 2")
+    for r in range(256):
+        e(f"v_accvgpr_write_b32 a{r}, 0")
+    # requested by the C++ side: tile 0 (17 pieces), then A(1) (9 pieces).  A walking workgroup's later tiles: as in prologue16
+    e("s_waitcnt vmcnt(0)" if walk else "s_waitcnt vmcnt(9)")
+    e("s_barrier")
+    for r in frag_reads288("A", 0, 0) + frag_reads288("B", 0, 0):
+        e(r)
+
+
+def loop_text288(walk=False):
+    e = Emit()
+    prologue288(e, walk)
+    e("s_cmp_eq_u32 s68, 0")
+    e("s_cbranch_scc1 .Lv9n%=")
+    e(".p2align 6")
+    e(".Lv9l%=:")
+    body288(e, "FULL")
+    e("s_sub_u32 s68, s68, 1")
+    e("s_cmp_lg_u32 s68, 0")
+    e("s_cbranch_scc1 .Lv9l%=")
+    e(".Lv9n%=:")
+    body288(e, "NEXT")
+    body288(e, "LAST")
+    e("s_nop 15")
+    e("s_nop 15")
+    return e.lines
+
+
+def main288(path):
+    parts = ["// GENERATED by scripts/gen_v9_loop.py --tile288 -- do not edit (tests/test_v9_gen288_cpu.py compares).",
+             "// The K loop of the 288 x 256 x 64 tile of gemm_v9 as inline asm (both operands K-major); MK_V9_SFX = \"bf16\" / \"f16\".",
+             "// Register map, LDS slots and the wait protocol: see the generator."]
+    for walk in (False, True):
+        lines = loop_text288(walk)
+        order_ok(lines)
+        parts.append(f"#define V9_LOOP288_TEXT_00{'_W' if walk else ''} \\\n" + c_string(lines))
+    clob = ", ".join([f'"v{r}"' for r in range(NV288)] + [f'"a{r}"' for r in range(256)] +
+                     [f'"s{r}"' for r in range(64, 76)] + ['"scc"', '"memory"'])
+    parts.append(f"#define V9_LOOP288_CLOBBERS {clob}")
+    parts.append(f"#define V9_LDS288 {LDS288}")
+    parts.append(f"#define V9_A_SLOT288 {A_SLOT288}")
+    parts.append(f"#define V9_B_BASE288 {B_BASE288}")
+    txt = "\n".join(parts) + "\n"
+    if path == "-":
+        sys.stdout.write(txt)
+    else:
+        with open(path, "w") as f:
+            f.write(txt)
+
+
 def loop_text(a_red, b_red, walk=False):
     e = Emit()
     prologue(e, a_red, b_red, walk)
@@ -528,8 +703,11 @@ def main(path):
 
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    tile288 = False
     for a in sys.argv[1:]:
-        if a == "--nodma":
+        if a == "--tile288":
+            tile288 = True
+        elif a == "--nodma":
             NO_DMA = True
         elif a == "--noread":
             NO_READ = True
@@ -541,4 +719,7 @@ if __name__ == "__main__":
             MFMA16 = 0
         elif a.startswith("--"):
             sys.exit(f"unknown option {a}")
-    main(args[0] if args else "macaw_llm_amd/csrc/gemm_v9_loop.inc")
+    if tile288:
+        main288(args[0] if args else "macaw_llm_amd/csrc/gemm_v9_loop288.inc")
+    else:
+        main(args[0] if args else "macaw_llm_amd/csrc/gemm_v9_loop.inc")
