@@ -468,7 +468,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamItem* items,
   // flight per lane before the first use
   for (long i0 = base + (long)threadIdx.x * N; i0 < vec_end; i0 += 512L * N) {
     const long i1 = i0 + 256L * N;
-    const bool two = i1 < vec_end;             // (a chunk is 32768 elements: true except on a ragged tail)
+    const bool two = i1 < vec_end;             // (a full MK_ADAMW_CHUNK slice is whole trips of both groups: false only on a tensor's ragged last slice)
     const long j1 = two ? i1 : i0;
     float g0[N], w0[N], m0[N], v0[N], g1[N], w1[N], m1[N], v1[N];
     adam_load4_nt(grad + i0, g0);
