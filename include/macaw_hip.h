@@ -553,6 +553,54 @@ int mk_seq_ban(void* logits, int64_t ld, int32_t V, int32_t B, const int64_t* pr
                int32_t n_add, const int64_t* seq_ids, const int32_t* seq_off, int32_t n_seq, int32_t dtype, void* stream);
 int mk_stop_match(const int64_t* out, int64_t out_ld, int32_t n_max, int32_t B, const int32_t* n_dev, int32_t n_add,
                   const int64_t* seq_ids, const int32_t* seq_off, int32_t n_seq, void* done, void* stream);
+/* Grammar-constrained decoding (generate(grammar=)): a deterministic automaton over token ids held in device memory --
+ *   what vLLM (guided_regex, guided_choice), TGI (grammar) and outlines offer, and HF's prefix_allowed_tokens_fn without
+ *   its Python callback per token -- written down here; restated in numpy / torch in tests/grammar_ref.py, to which the
+ *   three kernels are pinned exactly (integers and the -inf bit pattern only).
+ *
+ * The device table of a grammar: next int32 [n_states][V] at row pitch ld_next >= V, next[s][t] the state after token t
+ *   in state s, or -1 when t is not allowed; flags uint8 [n_states], bit 0 = accepting, bit 1 = terminal, which is
+ *   accepting with no allowed token.  The table is token-trimmed: a transition into a state from which no accepting
+ *   state can be reached by tokens of this vocabulary is -1 (the table's maker does that; the kernels take the table as
+ *   it stands).  Per sample: state int32 [B], -1 an unconstrained row, -2 a broken one.
+ *
+ * The mask rule (mk_grammar_mask), in place, BEHIND mk_logits_process and mk_seq_ban and in front of every selection
+ *   (mk_decode_emit, mk_decode_emit_sample, mk_argmax_rows, mk_sample_rows): nothing is written for a row whose done
+ *   byte is set, or whose state is < 0 or >= n_states.  Otherwise every column c in [0, V) with next[s][c] < 0 is set to
+ *   -inf, and column eos (when 0 <= eos < V) is set to -inf unless flags[s] & 1: the table's own entry in that column is
+ *   ignored.  Every other column keeps its bits, +-0, +-inf and NaN included, and so does the padding [V, ld).  This is
+ *   HF's PrefixConstrainedLogitsProcessor with the callback allowed(state) + [eos if accepting], with the two
+ *   deliberate differences mk_seq_ban documents: the banned column is SET to -inf whatever it held (HF ADDS -inf, which
+ *   turns a banned +inf or NaN into NaN), and -0 stays -0.
+ *   One launch of (column chunks of 1024, rows) workgroups of 256 threads; a thread reads four entries of the table's row
+ *   -- one 16-byte load where ld_next % 4 == 0 and the table is 16-byte aligned, four 4-byte loads otherwise --
+ *   and the row offset state * ld_next is computed in 64 bits.  Only banned columns are written.
+ *
+ * The advance rule (mk_grammar_advance), right BEHIND the emit and in front of mk_stop_match and
+ *   mk_decode_emit_logprobs, with n = clamp((n_dev ? *n_dev : 0) + n_add, 0, n_max) read as mk_stop_match reads it: a
+ *   row that was done before this launch is skipped (a row whose emit just took eos included), and so is a row with
+ *   state < 0.  Otherwise t = out[b][n - 1] and s' = next[s][t], taken as -1 when t is outside [0, V) (and when n == 0,
+ *   s >= n_states or s' >= n_states).  s' >= 0: state[b] = s'; if s' is terminal, done[b] = 1 and end[b] = n.  s' < 0,
+ *   reachable only when other processors banned every allowed column: state[b] = -2, done[b] = 1, end[b] = n.  The
+ *   completing token stays in the output and pad follows it, as with a stop sequence, and it keeps its real
+ *   log-probability.  end int32 [B] starts at -1.  The advance is stateful: it runs exactly once per step.  One thread
+ *   per row; no other byte is written; plain vector stores, no atomics.
+ *
+ * mk_grammar_build makes the table of a byte-level automaton: char_next int32 [S][256] (-1: dead), the vocabulary as
+ *   tok_bytes uint8 [total], the tokens' bytes back to back, and tok_off int32 [V + 1] ascending from 0.  Entry (s, t)
+ *   is char_next walked over token t's bytes from s: -1 on a dead byte transition or an empty token.  One thread per
+ *   (state, token), tokens of any length.  The offsets are device memory and are taken as they stand: the caller
+ *   (ops.grammar_build) checks on the host that they ascend from 0 before it uploads them.
+ *
+ * MK_ERR_BAD_ARG for a null pointer (n_dev may be null), B <= 0, V <= 0, S <= 0, n_states <= 0, ld < V, ld_next < V,
+ *   n_max < 0, out_ld < n_max.  MK_ERR_UNSUPPORTED: another dtype, more than 65535 rows, S * V >= 2^32 (mk_grammar_build runs one thread per entry). */
+int mk_grammar_mask(void* logits, int64_t ld, int32_t V, int32_t B, const int32_t* next, int64_t ld_next, int32_t n_states,
+                    const void* flags, const int32_t* state, const void* done, int64_t eos, int32_t dtype, void* stream);
+int mk_grammar_advance(const int64_t* out, int64_t out_ld, int32_t n_max, int32_t B, int32_t V, const int32_t* n_dev,
+                       int32_t n_add, const int32_t* next, int64_t ld_next, int32_t n_states, const void* flags,
+                       int32_t* state, void* done, int32_t* end, void* stream);
+int mk_grammar_build(const int32_t* char_next, const void* tok_bytes, const int32_t* tok_off, int32_t S, int32_t V,
+                     int32_t* next, int64_t ld_next, void* stream);
 /* Token log-probabilities (generate(return_logprobs=True, top_logprobs=n)): how sure the model was of a token, HF's
  *   compute_transition_scores(normalize_logits=True), written down here; restated in numpy in tests/logprobs_ref.py, to
  *   which the kernels are pinned.  The logits are read as they stand in front of the selection: behind the logits

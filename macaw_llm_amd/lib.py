@@ -123,6 +123,9 @@ SIGNATURES = {
                           _i32, _vp],
     "mk_seq_ban": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp],
     "mk_stop_match": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
+    "mk_grammar_mask": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp],
+    "mk_grammar_advance": [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "mk_grammar_build": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp],
     "mk_token_logprobs": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp],
     "mk_decode_emit_logprobs": [_vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32,
                                 _vp],

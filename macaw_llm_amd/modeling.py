@@ -81,6 +81,8 @@ PARALLEL_SAMPLES = [1]
 SESSION = [False]
 # MM_LLMs.set_adapters: the adapter_names MM_LLMs.forward hands to generate() (None = off: the call without them)
 ADAPTERS = [None]
+# MM_LLMs.set_grammar: the grammar MM_LLMs.forward hands to generate() (None = off: the call without it)
+GRAMMAR = [None]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -180,6 +182,40 @@ def _stopping_check(where, stop_sequences, bad_words_ids, eos=None, num_beams=1,
     if bad is not None:
         bad = [q for q in bad if q != [eos]] or None
     return stop, bad
+
+
+def _grammar_check(where, grammar, num_beams=1, lookup=0, session=False):
+    """the grammar of generate() / set_grammar -> a TokenDFA (every row) or a list of TokenDFA | None (one per prompt)"""
+    from .grammar import TokenDFA
+    rows = list(grammar) if isinstance(grammar, (list, tuple)) else [grammar]
+    for g in rows:
+        if not isinstance(g, TokenDFA) and not (g is None and isinstance(grammar, (list, tuple))):
+            raise ValueError(f"{where}: grammar must be None, a grammar.TokenDFA or a list of TokenDFA | None (one per "
+                             f"prompt), got {type(g).__name__}")
+    if isinstance(grammar, (list, tuple)) and not rows:
+        raise ValueError(f"{where}: grammar is an empty list; pass None, a grammar.TokenDFA or one entry per prompt")
+    if num_beams > 1:
+        raise ValueError(f"{where}(grammar=) with num_beams={num_beams}: grammars along each beam's back-tracked history "
+                         "are not built; use num_beams=1")
+    if lookup:
+        raise ValueError(f"{where}(grammar=) with prompt_lookup_num_tokens={lookup}: a constrained multi-token verify step "
+                         "is not built")
+    if session:
+        raise ValueError(f"{where}(grammar=) with session= / return_session=True: a grammar's state is not kept across "
+                         "sessions (not built)")
+    return rows if isinstance(grammar, (list, tuple)) else grammar
+
+
+def _grammar_rows(gram, n_prompts, V):
+    """generate(grammar=) once the batch and the vocabulary are known -> one TokenDFA | None per prompt"""
+    rows = gram if isinstance(gram, list) else [gram] * n_prompts
+    if len(rows) != n_prompts:
+        raise ValueError(f"generate(grammar=): a list of {len(rows)} grammars for {n_prompts} prompts (one per prompt, None "
+                         "for an unconstrained row)")
+    for g in rows:
+        if g is not None and g.vocab_size is not None and g.vocab_size != V:
+            raise ValueError(f"generate(grammar=): the grammar's vocabulary size {g.vocab_size} is not the model's ({V})")
+    return rows
 
 
 def _guidance_check(where, guidance_scale):
@@ -837,7 +873,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     # host looking before every step.
     @torch.no_grad()
     def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None,
-                        n_top=None, feed=None, stopped=None):
+                        n_top=None, feed=None, stopped=None, rematch=None, ends=None):
         """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
         memory -- the position (int32 counter read by the fused RoPE + cache append + attention
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
@@ -851,7 +887,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         GenerateLogprobs, trimmed to the ids' columns.  feed(tok) (None: the embedding of tok): the token rows a step runs
         on -- with guidance_scale both rows of every sample, B counting the samples: `logits` then takes 2B hidden rows
         and returns the B guided rows, and tok, done, out_buf, state and the books stay per sample.  stopped(out_buf,
-        done, n_dev) (None: off): the stop-sequence match directly behind the emit, which sets done flags as eos does."""
+        done, n_dev) (None: off): what sets done flags directly behind the emit as eos does -- the grammar's advance, which
+        is stateful and runs once per step, then the stop-sequence match.  rematch (None: none): the stateless part of it,
+        the match, which the loop evaluates once more over every returned column for the width; ends (None: no grammar):
+        int32 [B], the count at which the grammar finished a row (-1: it did not), which gives the width its part."""
         state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
         t_dev = state[:1]
         tok = torch.zeros(B, dtype=torch.long, device=dev)
@@ -863,7 +902,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         def emit(h_last):                # argmax, pad / eos handling, output column, position += 1
             lg = logits(h_last)
             if process is not None:
-                process(lg, out_buf, state[1:2])
+                process(lg, out_buf, state[1:2], done=done)
             if sample is not None:
                 ops.decode_emit_sample(lg, V, pad, eos, tok, done, out_buf, state, *sample)
             else:
@@ -882,10 +921,14 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         # the eager loop stops right after the token at which every sample has finished
         fin = (res == eos).cumsum(1) > 0
         if stopped is not None and bool(done.all()):     # ... by eos or by a stop sequence: every column's tail, once more
-            hit = torch.zeros((res.shape[1], B), dtype=torch.bool, device=dev)
-            for c in range(res.shape[1]):
-                stopped(out_buf, hit[c], n_add=c + 1)
-            fin |= hit.t().cumsum(1) > 0
+            if rematch is not None:
+                hit = torch.zeros((res.shape[1], B), dtype=torch.bool, device=dev)
+                for c in range(res.shape[1]):
+                    rematch(out_buf, hit[c], n_add=c + 1)
+                fin |= hit.t().cumsum(1) > 0
+            if ends is not None:     # the grammar's ends were written when they happened: the advance is not run again
+                cols = torch.arange(res.shape[1], dtype=torch.int32, device=dev)
+                fin |= (ends >= 0)[:, None] & (cols[None, :] >= ends[:, None] - 1)
         fin = fin.all(0)
         if bool(fin.any()):
             res = res[:, : int(torch.nonzero(fin)[0]) + 1]
@@ -974,7 +1017,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
                  negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
                  bad_words_ids=None, num_samples=1, session=None, return_session=False, session_capacity=None,
-                 adapter_names=None, **_):
+                 adapter_names=None, grammar=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -1237,7 +1280,32 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         name, a wrong count of names, a model without a bank or with a live adapter as well, fp32, use_cache=False, unfused
         storage, more than 32 rows, a shape outside ops.decode_attn_ok, num_beams > 1, num_samples > 1,
         prompt_lookup_num_tokens > 0, guidance_scale and sessions (each maps rows to samples in its own way: not built).
-        None (the default): not one launch differs."""
+        None (the default): not one launch differs.
+
+        grammar=g: grammar-constrained decoding -- what vLLM's guided_regex / guided_choice, TGI's grammar and outlines
+        give, and HF's prefix_allowed_tokens_fn without its Python callback per token.  g is a grammar.TokenDFA
+        (TokenDFA.from_regex(pattern, vocab), .from_choices(token-id lists), .from_edges(...)), applied to every row, or a
+        list with one entry per prompt, each a TokenDFA or None for an unconstrained row; distinct objects go into one
+        device table back to back.  The rule is written down in include/macaw_hip.h and restated in
+        tests/grammar_ref.py: a row may only emit tokens its current state allows, eos exactly in accepting states, and a
+        row whose state becomes terminal (accepting, nothing may follow) finishes there as at a stop sequence -- the
+        completing token stays in the output with its real log-probability, pad_token_id follows, and the returned width
+        is the column at which the last row finished.  One launch (ops.grammar_mask) sets the other columns to -inf
+        behind ops.logits_process and ops.seq_ban and in front of every selection, token 0 included; one launch
+        (ops.grammar_advance) moves the per-row state right behind the emit, in front of ops.stop_match.  Table, states
+        and ends live on the device: on the hipGraph path both launches are inside the captured step, still one replay
+        per token, and the host reads nothing more.  The eager loops (decode_graph=False, MACAW_NO_DECODE_GRAPH,
+        max_new_tokens <= 2), the padded-batch loops and use_cache=False (any dtype) run the same two launches.
+        Composes with decode_weights, kv_cache="fp8", sampling (mask first, then the warpers: top_k counts allowed
+        columns), the processors, bad_words_ids, stop_sequences, log-probabilities (scored on the masked logits, i.e.
+        renormalised over the allowed set, as in HF), a padded mask, guidance (on the B guided rows), num_samples (each
+        prompt's start state repeats n times), LoRA and adapter_names.  Two limits: max_new_tokens can cut an answer
+        short (check with g.walk(ids) / g.is_accepting), and without an eos_token_id an accepting state that still has
+        allowed tokens never ends by itself.  Should the other processors ban every column a state allows, the row is
+        marked broken and finishes.  ValueError naming the condition for an object that is not a TokenDFA, num_beams > 1,
+        prompt_lookup_num_tokens > 0, session= / return_session=True (grammars along beams, through the verify step and
+        across sessions are not built), a list of the wrong length and a vocabulary size that is not the model's.  None
+        (default): nothing is allocated, launched or read."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1352,6 +1420,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 why = "use_cache=False (the recompute loop runs the training layer, which has no per-row adapters)"
             if why is not None:
                 raise ValueError(f"{what}: {why}")
+        gram = None               # grammar=: one TokenDFA | None per prompt (None: off, nothing below runs)
+        if grammar is not None:
+            gram = _grammar_check("generate", grammar, K, G, sess)
         no_graph = _no_decode_graph(decode_graph, max_new_tokens)
         graph = no_graph is None  # the decode step is captured in a hipGraph (the greedy loop also needs decode_attn_ok)
 
@@ -1359,6 +1430,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if inputs_embeds is None:
             inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(*input_ids.shape, -1)
         _dev_check(inputs_embeds)
+        n_prompts, rows_per = inputs_embeds.shape[0], N      # (grammar=: the prompts and the rows each of them decodes)
         if N > 1 and not use_cache:   # the prompt repeated N times through the recompute loop: a batch of B * N rows
             inputs_embeds = inputs_embeds.repeat_interleave(N, 0)
             attention_mask = attention_mask.repeat_interleave(N, 0) if attention_mask is not None else None
@@ -1504,26 +1576,45 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 raise ValueError(f"{call} and use_cache=True: {why}; the "
                                  "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
                                  "there is no masked attention over a cache: pass use_cache=False")
+        if gram is not None:
+            gram = _grammar_rows(gram, n_prompts, V)
+            if all(g is None for g in gram):          # a list of unconstrained rows: the plain call
+                gram = None
 
         if N > 1:                 # from here on the emits, the books and the processors count the B * N rows
             Bs = B * N
             if hist is not None:  # row r's history starts with its prompt's ids
                 hist, hist_len = hist.repeat_interleave(N, 0).contiguous(), hist_len.repeat_interleave(N).contiguous()
-        process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add)
-        if proc is not None or bad is not None:
+        g_tab = g_state = g_end = None    # grammar=: the device table, and per row its state and the count it ended at
+        if gram is not None:
+            from .grammar import combine
+            g_tab, g_start = combine(gram, dev, V)
+            g_state = torch.tensor(g_start, dtype=torch.int32).repeat_interleave(rows_per).to(dev)
+            g_end = torch.full((Bs,), -1, dtype=torch.int32, device=dev)
+        process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add, done)
+        if proc is not None or bad is not None or g_tab is not None:
             bad_t = ops.SeqTable(bad, dev) if bad is not None else None
 
-            def process(lg, gen, n_dev=None, n_add=0):
+            def process(lg, gen, n_dev=None, n_add=0, done=None):
                 if proc is not None:
                     ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
                 if bad_t is not None:  # bad_words_ids: one more launch behind the processors, on the same history
                     ops.seq_ban(lg, V, gen, bad_t, n_dev, n_add, hist, hist_len)
+                if g_tab is not None:  # grammar: behind both, so that the selection sees allowed columns alone
+                    ops.grammar_mask(lg, V, g_tab, g_state, done, eos_token_id)
         stopped = None                # stop_sequences: stopped(generated ids [B, n_max], done, n_dev, n_add) behind an emit
         if stop is not None:
             stop_t = ops.SeqTable(stop, dev)
 
             def stopped(gen, done, n_dev=None, n_add=0):
                 ops.stop_match(gen, stop_t, done, n_dev, n_add)
+        rematch = stopped             # what the graph loop may evaluate once more behind its steps: the stateless match
+        if g_tab is not None:         # grammar: the state moves in front of the match, exactly once per step
+
+            def stopped(gen, done, n_dev=None, n_add=0):
+                ops.grammar_advance(gen, g_tab, g_state, done, g_end, n_dev, n_add)
+                if rematch is not None:
+                    rematch(gen, done, n_dev, n_add)
         if process is not None or stopped is not None:
             gen_buf = torch.full((Bs, max_new_tokens), pad, dtype=torch.long, device=dev)  # the eager loops' ids so far
         w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
@@ -1551,7 +1642,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             pads = torch.full((Bs,), pad, dtype=torch.long, device=dev)
             lg = logits(h_last)
             if process is not None:
-                process(lg, gen_buf, n_add=t)
+                process(lg, gen_buf, n_add=t, done=done)
             ids = ops.sample_rows(lg, V, *sample, step=t) if sample is not None else ops.argmax_rows(lg, V)
             nxt = torch.where(done, pads, ids)
             if gen_buf is not None:
@@ -1740,7 +1831,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                                  length_penalty, early_stopping, graph))
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
             res = self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
-                                       process, n_top, feed, stopped)
+                                       process, n_top, feed, stopped, rematch, g_end)
             return hand_over(res) if sess else res
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch or of
         # parallel samples
@@ -1966,6 +2057,9 @@ class MM_LLMs(PreTrainedModel):
             # adapters set: one name per sample out of the LLM's bank; unset: exactly the call without them
             if ADAPTERS[0] is not None:
                 par["adapter_names"] = ADAPTERS[0]
+            # a grammar set: every answer is constrained by it; unset: exactly the call without it
+            if GRAMMAR[0] is not None:
+                par["grammar"] = GRAMMAR[0]
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
@@ -2105,6 +2199,18 @@ class MM_LLMs(PreTrainedModel):
                 raise ValueError(f"set_adapters: names must be None or a list of adapter names (str), got {names!r}")
             names = list(names)
         ADAPTERS[0] = names
+
+    @staticmethod
+    def set_grammar(g=None):
+        """Grammar-constrained decoding for `inputs["inference"] = True` (LlamaForCausalLM.generate's grammar): off (None)
+        by default.  g: a grammar.TokenDFA applied to every sample, or a list with one TokenDFA | None per sample.  With a
+        LLaMA SentencePiece tokenizer, grammar.vocab_bytes(tokenizer.convert_ids_to_tokens(range(V)), special ids) is the
+        vocabulary TokenDFA.from_regex takes.  The form is validated here; what depends on the call (beams, prompt lookup,
+        sessions, the batch, the vocabulary size) is validated by generate().  No arguments: back to off.  Process-wide
+        switch, like set_stopping."""
+        if g is not None:
+            g = _grammar_check("set_grammar", g)
+        GRAMMAR[0] = g
 
     @staticmethod
     def set_parallel_samples(num_samples=1):

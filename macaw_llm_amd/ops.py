@@ -876,6 +876,94 @@ def stop_match(out, table: SeqTable, done, n_dev=None, n_add=0):
                                _p(table.ids), _p(table.off), table.n, _p(done), _st()), "mk_stop_match")
 
 
+class GrammarTable:
+    """the device table of a grammar (include/macaw_hip.h, "Grammar-constrained decoding"): next int32 [n_states, V]
+    row-major at a pitch >= V whose rows are whole in its storage, flags uint8 [n_states] (bit 0 accepting, bit 1
+    terminal).  Taken as it stands: grammar.TokenDFA.table makes a trimmed one"""
+
+    def __init__(self, next, flags):
+        if next.dtype != torch.int32 or next.dim() != 2 or (next.shape[1] > 1 and next.stride(1) != 1) or next.numel() == 0:
+            raise MacawHipError(f"GrammarTable: next {next.dtype} {tuple(next.shape)} {next.stride()}; expected row-major "
+                                "int32 [n_states, V]")
+        self.n_states, self.V = next.shape
+        self.ld = max(next.stride(0), self.V)
+        if next.storage_offset() + self.n_states * self.ld > next.untyped_storage().nbytes() // 4:
+            raise MacawHipError("GrammarTable: the last row of next is shorter than the row pitch")
+        if flags.dtype != torch.uint8 or flags.numel() != self.n_states or not flags.is_contiguous():
+            raise MacawHipError(f"GrammarTable: flags {flags.dtype} {tuple(flags.shape)}; expected contiguous uint8 "
+                                f"[{self.n_states}]")
+        self.next, self.flags = next, flags
+
+
+def _grammar_rows(op, B, state, done):
+    if state.dtype != torch.int32 or state.numel() != B or not state.is_contiguous():
+        raise MacawHipError(f"{op}: state {state.dtype} {tuple(state.shape)}; expected contiguous int32 [{B}]")
+    if done.dtype not in (torch.bool, torch.uint8) or done.numel() != B or not done.is_contiguous():
+        raise MacawHipError(f"{op}: done {done.dtype} {tuple(done.shape)}; expected contiguous bool / uint8 [{B}]")
+
+
+def grammar_mask(logits, V, table: GrammarTable, state, done, eos=None):
+    """the grammar's mask in one launch, in place, behind logits_process and seq_ban and in front of a selection (see
+    mk_grammar_mask): in row b of logits [B, >= V] row-major every column that table.next[state[b]] does not allow gets
+    -inf, and so does eos unless the state is accepting; rows whose done flag is set or whose state is no state of the
+    table (-1: unconstrained) are not written.  Returns logits"""
+    lib = _L.load()
+    B = logits.shape[0]
+    _grammar_rows("grammar_mask", B, state, done)
+    if V != table.V:
+        raise MacawHipError(f"grammar_mask: {V} columns, but the table holds {table.V} tokens")
+    _L.check(lib.mk_grammar_mask(_p(logits), _rowmajor(logits), V, B, _p(table.next), table.ld, table.n_states,
+                                 _p(table.flags), _p(state), _p(done), -1 if eos is None else int(eos), dt(logits), _st()),
+             "mk_grammar_mask")
+    return logits
+
+
+def grammar_advance(out, table: GrammarTable, state, done, end, n_dev=None, n_add=0):
+    """the grammar's step in one launch, right behind an emit and in front of stop_match (see mk_grammar_advance): row b
+    that has not finished and has a state >= 0 moves along out[b, n - 1], n = (n_dev[0] if n_dev is not None else 0) +
+    n_add; a terminal state (or a token the table does not allow: state -2) sets done[b] and end[b] = n.  state int32
+    [B], done bool / uint8 [B] and end int32 [B] are updated in place.  Run it exactly once per step"""
+    lib = _L.load()
+    B = out.shape[0]
+    _gen_args("grammar_advance", B, out, n_dev)
+    _grammar_rows("grammar_advance", B, state, done)
+    if end.dtype != torch.int32 or end.numel() != B or not end.is_contiguous():
+        raise MacawHipError(f"grammar_advance: end {end.dtype} {tuple(end.shape)}; expected contiguous int32 [{B}]")
+    _L.check(lib.mk_grammar_advance(_p(out), max(out.stride(0), out.shape[1]), out.shape[1], B, table.V, _p(n_dev),
+                                    int(n_add), _p(table.next), table.ld, table.n_states, _p(table.flags), _p(state),
+                                    _p(done), _p(end), _st()), "mk_grammar_advance")
+
+
+def grammar_build(char_next, tok_bytes, tok_off, dev=None, ld_next=None):
+    """the token table of a byte automaton in one launch (see mk_grammar_build): char_next int32 [S, 256], tok_bytes uint8
+    [total] and tok_off int32 [V + 1], the vocabulary's bytes back to back -- host or device tensors; the offsets are
+    checked on the host (ascending from 0, the last one the total) before they are uploaded.  Returns next int32 [S, V] on
+    dev (default: char_next's device) at pitch ld_next (default: V rounded up to a multiple of 4, which lets the mask
+    load 16 bytes at a time)"""
+    lib = _L.load()
+    if char_next.dtype != torch.int32 or char_next.dim() != 2 or char_next.shape[1] != 256 or char_next.shape[0] < 1:
+        raise MacawHipError(f"grammar_build: char_next {char_next.dtype} {tuple(char_next.shape)}; expected int32 [S, 256]")
+    if tok_off.dtype != torch.int32 or tok_off.dim() != 1 or tok_off.numel() < 2 or tok_bytes.dtype != torch.uint8:
+        raise MacawHipError(f"grammar_build: tok_off {tok_off.dtype} {tuple(tok_off.shape)}, tok_bytes {tok_bytes.dtype}; "
+                            "expected int32 [V + 1] and uint8 [total]")
+    off = tok_off.cpu()
+    if int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) or int(off[-1]) != tok_bytes.numel():
+        raise MacawHipError("grammar_build: tok_off must ascend from 0 to the number of bytes")
+    dev = torch.device(char_next.device if dev is None else dev)
+    if dev.type != "cuda":
+        raise MacawHipError(f"grammar_build: the table is made by a HIP kernel and needs a GPU device, got {dev}")
+    S, V = char_next.shape[0], tok_off.numel() - 1
+    ld = (V + 3) // 4 * 4 if ld_next is None else int(ld_next)
+    if ld < V:
+        raise MacawHipError(f"grammar_build: ld_next {ld} < V {V}")
+    nxt = torch.full((S, ld), -1, dtype=torch.int32, device=dev)
+    cn, tb, to = char_next.to(dev).contiguous(), tok_bytes.to(dev).contiguous(), tok_off.to(dev).contiguous()
+    if tb.numel() == 0:          # a vocabulary of empty tokens: nothing to read, and no null pointer to pass
+        tb = torch.zeros(1, dtype=torch.uint8, device=dev)
+    _L.check(lib.mk_grammar_build(_p(cn), _p(tb), _p(to), S, V, _p(nxt), ld, _st()), "mk_grammar_build")
+    return nxt[:, :V]
+
+
 MAX_TOP_LOGPROBS = 20
 
 

@@ -84,6 +84,16 @@ with torch.no_grad():
 # kernels: 8 more launches per layer and token, 256 for the model).  ms per token of every run ((72 - 8 tokens) / 64), the
 # medians and each arm's run-to-run spread, and the time to the first token (the call with max_new_tokens=1: for "merged" it
 # holds the merge, for the names arms the prefill's per-run adapter launches)
+#        bench_generate.py --grammar-ab [--reps R] [B ...]: grammar-constrained decoding (default B = 1, 8, 32).  Three greedy arms
+# alternated in this process on this model: "greedy" = no grammar; "free" = a one-state grammar that allows every token, so the
+# ids are the greedy ones and the difference is the two launches per step (ops.grammar_mask in front of the emit,
+# ops.grammar_advance behind it); "json" = the 35-state pattern \{"name": "[a-z ]{1,12}", "n": (0|[1-9]\d?)\} over a synthetic
+# vocabulary of the model's size (3 specials, the 256 bytes, random pieces of 2 to 17 bytes), whose answer ends by itself: every
+# free arm is timed against greedy over 72 tokens ((72 - 8 tokens) / 64) and the json arm against greedy over its own width W ((W - 8 tokens) / (W - 8); 3 in place of 8 where W <= 16), ms per token of every run, the medians, the
+# differences and the greedy run-to-run spread.  Then the time of one ops.grammar_mask and one ops.grammar_advance launch inside a
+# hipGraph against their neighbours ops.decode_emit, ops.seq_ban and ops.stop_match, and the making of a table (ops.grammar_build plus the trim) for (S, V) = (35, V) and for a pattern of 3001
+# states
+GRAMMAR = "--grammar-ab" in sys.argv
 ADAPTERS = "--adapters-ab" in sys.argv
 SESSION = "--session-ab" in sys.argv
 NSAMPLE = "--nsample-ab" in sys.argv
@@ -102,7 +112,114 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if GRAMMAR:
+    import random
+    from macaw_llm_amd import ops
+    from macaw_llm_amd.grammar import TokenDFA
+    V = model.llm.lm_head.weight.shape[0]
+    JSON = r'\{"name": "[a-z ]{1,12}", "n": (0|[1-9]\d?)\}'
+    rnd = random.Random(7)
+    vocab = [None] * 3 + [bytes([i]) for i in range(256)]
+    vocab += [bytes(rnd.choice(b'{}":, name0123456789abcxyz.-') for _ in range(rnd.randint(2, 17))) for _ in range(V - len(vocab))]
+    free = TokenDFA.from_edges(1, [(0, t, 0) for t in range(V)], [0], vocab_size=V)
+    json_g = TokenDFA.from_regex(JSON, vocab)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+
+    def timed(fn, n=1):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(n):
+            out = fn()
+        torch.cuda.synchronize()
+        return out, (time.perf_counter() - t0) / n
+
+    # the making of a table: the byte walk on the device and the trim, first call (kernel load) and a fresh object after it
+    for name, make in (("35-state JSON", lambda: TokenDFA.from_regex(JSON, vocab)),
+                       ("[a-z ]{1,3000}", lambda: TokenDFA.from_regex("[a-z ]{1,3000}", vocab))):
+        t0 = time.perf_counter(); g = make(); host = time.perf_counter() - t0
+        times = []
+        for _ in range(3):
+            g = make()
+            (tab, _s), t = timed(lambda: g.table(dev))
+            times.append(t * 1e3)
+        cn = torch.from_numpy(g.char_next).to(dev)
+        tb, to = torch.from_numpy(g._tok_bytes.copy()).to(dev), torch.from_numpy(g._tok_off).to(dev)
+        _, tk = timed(lambda: ops.grammar_build(cn, tb, to), 5)
+        print(f"table {name}: {g.n_states} states x {V} tokens = {g.n_states * V * 4 / 2 ** 20:.1f} MiB; host compile "
+              f"{host * 1e3:.1f} ms; TokenDFA.table (upload + mk_grammar_build + trim + flags) {times[0]:.1f} ms the first time, "
+              f"{med(times[1:]):.1f} ms after; the mk_grammar_build launch with its allocation alone {tk * 1e3:.2f} ms", flush=True)
+        del tab, g
+    ARMS = {"greedy": None, "free": free, "json": json_g}
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms, msW = {a: [] for a in ("greedy", "free")}, {a: [] for a in ("greedy", "json")}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            gen = lambda arm, new: model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, pad_token_id=0, grammar=ARMS[arm])  # noqa: E731
+            rows = gen("json", 72)
+            W = rows.shape[1]
+            LO = 8 if W > 16 else 3                 # the shorter call, whose prefill and first steps the difference cancels
+            texts = [b"".join(vocab[t] for t in (r[:r.index(0)] if 0 in r else r)) for r in rows.tolist()]
+            print(f"B={B:2d}: the json arm ends by itself after W = {W} tokens; row 0 says {texts[0]!r}", flush=True)
+            assert torch.equal(gen("free", 72), gen("greedy", 72)), "the free grammar changed the ids"
+            # free against greedy over 72 tokens, as the other -ab arms; json against greedy over the json arm's own width
+            for rep in range(REPS):
+                for arm in ARMS:
+                    for book, lo, hi in ((ms, 8, 72), (msW, LO, W)):
+                        if arm not in book:
+                            continue
+                        t = {}
+                        for new in (lo, hi):
+                            ids, t[new] = timed(lambda: gen(arm, new))
+                            assert ids.shape[1] == new, f"{arm} stopped at {ids.shape[1]} of {new} tokens"
+                        book[arm].append((t[hi] - t[lo]) / (hi - lo) * 1e3)
+                        print(f"B={B:2d} rep {rep} {arm:6s}: decode {book[arm][-1]:6.3f} ms/token over {hi - lo} tokens", flush=True)
+        for arm, book in (("free", ms), ("json", msW)):
+            spread = max(book["greedy"]) - min(book["greedy"])
+            d = med(book[arm]) - med(book["greedy"])
+            print(f"B={B:2d}: greedy {med(book['greedy']):6.3f} ms/token, {arm} {med(book[arm]):6.3f} ms/token, {arm} - greedy = "
+                  f"{d * 1e3:+7.1f} us per token ({d / med(book['greedy']) * 100:+5.2f} %), greedy run-to-run spread "
+                  f"{spread * 1e3:6.1f} us: {'inside' if abs(d) <= spread else 'OUTSIDE'} the spread", flush=True)
+        # one launch by itself: 40 launches captured in a hipGraph (no host between them), replayed 4 times between two events
+        x = torch.randn(B, V, device=dev).mul_(3).to(torch.bfloat16)
+        tab_j, _ = json_g.table(dev)
+        tab_f, _ = free.table(dev)
+        out = torch.randint(3, V, (B, 256), generator=torch.Generator(device=dev).manual_seed(3), device=dev)
+        tok, done = torch.zeros(B, dtype=torch.long, device=dev), torch.zeros(B, dtype=torch.bool, device=dev)
+        out_e = torch.zeros((B, 256), dtype=torch.long, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        n_dev = torch.tensor([100], dtype=torch.int32, device=dev)
+        s_j = (torch.arange(B, dtype=torch.int32, device=dev) * 5) % json_g.n_states
+        s_f, end = torch.zeros(B, dtype=torch.int32, device=dev), torch.full((B,), -1, dtype=torch.int32, device=dev)
+        small = ops.SeqTable([[13, V + i] for i in range(3)] + [[V + 9]], dev)      # the neighbours: sequences that never fire
+        us = {}
+        for name, fn in (("decode_emit", lambda: ops.decode_emit(x, V, 0, -1, tok, done, out_e, st)),
+                         ("grammar_mask json", lambda: ops.grammar_mask(x, V, tab_j, s_j, done, -1)),
+                         ("grammar_mask free", lambda: ops.grammar_mask(x, V, tab_f, s_f, done, -1)),
+                         ("grammar_advance free", lambda: ops.grammar_advance(out, tab_f, s_f, done, end, n_dev)),
+                         ("seq_ban 4 seqs", lambda: ops.seq_ban(x, V, out, small, n_dev)),
+                         ("stop_match 4 seqs", lambda: ops.stop_match(out, small, done, n_dev))):
+            for i in range(5):
+                fn()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for i in range(40):
+                    fn()
+            graph.replay()
+            st.zero_()                              # (the emit's output column: 5 + 5 * 40 launches stay inside out_e's 256)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(4):
+                graph.replay()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 160 * 1e3
+            st.zero_()
+            del graph
+        assert not bool(done.any()) and s_f.tolist() == [0] * B
+        print(f"B={B:2d}: one launch on [B, {V}] bf16 logits, 40 in a hipGraph (device time incl. the gap between two graph nodes): " +
+              ", ".join(f"{k} {v:6.2f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if ADAPTERS:
     from macaw_llm_amd import lora
     llm = model.llm
