@@ -906,6 +906,43 @@ int mk_decode_step_attn_shared(const void* q, const void* k_new, const void* v_n
                                int64_t p_bs, void* kt, void* vt, int64_t t_ld, int64_t t_bs, void* o, int64_t o_bs,
                                const int32_t* t_dev, const int32_t* t_off, int32_t S0, int32_t Tn, int32_t B, int32_t n,
                                int32_t H, int32_t hd, float scale, int32_t dtype, void* stream);
+/* Scoring (LlamaForCausalLM.score): the log-likelihood of GIVEN answers over a shared prompt.  The rule, restated in
+ *   tests/score_ref.py:
+ *   There are B prompts; prompt b has L_b valid tokens and n_b <= n options.  Option (b, j) is a token list
+ *   c[0 ... len - 1], len >= 1, and its result is, for g = 0 ... len - 1,
+ *     lp[b, j, g] = log_softmax(logits of the model at position L_b + g - 1, given prompt b followed by c[0 ... g - 1])[c[g]]
+ *   over positions 0 ... L_b + len - 1: what a fresh call on the concatenation alone computes, and what
+ *   generate(return_logprobs=True) reports for a token it emitted itself.  Token 0 of every option of prompt b is predicted
+ *   by the prompt's last valid hidden row, computed once per prompt; token g >= 1 by the hidden row of FED token g - 1, so an
+ *   option feeds its first len - 1 tokens and the pass has F = (longest option) - 1 rows per option (F = 0: no pass at
+ *   all).  The arithmetic of a value is mk_token_logprobs' (fp64 log-sum-exp, one rounding).
+ * mk_score_attn: the attention of that pass, F teacher-forced rows per option over mk_decode_step_attn_shared's layout.
+ *   Row r = (b * n + j) * F + g of q / k_new / v_new (unrotated, row stride in_bs) and of o (row stride o_bs) is fed token g
+ *   of option (b, j).  Prompt cache kp / vp [B][S0][2D] (p_ld, p_bs), read only; L_b = clamp(S0 + (t_off ? t_off[b] : 0),
+ *   0, S0), t_off int32 [B] on the device or null.  Tail cache kt / vt [B * n][F][2D] (t_ld, t_bs).  len int32 [B * n] ON
+ *   THE DEVICE: option (b, j) feeds f = clamp(len[b * n + j], 0, F) rows; the host never reads it.
+ *     g < f (a live row): p = L_b + g; q and k_new are rotated with table row p (mk_rope's rounding points); the rotated
+ *       key and v_new go to tail row g of the option; o = attention of the rotated query over prompt rows 0 ... L_b - 1 of
+ *       prompt b followed by tail rows 0 ... g of the option.
+ *     g >= f (a dead row): o is exactly zero, tail row g is not written, and no byte of the row's q / k_new / v_new
+ *       influences anything.
+ *   No prompt byte is written, no prompt row >= L_b is read, and for row g no tail row > g is read.
+ *   Two kernels on the given stream inside the one call: a RoPE-and-append kernel for every live row (one lane group per
+ *   row and head, the step body's own rope8, so its bits), then one workgroup per (head, row) that runs
+ *   mk_decode_step_attn's kernel body in its shared-prompt form at the row's position WITHOUT the append -- the same key ->
+ *   lane map, trips, online softmax and merge order, only the address of a key differs -- while the tail rows 0 ... g - 1 it
+ *   reads are the ones the first kernel stored.  So a live row's output and appended key are BIT FOR BIT those of
+ *   mk_decode_step_attn called for the row alone (B = 1, the one-workgroup-per-head form) at *t_dev = p over a physically
+ *   gathered cache [prompt rows 0 ... L_b - 1 | tail rows 0 ... g - 1].  Any row count: grid.y carries at most 65535 rows
+ *   of a launch, and the attention kernel is launched as often as B * n * F needs.
+ *   Domain, else MK_ERR_UNSUPPORTED and nothing is launched: that of mk_decode_step_attn (dtype bf16 / f16; hd in {16, 32,
+ *   64, 128}; alignment and strides), len and t_off 4-byte aligned, H <= 65535.  n is not bounded here (score() allows 32).
+ *   MK_ERR_BAD_ARG: a null pointer (t_off excepted; kp / vp may be null when S0 == 0), B, n, H or F < 1, S0 < 0.
+ *   The tables must hold S0 + F rows (ops.score_attn checks).  Pinned by tests/test_score_attn_gpu.py. */
+int mk_score_attn(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                  const void* sin_t, const void* kp, const void* vp, int64_t p_ld, int64_t p_bs, void* kt, void* vt,
+                  int64_t t_ld, int64_t t_bs, void* o, int64_t o_bs, const int32_t* len, const int32_t* t_off, int32_t S0,
+                  int32_t F, int32_t B, int32_t n, int32_t H, int32_t hd, float scale, int32_t dtype, void* stream);
 int mk_kv_append(const void* src, void* cache, int32_t cols, int32_t batch, int64_t s_src,
                  int64_t s_cache, int64_t ld_cache, const int32_t* t_dev, int32_t t_max,
                  int32_t elem_size, void* stream);

@@ -13,6 +13,8 @@
 //                   indirection table: the prompt's keys once per sample, no cache row ever copied (beam.hip: the emit)
 //   mk_decode_step_attn_shared  the 16-bit step for n rows per sample over a prompt cache stored once per sample and a
 //                        tail cache per row (parallel sampling): the plain step body per row, a tile of rows per workgroup
+//   mk_score_attn   F teacher-forced rows per option over that layout (score()): a RoPE-and-append kernel for every live
+//                   row, then the plain step body per row without its append, at a position per row
 //   mk_decode_step_attn_multi  the 16-bit step for Q rows per sample at positions pos[b] ... pos[b] + Q - 1 (the verify
 //                   pass of prompt-lookup decoding, spec.hip): the plain step body, one workgroup per (head, sample, row)
 //   mk_kv_append_rows / mk_kv_quant_append_rows  the prefill's cache write of a padded batch: source row j of sample
@@ -119,6 +121,8 @@ __global__ __launch_bounds__(1024) void decode_emit_kernel(const T* logits, long
 #define decode_step_attn_multi_kernel decode_step_attn_multi_f16_kernel
 #define decode_step_attn4_kernel decode_step_attn4_f16_kernel
 #define decode_step_attn_shared_kernel decode_step_attn_shared_f16_kernel
+#define score_append_kernel score_append_f16_kernel
+#define score_attn_kernel score_attn_f16_kernel
 #define kv_quant_append_kernel kv_quant_append_f16_kernel
 #define decode_step_attn_kv8_kernel decode_step_attn_kv8_f16_kernel
 #include "decode_impl.inc"
@@ -128,6 +132,8 @@ __global__ __launch_bounds__(1024) void decode_emit_kernel(const T* logits, long
 #undef decode_step_attn_multi_kernel
 #undef decode_step_attn4_kernel
 #undef decode_step_attn_shared_kernel
+#undef score_append_kernel
+#undef score_attn_kernel
 #undef kv_quant_append_kernel
 #undef decode_step_attn_kv8_kernel
 #undef MK_E16_T
@@ -179,6 +185,15 @@ extern "C" int mk_decode_step_attn_shared(const void* q, const void* k_new, cons
                                           int32_t dtype, void* stream) {
   if (dtype == MK_F16) return e_f16::decode_step_attn_shared_impl(q, k_new, v_new, in_bs, cos_t, sin_t, kp, vp, p_ld, p_bs, kt, vt, t_ld, t_bs, o, o_bs, t_dev, t_off, S0, Tn, B, n, H, hd, scale, dtype, stream);
   return e_bf16::decode_step_attn_shared_impl(q, k_new, v_new, in_bs, cos_t, sin_t, kp, vp, p_ld, p_bs, kt, vt, t_ld, t_bs, o, o_bs, t_dev, t_off, S0, Tn, B, n, H, hd, scale, dtype, stream);
+}
+
+extern "C" int mk_score_attn(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t,
+                             const void* sin_t, const void* kp, const void* vp, int64_t p_ld, int64_t p_bs, void* kt,
+                             void* vt, int64_t t_ld, int64_t t_bs, void* o, int64_t o_bs, const int32_t* len,
+                             const int32_t* t_off, int32_t S0, int32_t F, int32_t B, int32_t n, int32_t H, int32_t hd,
+                             float scale, int32_t dtype, void* stream) {
+  if (dtype == MK_F16) return e_f16::score_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, kp, vp, p_ld, p_bs, kt, vt, t_ld, t_bs, o, o_bs, len, t_off, S0, F, B, n, H, hd, scale, dtype, stream);
+  return e_bf16::score_attn_impl(q, k_new, v_new, in_bs, cos_t, sin_t, kp, vp, p_ld, p_bs, kt, vt, t_ld, t_bs, o, o_bs, len, t_off, S0, F, B, n, H, hd, scale, dtype, stream);
 }
 
 extern "C" int mk_decode_step_attn_kv8_var(const void* q, const void* k_new, const void* v_new, int64_t in_bs,

@@ -167,7 +167,9 @@ MK_DEV void rope8(const e16x8& xv, const e16x8& cv, const e16x8& sv, bool first,
 // SHARED (mk_decode_step_attn_shared): b = the ROW, whose slot of a.kc / a.vc is its tail cache, p0 = the prompt's length:
 // key t < p0 is row t of the prompt cache of sample b / a.n, key p0 <= t < p tail row t - p0, and the new key goes to tail
 // row p - p0.  Only the address of a key differs.
-template <int HD, int NWV, bool BEAM, bool MULTI = false, bool SHARED = false, typename A>
+// APPEND = false (mk_score_attn): the row's rotated key and value are already in the tail cache (score_append_kernel wrote
+// them, the same rope8 bits) and the body stores nothing but o; key p still comes from registers.
+template <int HD, int NWV, bool BEAM, bool MULTI = false, bool SHARED = false, bool APPEND = true, typename A>
 MK_DEV void decode_step_attn_body(const A& a, float (*red)[HD], float* redw, int h, int b, long in_row, long o_row, int p,
                                   int p0 = 0, const e16 (*knew)[HD] = nullptr, long vn0 = 0) {
   constexpr int LPK = HD / 8, KPW = 64 / LPK, KPP = NWV * KPW;
@@ -187,14 +189,16 @@ MK_DEV void decode_step_attn_body(const A& a, float (*red)[HD], float* redw, int
     rope8<LPK>(qv, cv, sv, first, qf);
     rope8<LPK>(kv, cv, sv, first, kf);
   }
-  if (wave == 0 && grp == 0) {     // append the new key / value (cache row p)
-    e16x8 kb;
+  if constexpr (APPEND) {
+    if (wave == 0 && grp == 0) {   // append the new key / value (cache row p)
+      e16x8 kb;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) kb[e] = (e16)kf[e];
-    long off = (long)b * a.kv_bs + (long)p * a.kv_ld + (long)h * HD + d0;
-    if constexpr (SHARED) off = (long)b * a.kv_bs + (long)(p - p0) * a.kv_ld + (long)h * HD + d0;
-    *reinterpret_cast<e16x8*>(a.kc + off) = kb;
-    *reinterpret_cast<e16x8*>(a.vc + off) = vnew;
+      for (int e = 0; e < 8; ++e) kb[e] = (e16)kf[e];
+      long off = (long)b * a.kv_bs + (long)p * a.kv_ld + (long)h * HD + d0;
+      if constexpr (SHARED) off = (long)b * a.kv_bs + (long)(p - p0) * a.kv_ld + (long)h * HD + d0;
+      *reinterpret_cast<e16x8*>(a.kc + off) = kb;
+      *reinterpret_cast<e16x8*>(a.vc + off) = vnew;
+    }
   }
   const e16* K = a.kc + (long)b * a.kv_bs + (long)h * HD + d0;
   const e16* V = a.vc + (long)b * a.kv_bs + (long)h * HD + d0;
@@ -665,6 +669,126 @@ int decode_step_attn_shared_impl(const void* q, const void* k_new, const void* v
   else if (hd == 64) decode_step_attn_shared_launch<64>(a, B, H, st);
   else if (hd == 32) decode_step_attn_shared_launch<32>(a, B, H, st);
   else decode_step_attn_shared_launch<16>(a, B, H, st);
+  return mk_check_launch();
+}
+
+// SCORE (mk_score_attn): F teacher-forced rows per option over a prompt cache [B][S0] and a tail cache per option
+// [B * n][F].  Row r = (b * n + j) * F + g is fed token g of option (b, j), at position p = L_b + g; it is live while
+// g < f = clamp(len[b * n + j], 0, F).  Two kernels on one stream: score_append_kernel rotates every live row's key (rope8:
+// the body's own bits) and stores it with the value in tail row g; score_attn_kernel then runs the SHARED body per live row
+// WITHOUT its append, so that a row reads its earlier sisters' tail rows, which other workgroups of the first kernel wrote.
+struct ScoreArgs : DecodeStepSharedArgs {
+  const int32_t* len;                                       // [B * n] on the device: fed rows per option
+  int F;
+  long rows, row0;                                          // B * n * F; first row of this launch (score_attn_kernel)
+};
+
+// one lane group of LPK lanes per (row, head): thread i of the grid-stride loop holds 8 elements of unit i / LPK
+template <int HD>
+__global__ __launch_bounds__(256) void score_append_kernel(ScoreArgs a, int H) {
+  constexpr int LPK = HD / 8;
+  const int sub = threadIdx.x % LPK, d0 = sub * 8;
+  const long units = a.rows * H;
+  const long stride = (long)gridDim.x * (256 / LPK);
+  // (units rounded up to the stride, so that all lanes of a wave make the same trips: the shuffles need every partner)
+  for (long u0 = (long)blockIdx.x * (256 / LPK); u0 < units; u0 += stride) {
+    const long u = u0 + threadIdx.x / LPK;
+    bool live = u < units;
+    long row = 0;
+    int h = 0, opt = 0, g = 0;
+    if (live) {
+      row = u / H; h = (int)(u % H);
+      opt = (int)(row / a.F); g = (int)(row % a.F);
+      live = g < min(max(a.len[opt], 0), a.F);
+    }
+    e16x8 kv, vv, cv, sv;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { kv[e] = (e16)0.f; vv[e] = (e16)0.f; cv[e] = (e16)0.f; sv[e] = (e16)0.f; }
+    if (live) {
+      const int b = opt / a.n;
+      const int L = (int)min(max((long)a.S0 + (a.t_off ? a.t_off[b] : 0), 0L), (long)a.S0);
+      const long in_off = row * a.in_bs + (long)h * HD + d0;
+      kv = *reinterpret_cast<const e16x8*>(a.kn + in_off);
+      vv = *reinterpret_cast<const e16x8*>(a.vn + in_off);
+      cv = *reinterpret_cast<const e16x8*>(a.cos_t + (long)(L + g) * HD + d0);
+      sv = *reinterpret_cast<const e16x8*>(a.sin_t + (long)(L + g) * HD + d0);
+    }
+    float kf[8];
+    rope8<LPK>(kv, cv, sv, d0 < HD / 2, kf);
+    if (live) {
+      e16x8 kb;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) kb[e] = (e16)kf[e];
+      const long off = (long)opt * a.kv_bs + (long)g * a.kv_ld + (long)h * HD + d0;
+      *reinterpret_cast<e16x8*>(a.kc + off) = kb;
+      *reinterpret_cast<e16x8*>(a.vc + off) = vv;
+    }
+  }
+}
+
+// one workgroup per (head, row); a dead row's output is zeros
+template <int HD, int NWV>
+__global__ __launch_bounds__(NWV * 64) void score_attn_kernel(ScoreArgs a) {
+  __shared__ float red[NWV][HD];
+  __shared__ float redw[2 * NWV];
+  const int h = blockIdx.x;
+  const long row = a.row0 + blockIdx.y;
+  const int opt = (int)(row / a.F), g = (int)(row % a.F);
+  if (g >= min(max(a.len[opt], 0), a.F)) {
+    if (threadIdx.x < HD) a.o[row * a.o_bs + (long)h * HD + threadIdx.x] = (e16)0.f;
+    return;
+  }
+  const int b = opt / a.n;
+  const int L = (int)min(max((long)a.S0 + (a.t_off ? a.t_off[b] : 0), 0L), (long)a.S0);
+  decode_step_attn_body<HD, NWV, false, false, true, false>(a, red, redw, h, opt, row * a.in_bs, row * a.o_bs, L + g, L);
+}
+
+template <int HD>
+void score_attn_launch(ScoreArgs a, int H, hipStream_t st) {
+  constexpr int UPB = 256 / (HD / 8);                       // (row, head) units per workgroup of the append
+  const long units = a.rows * H;
+  const long want = (units + UPB - 1) / UPB, blocks = want < (1L << 20) ? want : (1L << 20);
+  MK_LAUNCH((score_append_kernel<HD>), dim3((unsigned)blocks), dim3(256), 0, st, a, H);
+  // grid.y carries at most 65535 rows, and a launch at most 2^31 threads: the rows go in as many launches as that takes
+  long per = (1L << 22) / H;
+  per = per > 65535 ? 65535 : per < 1 ? 1 : per;
+  for (long r0 = 0; r0 < a.rows; r0 += per) {
+    a.row0 = r0;
+    const long nr = a.rows - r0 < per ? a.rows - r0 : per;
+    MK_LAUNCH((score_attn_kernel<HD, 8>), dim3(H, (unsigned)nr), dim3(512), 0, st, a);
+  }
+}
+
+// mk_score_attn: the shared entry point's checks over B * n * F rows
+int score_attn_impl(const void* q, const void* k_new, const void* v_new, int64_t in_bs, const void* cos_t, const void* sin_t,
+                    const void* kp, const void* vp, int64_t p_ld, int64_t p_bs, void* kt, void* vt, int64_t t_ld,
+                    int64_t t_bs, void* o, int64_t o_bs, const int32_t* len, const int32_t* t_off, int32_t S0, int32_t F,
+                    int32_t B, int32_t n, int32_t H, int32_t hd, float scale, int32_t dtype, void* stream) {
+  if (!q || !k_new || !v_new || !cos_t || !sin_t || !kt || !vt || !o || !len || B < 1 || H < 1 || n < 1 || F < 1 || S0 < 0 ||
+      (S0 > 0 && (!kp || !vp)))
+    return MK_ERR_BAD_ARG;
+  if (dtype != E16<e16>::dtype || (hd != 16 && hd != 32 && hd != 64 && hd != 128)) return MK_ERR_UNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_new) |
+                       reinterpret_cast<uintptr_t>(v_new) | reinterpret_cast<uintptr_t>(cos_t) |
+                       reinterpret_cast<uintptr_t>(sin_t) | reinterpret_cast<uintptr_t>(kp) |
+                       reinterpret_cast<uintptr_t>(vp) | reinterpret_cast<uintptr_t>(kt) | reinterpret_cast<uintptr_t>(vt);
+  if ((al & 15) || ((reinterpret_cast<uintptr_t>(len) | reinterpret_cast<uintptr_t>(t_off)) & 3) || (in_bs % 8) ||
+      (p_ld % 8) || (p_bs % 8) || (t_ld % 8) || (t_bs % 8) || H > 65535 || (int64_t)B * n > INT32_MAX ||
+      (int64_t)S0 + F > INT32_MAX)
+    return MK_ERR_UNSUPPORTED;
+  ScoreArgs a;
+  a.q = (const e16*)q; a.kn = (const e16*)k_new; a.vn = (const e16*)v_new; a.in_bs = in_bs;
+  a.cos_t = (const e16*)cos_t; a.sin_t = (const e16*)sin_t;
+  a.kp = (const e16*)kp; a.vp = (const e16*)vp; a.p_ld = p_ld; a.p_bs = p_bs;
+  a.kc = (e16*)kt; a.vc = (e16*)vt; a.kv_ld = t_ld; a.kv_bs = t_bs;
+  a.o = (e16*)o; a.o_bs = o_bs;
+  a.t_dev = nullptr; a.t_off = t_off; a.t_max = F; a.S0 = S0; a.Tn = F; a.n = n; a.scale = scale;
+  a.len = len; a.F = F; a.rows = (long)B * n * F; a.row0 = 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hd == 128) score_attn_launch<128>(a, H, st);
+  else if (hd == 64) score_attn_launch<64>(a, H, st);
+  else if (hd == 32) score_attn_launch<32>(a, H, st);
+  else score_attn_launch<16>(a, H, st);
   return mk_check_launch();
 }
 

@@ -1088,6 +1088,114 @@ def llama_layer_cached(x2, B, Sn, t0, kvc, Tmax, pos, cos, sin, n_heads, eps, wq
     return out
 
 
+class ScoreLayout(NamedTuple):
+    """the options of LlamaForCausalLM.score() as the scoring pass takes them (score_layout): B prompts, n options each,
+    Lc = the longest option, F = Lc - 1 fed rows per option"""
+    fed: torch.Tensor        # int64 [B * n * F]: row (b * n + j) * F + g feeds token g of option (b, j); a dead row feeds id 0
+    lens: torch.Tensor       # int32 [B * n]: the fed rows of each option, max(length - 1, 0): mk_score_attn's len
+    targets: torch.Tensor    # int64 [B, n, Lc]: the scored ids, 0 behind each option's end
+    lengths: torch.Tensor    # int64 [B, n]: tokens per option, 0 = absent
+    n: int
+    F: int
+    Lc: int
+
+
+SCORE_MAX_N = 32
+
+
+def score_layout(continuations=None, continuation_ids=None, continuation_lengths=None, B=None, V=None):
+    """The host side of LlamaForCausalLM.score(): pure, and for the list form on the CPU.
+    continuations: a list of B lists of token-id lists (prompt b's options; prompts may have different counts, absent ones
+    are padded to n = the largest count; options may have different lengths >= 1), or continuation_ids int64 [B, n, Lc]
+    with continuation_lengths [B, n] (0 = absent; any device, no value of either is read on the host: lengths are clamped
+    into [0, Lc] and, with V, the ids fed into [0, V - 1] by tensor operations).  Exactly one form.  Option (b, j) feeds
+    its first length - 1 tokens: F = Lc - 1 rows per option, the rows behind an option's own feed id 0.
+    ValueError: both or neither form, a batch other than B (where B is given), n > 32, and in list form a prompt without
+    options, an empty option and (with V) an id outside [0, V)."""
+    if (continuations is None) == (continuation_ids is None):
+        raise ValueError("score: pass exactly one of continuations (lists) and continuation_ids (a tensor), got "
+                         f"{'both' if continuations is not None else 'neither'}")
+    if continuations is not None:
+        if continuation_lengths is not None:
+            raise ValueError("score: continuation_lengths goes with continuation_ids, not with continuations")
+        opts = [[[int(t) for t in o] for o in p] for p in continuations]
+        if B is not None and len(opts) != B:
+            raise ValueError(f"score: {len(opts)} lists of continuations for a batch of {B} prompts")
+        if not opts or any(len(p) == 0 for p in opts):
+            raise ValueError("score: every prompt needs at least one continuation")
+        empty = [(b, j) for b, p in enumerate(opts) for j, o in enumerate(p) if len(o) == 0]
+        if empty:
+            raise ValueError(f"score: empty continuation(s) at (prompt, option) {empty}: an option has at least one token")
+        if V is not None:
+            bad = sorted({t for p in opts for o in p for t in o if not 0 <= t < V})
+            if bad:
+                raise ValueError(f"score: token id(s) {bad[:8]} outside [0, {V})")
+        n, Lc = max(len(p) for p in opts), max(len(o) for p in opts for o in p)
+        if n > SCORE_MAX_N:
+            raise ValueError(f"score: {n} continuations for one prompt; at most {SCORE_MAX_N}")
+        ids = torch.zeros((len(opts), n, Lc), dtype=torch.int64)
+        lengths = torch.zeros((len(opts), n), dtype=torch.int64)
+        for b, p in enumerate(opts):
+            for j, o in enumerate(p):
+                ids[b, j, :len(o)] = torch.tensor(o, dtype=torch.int64)
+                lengths[b, j] = len(o)
+    else:
+        ids, lengths = continuation_ids, continuation_lengths
+        if lengths is None:
+            raise ValueError("score: continuation_ids needs continuation_lengths [B, n]")
+        if ids.dim() != 3 or ids.dtype != torch.int64 or ids.shape[2] < 1:
+            raise ValueError(f"score: continuation_ids should be int64 [B, n, Lc >= 1], but is {ids.dtype} {tuple(ids.shape)}")
+        if tuple(lengths.shape) != tuple(ids.shape[:2]) or lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"score: continuation_lengths should be an integer tensor {tuple(ids.shape[:2])}, but is "
+                             f"{lengths.dtype} {tuple(lengths.shape)}")
+        if B is not None and ids.shape[0] != B:
+            raise ValueError(f"score: continuation_ids for {ids.shape[0]} prompts and a batch of {B}")
+        if ids.shape[1] < 1 or ids.shape[1] > SCORE_MAX_N:
+            raise ValueError(f"score: {ids.shape[1]} continuations per prompt; between 1 and {SCORE_MAX_N}")
+        n, Lc = ids.shape[1], ids.shape[2]
+        lengths = lengths.to(device=ids.device, dtype=torch.int64).clamp(0, Lc)
+    F = Lc - 1
+    col = torch.arange(Lc, device=ids.device)
+    targets = torch.where(col < lengths[..., None], ids, torch.zeros_like(ids)).contiguous()
+    fed = torch.where(col[:F] < lengths[..., None] - 1, ids[..., :F], torch.zeros_like(ids[..., :F]))
+    if V is not None:
+        fed = fed.clamp(0, V - 1)
+    lens = (lengths - 1).clamp(0, F).to(torch.int32).reshape(-1).contiguous()
+    return ScoreLayout(fed.reshape(-1).contiguous(), lens, targets, lengths.contiguous(), n, F, Lc)
+
+
+def llama_layer_score(x2, B, sp, lens, t_off, cos, sin, n_heads, eps, ws, ln1, ln2):
+    """No-grad decoder layer over the B * sp.n * F FED rows of a scoring pass (score_layout; F = sp.tail.shape[1]): row
+    (b * n + j) * F + g is fed token g of option j of prompt b.  A GEMM pass, not a weight stream: the four linears go
+    through ops.linear_fwd, RMSNorm and SwiGLU are the prefill's, and the attention is ops.score_attn over sp (a
+    SharedPrompt: the prompt cache the prefill wrote at B rows, and the layer's tail cache, which this call fills).  lens
+    int32 [B * n] on the device: the fed rows of each option; t_off: Ragged.t_off of a padded batch or None.  ws: the
+    layer's LayerWeights (the merged copies under a live adapter).  The rows of dead positions carry zeros out of the
+    attention and whatever the linears make of them; nothing reads them."""
+    M, D = x2.shape
+    H, hd = n_heads, D // n_heads
+    F = sp.tail.shape[1]
+    if M != B * sp.n * F:
+        raise ValueError(f"llama_layer_score: {M} rows for B * n * F = {B} * {sp.n} * {F}")
+    FF = ws.wg.shape[0]
+    att = torch.empty((M, D), dtype=x2.dtype, device=x2.device)
+    _, y1, _ = ops.rmsnorm_fwd(x2, ln1, eps)
+    if ws.wqkv is not None:
+        qkv = ops.linear_fwd(y1, ws.wqkv)
+        ops.score_attn(qkv, qkv, qkv, 3 * D, cos, sin, sp.prompt, sp.tail, lens, t_off, sp.S0, B, sp.n, H, hd, att,
+                       1.0 / math.sqrt(hd), k_off=D, v_off=2 * D)
+    else:
+        q, k, v = ops.linear_fwd(y1, ws.wq), ops.linear_fwd(y1, ws.wk), ops.linear_fwd(y1, ws.wv)
+        ops.score_attn(q, k, v, D, cos, sin, sp.prompt, sp.tail, lens, t_off, sp.S0, B, sp.n, H, hd, att, 1.0 / math.sqrt(hd))
+    h1 = ops.linear_fwd(att, ws.wo, residual=x2)
+    _, y2, _ = ops.rmsnorm_fwd(h1, ln2, eps)
+    if ws.wgu is not None:
+        a = ops.swiglu2d_fwd(ops.linear_fwd(y2, ws.wgu), FF)
+    else:
+        a = ops.swiglu_fwd(ops.linear_fwd(y2, ws.wg), ops.linear_fwd(y2, ws.wu))
+    return ops.linear_fwd(a, ws.wd, residual=h1)
+
+
 # =========================================================================
 # final norm + lm_head + shifted cross-entropy  (modeling.py:508,597-610)
 # =========================================================================

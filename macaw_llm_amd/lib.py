@@ -145,6 +145,8 @@ SIGNATURES = {
                                  _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "mk_decode_step_attn_shared": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp,
                                    _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
+    "mk_score_attn": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i32,
+                      _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "mk_spec_lookup": [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _vp],
     "mk_spec_verify_emit": [_vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32,
                             _vp],

@@ -87,6 +87,11 @@ GRAMMAR = [None]
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
 GenerateLogprobs = collections.namedtuple("GenerateLogprobs", ["ids", "logprobs", "top_ids", "top_logprobs"])
+# what LlamaForCausalLM.score returns
+ScoreResult = collections.namedtuple("ScoreResult", ["token_logprobs", "lengths", "sums", "top_ids", "top_logprobs"])
+# rows x vocabulary elements of one logits buffer of score(): the fed rows go through the final norm and the lm_head in
+# chunks of max(1, SCORE_LOGITS_ELEMS // V) rows (2^26 elements = 128 MiB in 16 bits: 2097 rows at V = 32000)
+SCORE_LOGITS_ELEMS = 1 << 26
 
 
 from .beam import beam_check, beam_result  # noqa: E402
@@ -1853,6 +1858,206 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         res = with_logprobs(torch.stack(out, dim=1))
         return hand_over(res) if sess else res
 
+    @torch.no_grad()
+    def score(self, inputs_embeds=None, input_ids=None, continuations=None, continuation_ids=None,
+              continuation_lengths=None, attention_mask=None, top_logprobs=0, use_cache=True):
+        """The log-likelihood of GIVEN answers over a shared prompt (lm-eval's loglikelihood, OpenAI / vLLM echo +
+        logprobs over the answer): what multiple-choice evaluation, re-ranking and perplexity of a reference need.
+
+        The rule (include/macaw_hip.h, "Scoring"; tests/score_ref.py).  B prompts; prompt b has L_b valid tokens and
+        n_b <= n options; option (b, j) is a token list c[0 ... len - 1], len >= 1, and for g = 0 ... len - 1
+            lp[b, j, g] = log_softmax(logits at position L_b + g - 1, given prompt b followed by c[0 ... g - 1])[c[g]]
+        -- what a fresh call on the concatenation alone computes, and what generate(return_logprobs=True) reports for a
+        token it emitted itself.  A value's arithmetic is ops.token_logprobs' (fp64 log-sum-exp, one rounding).
+
+        The prompt (inputs_embeds [B, S0, D] or input_ids [B, S0]) and attention_mask mean what they mean to generate():
+        any padding pattern, L_b the valid tokens of sample b.  The options come as
+          continuations         a list of B lists of token-id lists: prompts may have different option counts (absent
+                                options are padded to n = the largest), options different lengths; or
+          continuation_ids      int64 [B, n, Lc] with continuation_lengths [B, n] (0 = absent), on the device: no value
+                                of either is read on the host (lengths are clamped into [0, Lc]; a fed id is clamped
+                                into [0, V), a scored id outside it gives NaN) -- the form in which the output of
+                                generate(num_samples=n) is re-ranked.
+        Returns ScoreResult(token_logprobs f32 [B, n, Lc] (0.0 behind each option's end), lengths int64 [B, n], sums f32
+        [B, n] (the fp64 sum in column order, one rounding; -inf for an absent option), top_ids, top_logprobs): with
+        top_logprobs = m in [1, 20] the m most likely ids of every scored position, int64 [B, n, Lc, m] (-1 behind the
+        end), and their values f32 (0.0 behind the end); otherwise both None.
+
+        use_cache=True.  (1) The prefill runs ONCE per prompt at B rows into a [B, S0, 2D] prompt cache per layer -- the
+        launches of generate(num_samples=)'s prefill, a padded batch's compacted cache included.  (2) The prompt's last
+        valid hidden row gives, through the final norm and the lm_head at B rows, token 0 of every option.  (3) Token
+        g >= 1 is predicted by the hidden row of FED token g - 1: the B * n * F fed rows, F = Lc - 1, go through the
+        layers as one GEMM pass (engine.llama_layer_score: ops.linear_fwd, and ops.score_attn over the prompt cache and
+        a tail cache per option, at a position per row, dead rows masked on the device); with F = 0 no pass runs.  (4)
+        Final norm and lm_head over the fed rows in chunks of SCORE_LOGITS_ELEMS // V rows.  (5) ops.token_logprobs.
+        use_cache=False: the reference path and the fallback, every dtype: the B * n concatenations [prompt | option]
+        as one padded batch through the ordinary forward under the mask, the prompt recomputed per option.
+
+        A live LoRA adapter (get_peft_model / load_lora) runs on the per-call merged copies, as in generate().  Not
+        built: prompt log-probabilities, an e4m3 cache or quantised weights, adapter_names, sessions.
+
+        ValueError, naming the condition, before anything is allocated: both or neither of inputs_embeds / input_ids;
+        both or neither continuation form; a batch size other than B; a prompt without options or an empty option (list
+        form); a token id outside [0, V) (list form); n > 32; top_logprobs outside [0, 20]; L_b + len beyond the rotary
+        table (max_position_embeddings; the tensor form counts Lc for len); an attention_mask of another shape or a
+        sample without a valid token; and with use_cache=True fp32 parameters or a shape outside ops.score_attn_ok
+        ("use use_cache=False")."""
+        if (inputs_embeds is None) == (input_ids is None):
+            raise ValueError("score: pass exactly one of inputs_embeds and input_ids")
+        src = inputs_embeds if inputs_embeds is not None else input_ids
+        if src.dim() != (3 if inputs_embeds is not None else 2) or src.shape[1] < 1:
+            raise ValueError(f"score: the prompt should be inputs_embeds [B, S0, D] or input_ids [B, S0] with S0 >= 1, but is "
+                             f"{tuple(src.shape)}")
+        B, S0 = src.shape[:2]
+        dev = src.device
+        if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, numbers.Integral) or \
+                not 0 <= top_logprobs <= ops.MAX_TOP_LOGPROBS:
+            raise ValueError(f"score: top_logprobs must be an integer in [0, {ops.MAX_TOP_LOGPROBS}], got {top_logprobs!r}")
+        m = int(top_logprobs)
+        emb_w = self.model.embed_tokens.weight
+        V, D = self.lm_head.weight.shape[0], emb_w.shape[1]
+        lay = eng.score_layout(continuations, continuation_ids, continuation_lengths, B=B, V=V)
+        n, F, Lc = lay.n, lay.F, lay.Lc
+        ragged = rg_pos = rg_last = None
+        n_valid = [S0] * B
+        if attention_mask is not None:
+            padded = eng.ragged_from_mask(attention_mask.to(dev), B, S0)        # None for a mask without a zero
+            if padded is not None:
+                ragged, rg_pos, rg_last = padded
+                n_valid = (ragged.t_off + S0).tolist()
+        # the longest option per prompt: its own in list form (the layout is on the host), Lc in tensor form
+        longest = lay.lengths.max(1).values.tolist() if continuations is not None else [Lc] * B
+        table = self.config.max_position_embeddings
+        over = [b for b in range(B) if n_valid[b] + longest[b] > table]
+        if over:
+            raise ValueError(f"score: prompt(s) {over}: L_b + len = {[n_valid[b] + longest[b] for b in over]} positions are "
+                             f"beyond the rotary table (max_position_embeddings = {table})")
+        layers = self.model.layers
+        H = layers[0].self_attn.num_heads
+        hd, dtype = D // H, emb_w.dtype
+        if use_cache:
+            why = None
+            if dtype not in _16BIT:
+                why = f"fp32 parameters ({dtype}): the scoring attention takes bf16 / fp16"
+            elif not ops.score_attn_ok(dtype, hd, H):
+                why = f"ops.score_attn_ok is false for head size {hd} and {H} heads"
+            if why is not None:
+                raise ValueError(f"score with use_cache=True: {why}; use use_cache=False")
+
+        _dev_check(src)
+        if inputs_embeds is None:
+            inputs_embeds = ops.embedding_fwd(emb_w, input_ids.long().reshape(-1)).view(B, S0, D)
+        fed = lay.fed.to(dev)
+        lens = lay.lens.to(dev)
+        targets, lengths = lay.targets.to(dev), lay.lengths.to(dev)
+        eps = self.model.norm.variance_epsilon
+        R = B * n
+        own = torch.arange(B, device=dev).repeat_interleave(n)          # the prompt of option row r
+
+        def logprobs(h_rows, ids):    # hidden rows [M, D] -> token_logprobs of ids [M], the logits a bounded chunk at a time
+            step = max(1, SCORE_LOGITS_ELEMS // V)
+            outs = []
+            for r0 in range(0, h_rows.shape[0], step):
+                _, y, _ = ops.rmsnorm_fwd(h_rows[r0:r0 + step], self.model.norm.weight, eps)
+                outs.append(ops.token_logprobs(ops.linear_fwd(y, self.lm_head.weight), V, ids[r0:r0 + step].contiguous(), m))
+            if len(outs) == 1:
+                return outs[0]
+            return tuple(torch.cat(c) if m or i == 0 else None for i, c in enumerate(zip(*outs)))
+
+        if not use_cache:
+            # [prompt | fed tokens] per option, a padded batch: the prompt's mask, then ones over the option's own fed rows
+            emb = inputs_embeds.repeat_interleave(n, 0)
+            valid = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones((B, S0), dtype=torch.bool,
+                                                                                                 device=dev)
+            col = torch.arange(S0, device=dev)
+            last = torch.where(valid, col, torch.full_like(col, -1)).max(1).values           # [B]: the last valid prompt row
+            mask = None
+            if F:
+                emb = torch.cat([emb, ops.embedding_fwd(emb_w, fed).view(R, F, D)], dim=1)
+            if F or attention_mask is not None:
+                live = torch.arange(F, device=dev) < lens[:, None]                           # [R, F]
+                mask = torch.cat([valid.repeat_interleave(n, 0), live], dim=1).to(torch.int32)
+            S = S0 + F
+            self.model._defer_final_norm = True
+            try:
+                if mask is not None:
+                    h = self.model(inputs_embeds=emb.contiguous(), attention_mask=mask,
+                                   position_ids=(mask.cumsum(1) - 1).clamp_(min=0))
+                else:
+                    h = self.model(inputs_embeds=emb.contiguous())
+            finally:
+                self.model._defer_final_norm = False
+            # the row that predicts token g of option r: the prompt's last valid row for g = 0, fed row g - 1 behind it
+            rows = torch.arange(R, device=dev)[:, None] * S + torch.cat(
+                [last[own][:, None], S0 + torch.arange(F, device=dev).expand(R, F)], dim=1)
+            lp, ti, tl = logprobs(ops.embedding_fwd(h.contiguous().view(R * S, D), rows.reshape(-1).contiguous()),
+                                  targets.reshape(-1))
+            lp = lp.view(B, n, Lc)
+            if m:
+                ti, tl = ti.view(B, n, Lc, m), tl.view(B, n, Lc, m)
+        else:
+            rot = layers[0].self_attn.rotary_emb
+            cos, sin = rot.tables(S0 + Lc, dtype, dev)
+            if getattr(self, "_lora", None) is not None:      # the per-call merged copies, as in generate()
+                from .lora import lora_layers, merged_layer_weights
+                merged = dict(merged_layer_weights(self, lyr) for _, lyr in lora_layers(self))
+            else:
+                merged = {}
+            weights = []
+            for lyr in layers:
+                a, mlp = lyr.self_attn, lyr.mlp
+                weights.append(merged.get(lyr) or eng.LayerWeights(
+                    a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, mlp.gate_proj.weight,
+                    mlp.up_proj.weight, mlp.down_proj.weight, *lyr.fused_weights()))
+            # (1) the prefill, once per prompt at B rows: generate(num_samples=)'s launches
+            kvc = [torch.empty((B, S0, 2 * D), dtype=dtype, device=dev) for _ in layers]
+            pos = rg_pos if ragged is not None else torch.arange(S0, dtype=torch.int32, device=dev).repeat(B)
+            x2 = eng._c2(inputs_embeds, B * S0, D)
+            for i, lyr in enumerate(layers):
+                ws = weights[i]
+                x2 = eng.llama_layer_cached(
+                    x2, B, S0, 0, kvc[i], S0, pos, cos, sin, lyr.self_attn.num_heads, lyr.input_layernorm.variance_epsilon,
+                    ws.wq, ws.wk, ws.wv, ws.wo, ws.wg, ws.wu, ws.wd, lyr.input_layernorm.weight,
+                    lyr.post_attention_layernorm.weight, ws.wqkv, ws.wgu, ragged=ragged)
+            # (2) the last valid hidden row of every prompt -> token 0 of each of its options
+            if ragged is not None:
+                h_last = ops.embedding_fwd(x2.view(B * S0, D), rg_last)
+            else:
+                h_last = torch.empty((B, D), dtype=dtype, device=dev)
+                ops.copy2d(x2, h_last, 1, D, D, D, batch=B, s_src=S0 * D, s_dst=D, src_off=(S0 - 1) * D)
+            _, y0, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
+            z0 = ops.embedding_fwd(ops.linear_fwd(y0, self.lm_head.weight)[:, :V].contiguous(), own)      # [R, V]
+            lp, ti, tl = ops.token_logprobs(z0, V, targets[:, :, 0].reshape(-1).contiguous(), m)
+            lp = lp.view(B, n, 1)
+            if m:
+                ti, tl = ti.view(B, n, 1, m), tl.view(B, n, 1, m)
+            if F:
+                # (3) the fed rows, one GEMM pass; the tail cache serves one layer at a time
+                tail = torch.empty((R, F, 2 * D), dtype=dtype, device=dev)
+                t_off = ragged.t_off if ragged is not None else None
+                x = ops.embedding_fwd(emb_w, fed)
+                for i, lyr in enumerate(layers):
+                    x = eng.llama_layer_score(x, B, eng.SharedPrompt(kvc[i], tail, n, S0), lens, t_off, cos, sin,
+                                              lyr.self_attn.num_heads, lyr.input_layernorm.variance_epsilon, weights[i],
+                                              lyr.input_layernorm.weight, lyr.post_attention_layernorm.weight)
+                # (4), (5): fed row (r, g) predicts token g + 1
+                lp_f, ti_f, tl_f = logprobs(x, targets[:, :, 1:].reshape(-1))
+                lp = torch.cat([lp, lp_f.view(B, n, F)], dim=2)
+                if m:
+                    ti, tl = torch.cat([ti, ti_f.view(B, n, F, m)], dim=2), torch.cat([tl, tl_f.view(B, n, F, m)], dim=2)
+        # behind each option's end: 0.0 / -1 / 0.0, masked on the device
+        end = torch.arange(Lc, device=dev) >= lengths[..., None]                             # [B, n, Lc]
+        lp = torch.where(end, torch.zeros_like(lp), lp)
+        total = torch.zeros((B, n), dtype=torch.float64, device=dev)
+        for g in range(Lc):           # the fp64 sum in column order
+            total = total + lp[:, :, g].double()
+        sums = torch.where(lengths == 0, torch.full_like(total, float("-inf")), total).float()
+        if m:
+            ti = torch.where(end[..., None], torch.full_like(ti, -1), ti)
+            tl = torch.where(end[..., None], torch.zeros_like(tl), tl)
+            return ScoreResult(lp, lengths, sums, ti, tl)
+        return ScoreResult(lp, lengths, sums, None, None)
+
 
 # ---------------------------------------------------------- multimodal ------
 class MM_LLMs_Config(PretrainedConfig):
@@ -2066,6 +2271,17 @@ class MM_LLMs(PreTrainedModel):
                                      attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
                                      **turn, **guide, **stopping, **par, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
+
+    @torch.no_grad()
+    def score(self, inputs, continuations=None, **kw):
+        """LlamaForCausalLM.score of given answers over the multimodal prompt of `inputs` (forward's dict): the towers and
+        the alignment attention run ONCE per prompt (prepare_inputs_for_generation), then llm.score on the embeddings
+        with the options of `continuations` (or continuation_ids / continuation_lengths and the other arguments of
+        llm.score in kw).  The extended mask is passed under the same switch as inference (set_generate_mask)."""
+        _dtype_check(self._param_dtype())
+        text_embeddings, attention_mask, _ = self.prepare_inputs_for_generation(inputs)
+        return self.llm.score(inputs_embeds=text_embeddings, continuations=continuations,
+                              attention_mask=attention_mask if GENERATE_MASK[0] else None, **kw)
 
     @staticmethod
     def set_fp8(qkv: bool = True, align: bool = True, mlp: bool = False):

@@ -1107,6 +1107,47 @@ def decode_step_attn_shared(q, k_new, v_new, in_bs, cos_t, sin_t, prompt, tail, 
     return out
 
 
+def score_attn_ok(dtype, hd, H=1):
+    """mk_score_attn's domain: bf16 / fp16, hd in {16, 32, 64, 128}, at most 65535 heads.  The kernel keeps no per-key
+    buffer in LDS and splits its rows over as many launches as they need, so neither the prompt's length, the options'
+    length nor their number bounds it"""
+    return dtype in (torch.bfloat16, torch.float16) and hd in (16, 32, 64, 128) and 1 <= H <= 65535
+
+
+def score_attn(q, k_new, v_new, in_bs, cos_t, sin_t, prompt, tail, lens, t_off, S0, B, n, H, hd, out, scale,
+               q_off=0, k_off=0, v_off=0):
+    """the attention of a scoring pass (see mk_score_attn): row (b * n + j) * F + g is fed token g of option j of prompt
+    b, F = tail.shape[1].  prompt [B, S0, 2 * H * hd] holds each prompt's keys and values once (read only; t_off int32
+    [B] on the device = engine.Ragged.t_off, or None), tail [B * n, F, 2 * H * hd] receives the options' own rows, lens
+    int32 [B * n] on the device the fed rows of each option.  With L_b = clamp(S0 + t_off[b], 0, S0) a live row
+    (g < clamp(lens, 0, F)) runs at position L_b + g: RoPE, tail row g, attention over prompt rows 0 ... L_b - 1 and tail
+    rows 0 ... g; a dead row's output is zeros and nothing of it is read or stored.  out [B * n * F, H * hd].
+    Bit-identical per live row to decode_step_attn on a physically gathered cache"""
+    lib = _L.load()
+    es = q.element_size()
+    D = H * hd
+    if prompt.dtype != q.dtype or tuple(prompt.shape) != (B, S0, 2 * D) or not prompt.is_contiguous():
+        raise MacawHipError(f"score_attn: prompt {prompt.dtype} {tuple(prompt.shape)}; expected {q.dtype} "
+                            f"{(B, S0, 2 * D)}, contiguous")
+    if (tail.dtype != q.dtype or tail.dim() != 3 or tail.shape[0] != B * n or tail.shape[1] < 1 or tail.shape[2] != 2 * D
+            or not tail.is_contiguous()):
+        raise MacawHipError(f"score_attn: tail {tail.dtype} {tuple(tail.shape)}; expected {q.dtype} "
+                            f"[{B * n}, F >= 1, {2 * D}], contiguous")
+    F = tail.shape[1]
+    _i32_check("score_attn", "lens", lens, B * n)
+    if t_off is not None:
+        _i32_check("score_attn", "t_off", t_off, B)
+    if out.shape[0] != B * n * F or q.shape[0] != B * n * F:
+        raise MacawHipError(f"score_attn: {q.shape[0]} input and {out.shape[0]} output rows for B * n * F = {B * n * F}")
+    if cos_t.shape[0] < S0 + F or sin_t.shape[0] < S0 + F:
+        raise MacawHipError(f"score_attn: {cos_t.shape[0]} table rows for positions up to {S0 + F - 1}")
+    _L.check(lib.mk_score_attn(_p(q) + q_off * es, _p(k_new) + k_off * es, _p(v_new) + v_off * es, in_bs, _p(cos_t),
+                               _p(sin_t), _p(prompt) if S0 else None, _p(prompt) + D * es if S0 else None, 2 * D,
+                               S0 * 2 * D, _p(tail), _p(tail) + D * es, 2 * D, F * 2 * D, _p(out), _rowmajor(out), _p(lens),
+                               _p(t_off), S0, F, B, n, H, hd, scale, dt(q), _st()), "mk_score_attn")
+    return out
+
+
 class BeamState:
     """the device state of a beam search (include/macaw_hip.h, "State layout"): B samples, K beams, n_max columns"""
 

@@ -93,6 +93,14 @@ with torch.no_grad():
 # differences and the greedy run-to-run spread.  Then the time of one ops.grammar_mask and one ops.grammar_advance launch inside a
 # hipGraph against their neighbours ops.decode_emit, ops.seq_ban and ops.stop_match, and the making of a table (ops.grammar_build plus the trim) for (S, V) = (35, V) and for a pattern of 3001
 # states
+#        bench_generate.py --score-ab [--prompt-tokens N] [--reps R] [B ...]: score() of n = 4 given answers of 16 tokens per
+# prompt (default B = 1, 8).  Three arms alternated in this process on this model: "score" = score() (one prefill per prompt,
+# token 0 at B rows, then the B * n * 15 fed rows as one GEMM pass over the prompt cache: ops.score_attn); "recompute" =
+# score(use_cache=False), the prompt recomputed per option ([prompt | option] as a padded batch of B * n); "steps" = what
+# teacher-forced decode steps would cost: generate()'s ms per token at batch B * n ((72 - 8 tokens) / 64, greedy) x 16.  ms per
+# call of every run, the medians, each arm's run-to-run spread and the ratios; the towers and the alignment
+# (prepare_inputs_for_generation) run once per prompt outside every arm and are timed alone
+SCORE = "--score-ab" in sys.argv
 GRAMMAR = "--grammar-ab" in sys.argv
 ADAPTERS = "--adapters-ab" in sys.argv
 SESSION = "--session-ab" in sys.argv
@@ -112,7 +120,51 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if SCORE:
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    N_OPT, L_OPT = 4, 16
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, (time.perf_counter() - t0) * 1e3
+
+    V = model.llm.lm_head.weight.shape[0]
+    for B in [int(a) for a in _args] or [1, 8]:
+        inp = synthetic_inputs(cfg, B, PROMPT, modalities=("images", "audios"), seed=2, device=dev)
+        g = torch.Generator().manual_seed(4)
+        conts = [[torch.randint(3, V, (L_OPT,), generator=g).tolist() for _ in range(N_OPT)] for _ in range(B)]
+        with torch.no_grad():
+            emb, t_prep = timed(lambda: model.prepare_inputs_for_generation(inp)[0])
+            _, t_prep = timed(lambda: model.prepare_inputs_for_generation(inp)[0])
+            rep = emb.repeat_interleave(N_OPT, 0)
+            arms = {"score": lambda: model.llm.score(inputs_embeds=emb, continuations=conts),
+                    "recompute": lambda: model.llm.score(inputs_embeds=emb, continuations=conts, use_cache=False)}
+            a, b = arms["score"](), arms["recompute"]()          # warm-up, and the two paths agree to bf16 noise
+            print(f"B={B:2d} n={N_OPT} len={L_OPT} prompt rows {emb.shape[1]}: largest |score - recompute| over the token "
+                  f"log-probabilities {float((a.token_logprobs - b.token_logprobs).abs().max()):.3f}, over the sums "
+                  f"{float((a.sums - b.sums).abs().max()):.3f}; same argmax option for "
+                  f"{int((a.sums.argmax(1) == b.sums.argmax(1)).sum())} of {B} prompts", flush=True)
+            model.llm.generate(inputs_embeds=rep, max_new_tokens=8, eos_token_id=-1)
+            ms = {k: [] for k in ("score", "recompute", "steps")}
+            for r in range(REPS):
+                for k in ms:
+                    if k == "steps":
+                        t = {new: timed(lambda: model.llm.generate(inputs_embeds=rep, max_new_tokens=new, eos_token_id=-1))[1]
+                             for new in (8, 72)}
+                        ms[k].append((t[72] - t[8]) / 64 * L_OPT)
+                    else:
+                        ms[k].append(timed(arms[k])[1])
+                    print(f"B={B:2d} rep {r} {k:9s}: {ms[k][-1]:8.2f} ms", flush=True)
+        sp = {k: max(v) - min(v) for k, v in ms.items()}
+        print(f"B={B:2d} n={N_OPT} len={L_OPT} prompt rows {emb.shape[1]}: score {med(ms['score']):8.2f} ms (spread {sp['score']:.2f}), "
+              f"recompute {med(ms['recompute']):8.2f} ms (spread {sp['recompute']:.2f}), {L_OPT} teacher-forced steps at "
+              f"{B * N_OPT} rows {med(ms['steps']):8.2f} ms (spread {sp['steps']:.2f}); recompute / score = "
+              f"{med(ms['recompute']) / med(ms['score']):.2f}, steps / score = {med(ms['steps']) / med(ms['score']):.2f}; towers + "
+              f"alignment once per prompt {t_prep:.2f} ms (outside every arm)", flush=True)
+    sys.exit(0)
 if GRAMMAR:
     import random
     from macaw_llm_amd import ops
