@@ -462,6 +462,29 @@ int mk_decode_emit(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t
  *   Selection is an exact radix select; masses are 2^-40 fixed-point integers, so every sum is an integer sum and the
  *   result is bitwise reproducible.  bf16 / f16 / f32.  MK_ERR_BAD_ARG: null pointers, rows <= 0, V <= 0, ld < V,
  *   temperature <= 0 or not finite, top_p outside (0, 1], top_k < 0.  V <= 2^23, else MK_ERR_UNSUPPORTED.
+ *   6. The four warpers behind top-p (the _warp entries; HF's MinPLogitsWarper -> TypicalLogitsWarper ->
+ *      EpsilonLogitsWarper -> EtaLogitsWarper, min_tokens_to_keep = 1), between rule 3 and the draw of rule 4.  Every stage
+ *      works on the survivors of the stages before it, renormalised over them, and keeps at least one column.  With
+ *      x_max the largest value of the row (it survives rules 2-3), d_c = x_max - x_c, e_c = exp(-d_c) and Z the sum of e
+ *      over the current survivors:
+ *      min_p in [0, 1], 0 = off: c stays iff e_c >= min_p (e_c >= min_p * max e, and the maximum is a survivor).
+ *      typical_p in (0, 1], 1 = off: survivors whose fixed-point mass is 0 leave first (below V * 2^-40 in all, so a kept
+ *        set never has integer mass 0).  D = sum(e_c d_c) / Z, t_c = |d_c - D| (HF's |-log p_c - H|: the log Z terms
+ *        cancel); c stays iff the mass of the survivors with t strictly below t_c is below typical_p * Z -- rule 3 on
+ *        the key t, ascending: a tie group in t stays or goes whole, the column nearest to D always stays, and the kept
+ *        set is a band in d that may leave out the maximum.
+ *      epsilon_cutoff in [0, 1), 0 = off: c stays iff e_c / Z >= epsilon_cutoff; when no survivor passes, the survivors
+ *        of the largest value stay (a value floor: tie groups whole, as in HF).
+ *      eta_cutoff in [0, 1), 0 = off: the same with the threshold min(eta, sqrt(eta) * exp(-H)), H = log Z +
+ *        sum(e_c d_c) / Z the entropy of the renormalised survivors.
+ *      In the kernel: masses m_c = trunc(e_c * 2^40) as everywhere; Z, sum(trunc(m_c * d_c)) and the largest m_c are
+ *      integer reductions; the thresholds are integers (ceil(min_p * 2^40), ceil(typical_p * Z), ceil(threshold * Z)) and
+ *      the floors compare m_c against them; D (rounded once to fp32), H and the eta threshold are computed once per row in
+ *      fp64 from the integer sums; t_c is fp32 from the fp32 d_c and D, selected by the mass-weighted radix select of
+ *      rule 3.  The kept set is: rules 2-3's value prefix, and m_c >= one mass floor, and (typical on) t_c <= one band
+ *      edge.  The fall-back of the two cutoffs keeps the survivors of the largest MASS, which is the largest value
+ *      wherever two values differ in their fixed-point masses.  No difference to HF beyond rule 2's.
+ *      MK_ERR_BAD_ARG for a value outside these ranges or not finite.  All four off (0, 1, 0, 0): the entry without them.
  * mk_sample_rows: out_ids[row] = that token, the sampled twin of mk_argmax_rows.
  * mk_decode_emit_sample: mk_decode_emit with the argmax replaced by that draw for the samples not yet finished, row = b
  *   and step = state[1] (the output column, read on the device: a captured step draws a fresh number on every replay);
@@ -471,6 +494,20 @@ int mk_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, floa
 int mk_decode_emit_sample(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, int64_t eos,
                           int64_t* tok, void* done, int64_t* out, int64_t out_ld, int32_t* state, float temperature,
                           int32_t top_k, float top_p, uint64_t seed, int32_t dtype, void* stream);
+/* mk_sample_rows_warp, mk_decode_emit_sample_warp: the two entries above with rule 6's four values behind top_p.
+ * mk_sample_keep_rows: keep[row][c] (one byte, pitch keep_ld >= V) = 1 where the filter of rules 1-3 and 6 keeps column c,
+ *   0 elsewhere -- the set the draw of rule 4 lands in, from the same filter code; a row without a finite logit gets an
+ *   all-zero mask.  (A top-k survivor whose mass is 0 is kept and never drawn unless typical_p is on.) */
+int mk_sample_rows_warp(const void* logits, int64_t ld, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                        float top_p, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff, uint64_t seed,
+                        int32_t step, int64_t* out_ids, int32_t dtype, void* stream);
+int mk_decode_emit_sample_warp(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, int64_t eos,
+                               int64_t* tok, void* done, int64_t* out, int64_t out_ld, int32_t* state, float temperature,
+                               int32_t top_k, float top_p, float min_p, float typical_p, float epsilon_cutoff,
+                               float eta_cutoff, uint64_t seed, int32_t dtype, void* stream);
+int mk_sample_keep_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                        float top_p, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff, uint8_t* keep,
+                        int64_t keep_ld, int32_t dtype, void* stream);
 /* Logits processors (generate(repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=)): HF's
  *   RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor -> MinNewTokensLengthLogitsProcessor, in that
  *   order and with their arithmetic, written down here; restated in torch in tests/logits_proc_ref.py, to which the

@@ -60,6 +60,9 @@ DECODE_WEIGHTS = [None]
 KV_CACHE = [None]
 # MM_LLMs.set_sampling: the sampling arguments MM_LLMs.forward hands to generate()
 SAMPLING = [dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None)]
+# MM_LLMs.set_sampling's four warpers behind top-p, in a store of their own (HF's defaults: all off)
+_WARPERS_OFF = dict(min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
+SAMPLING_WARPERS = [dict(min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)]
 # MM_LLMs.set_beam_search: the beam arguments MM_LLMs.forward hands to generate()
 BEAM_SEARCH = [dict(num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1)]
 # MM_LLMs.set_logits_processors: the logits processors MM_LLMs.forward hands to generate()
@@ -107,6 +110,23 @@ def _sampling_check(where, temperature, top_k, top_p):
     if not isinstance(top_k, numbers.Integral) or top_k < 0:
         raise ValueError(f"{where}: top_k must be None or an integer >= 0, got {top_k!r}")
     return float(temperature), int(top_k), float(top_p)
+
+
+def _warpers_check(where, min_p, typical_p, epsilon_cutoff, eta_cutoff):
+    """the four warpers behind top-p of generate(do_sample=True) / set_sampling -> (min_p, typical_p, epsilon_cutoff,
+    eta_cutoff) as floats, or () when all four are off (None or 0, 1, 0, 0)"""
+    def real(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)
+    min_p = 0.0 if min_p is None else min_p
+    if not (real(min_p) and 0 <= min_p <= 1):
+        raise ValueError(f"{where}: min_p must be None or lie in [0, 1], got {min_p!r}")
+    if not (real(typical_p) and 0 < typical_p <= 1):
+        raise ValueError(f"{where}: typical_p must lie in (0, 1], got {typical_p!r}")
+    for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+        if not (real(v) and 0 <= v < 1):
+            raise ValueError(f"{where}: {name} must lie in [0, 1), got {v!r}")
+    warp = (float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff))
+    return () if warp == (0.0, 1.0, 0.0, 0.0) else warp
 
 
 def _processors_check(where, repetition_penalty, no_repeat_ngram_size, min_new_tokens):
@@ -884,7 +904,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
         by ops.decode_emit) -- so the launches of a step (5 per layer + 3) are captured once, after
         one eager step that also serves as the warm-up, and replayed; the host only looks at the
-        finished flags every few tokens.  sample = (temperature, top_k, top_p, seed): ops.decode_emit_sample draws the
+        finished flags every few tokens.  sample = (temperature, top_k, top_p, seed), followed by (min_p, typical_p,
+        epsilon_cutoff, eta_cutoff) when one of those four is on: ops.decode_emit_sample (ops.decode_emit_sample_warp) draws the
         token instead, its random number a hash of (seed, output column, sample) computed on the device.  process(logits,
         out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1].  n_top (None:
         off): ops.decode_emit_logprobs behind the emit, on the logits the emit selected from, writes the token's
@@ -909,7 +930,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if process is not None:
                 process(lg, out_buf, state[1:2], done=done)
             if sample is not None:
-                ops.decode_emit_sample(lg, V, pad, eos, tok, done, out_buf, state, *sample)
+                emit = ops.decode_emit_sample if len(sample) == 4 else ops.decode_emit_sample_warp
+                emit(lg, V, pad, eos, tok, done, out_buf, state, *sample)
             else:
                 ops.decode_emit(lg, V, pad, eos, tok, done, out_buf, state)
             if stopped is not None:      # in front of the log-probabilities' latch: the stop token keeps its value
@@ -1015,8 +1037,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     @torch.no_grad()
     def generate(self, inputs_embeds=None, input_ids=None, max_new_tokens=128, eos_token_id=2,
                  bos_token_id=1, pad_token_id=None, use_cache=True, decode_graph=True, decode_weights=None,
-                 kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None,
-                 attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
+                 kv_cache=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, min_p=None,
+                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, attention_mask=None, num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
                  return_beam_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                  prompt_lookup_num_tokens=None, max_matching_ngram_size=2, return_lookup_stats=False,
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
@@ -1077,6 +1099,22 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         (HF keeps the whole tie group), which makes top_k=1 greedy.  temperature <= 0, top_p outside (0, 1] and a
         negative top_k raise ValueError.  With do_sample=False (default) the four arguments are ignored and not one
         launch differs.  Composes with decode_weights, kv_cache and LoRA (they only change where the logits come from).
+
+        min_p, typical_p, epsilon_cutoff, eta_cutoff (do_sample=True; HF's names, defaults None, 1.0, 0.0, 0.0 = off, and
+        order: behind top_p, in front of the draw; HF's MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and
+        EtaLogitsWarper with min_tokens_to_keep = 1).  Each works on the survivors of the stages before it, renormalised
+        over them, and keeps at least one token.  min_p in [0, 1]: a token stays iff its probability is at least min_p times
+        the largest.  typical_p in (0, 1]: the tokens whose -log p lies nearest to the entropy, as many as it takes to reach
+        the mass typical_p (a band around the entropy: the most likely token can go).  epsilon_cutoff in [0, 1): a token
+        stays iff its probability is at least epsilon_cutoff.  eta_cutoff in [0, 1): the same with the threshold
+        min(eta, sqrt(eta) * exp(-entropy)).  The rule is rule 6 next to mk_sample_rows in include/macaw_hip.h, restated
+        in tests/warpers_ref.py; the stages run inside the one selection launch (csrc/sample.hip; ops.sample_rows_warp and
+        ops.decode_emit_sample_warp, called in place of ops.sample_rows / ops.decode_emit_sample), so the hipGraph path
+        keeps its one replay per token, and they reach every loop that samples: the eager loops, a padded batch,
+        use_cache=False, guidance, num_samples, sessions, adapter_names and a grammar (they see the masked row, as top_k
+        does).  Log-probabilities go on scoring the logits in front of temperature.  ops.sample_keep_rows returns the
+        surviving tokens of a row of logits.  Values outside the ranges, bool, NaN and inf raise ValueError; with
+        do_sample=False the four are ignored.  With all four off every launch is the one without them.
 
         attention_mask [B, S0] (any integer or bool dtype, non-zero = valid): a PADDED batch -- left padding, right
         padding or holes.  Sample b generates what its n_b valid tokens would generate alone, in order and unpadded:
@@ -1374,7 +1412,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             temperature, top_k, top_p = _sampling_check("generate", temperature, top_k, top_p)
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
-            sample = (temperature, top_k, top_p, int(seed))
+            sample = (temperature, top_k, top_p, int(seed)) + _warpers_check("generate", min_p, typical_p, epsilon_cutoff,
+                                                                             eta_cutoff)
         N = 1                     # num_samples: the rows per prompt (1: off, nothing below runs)
         if not (type(num_samples) is int and num_samples == 1):
             N = _num_samples_check("generate", num_samples)
@@ -1648,7 +1687,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             lg = logits(h_last)
             if process is not None:
                 process(lg, gen_buf, n_add=t, done=done)
-            ids = ops.sample_rows(lg, V, *sample, step=t) if sample is not None else ops.argmax_rows(lg, V)
+            if sample is None:
+                ids = ops.argmax_rows(lg, V)
+            elif len(sample) == 4:
+                ids = ops.sample_rows(lg, V, *sample, step=t)
+            else:                 # one of the four warpers on: the 8-tuple
+                ids = ops.sample_rows_warp(lg, V, *sample, step=t)
             nxt = torch.where(done, pads, ids)
             if gen_buf is not None:
                 gen_buf[:, t] = nxt
@@ -2265,10 +2309,13 @@ class MM_LLMs(PreTrainedModel):
             # a grammar set: every answer is constrained by it; unset: exactly the call without it
             if GRAMMAR[0] is not None:
                 par["grammar"] = GRAMMAR[0]
+            # one of the four warpers behind top-p set: passed on; unset: exactly the call without them
+            warpers = SAMPLING_WARPERS[0] if SAMPLING_WARPERS[0] != _WARPERS_OFF else {}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
                                      eos_token_id=2, bos_token_id=1, pad_token_id=32006,
                                      decode_weights=DECODE_WEIGHTS[0], kv_cache=KV_CACHE[0],
-                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **lps,
+                                     attention_mask=attention_mask if GENERATE_MASK[0] else None, **SAMPLING[0], **warpers,
+                                     **lps,
                                      **turn, **guide, **stopping, **par, **BEAM_SEARCH[0], **PROCESSORS[0], **look)
         return self.llm(inputs_embeds=text_embeddings, attention_mask=attention_mask, labels=labels)
 
@@ -2323,14 +2370,18 @@ class MM_LLMs(PreTrainedModel):
         GENERATE_MASK[0] = bool(on)
 
     @staticmethod
-    def set_sampling(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None):
+    def set_sampling(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, seed=None, *, min_p=None, typical_p=1.0,
+                     epsilon_cutoff=0.0, eta_cutoff=0.0):
         """Token selection of `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the same names):
         greedy by default; do_sample=True draws from the temperature / top-k / top-p filtered distribution, seed=None
-        taking a fresh seed from torch's default generator at every call.  Validated here when do_sample is set.
+        taking a fresh seed from torch's default generator at every call; min_p, typical_p, epsilon_cutoff and eta_cutoff
+        (keyword only, off by default) are the four warpers behind top-p.  Validated here when do_sample is set.
         Process-wide switch, like set_decode_weights and set_kv_cache."""
         if do_sample:
             _sampling_check("set_sampling", temperature, top_k, top_p)
+            _warpers_check("set_sampling", min_p, typical_p, epsilon_cutoff, eta_cutoff)
         SAMPLING[0] = dict(do_sample=bool(do_sample), temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        SAMPLING_WARPERS[0] = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
 
     @staticmethod
     def set_beam_search(num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1):

@@ -779,6 +779,27 @@ def decode_emit_sample(logits, V, pad, eos, tok, done, out, state, temperature=1
                                        int(seed) & 0xFFFFFFFFFFFFFFFF, dt(logits), _st()), "mk_decode_emit_sample")
 
 
+def _warpers_on(min_p, typical_p, epsilon_cutoff, eta_cutoff):
+    """whether any of the four warpers behind top-p is on (their off values: 0, 1, 0, 0)"""
+    return not (min_p == 0 and typical_p == 1 and epsilon_cutoff == 0 and eta_cutoff == 0)
+
+
+def decode_emit_sample_warp(logits, V, pad, eos, tok, done, out, state, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                            min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+    """decode_emit_sample with the four warpers behind top-p (rule 6 of the header; see mk_decode_emit_sample_warp): min_p,
+    typical_p, epsilon_cutoff, eta_cutoff, off at 0, 1, 0, 0 -- the same ids as sample_rows_warp(step=state[1]) on the
+    same logits.  With all four off this IS the decode_emit_sample call."""
+    if not _warpers_on(min_p, typical_p, epsilon_cutoff, eta_cutoff):
+        return decode_emit_sample(logits, V, pad, eos, tok, done, out, state, temperature, top_k, top_p, seed)
+    lib = _L.load()
+    B = logits.shape[0]
+    _L.check(lib.mk_decode_emit_sample_warp(_p(logits), _rowmajor(logits), V, B, pad, eos, _p(tok), _p(done), _p(out),
+                                            out.stride(0), _p(state), float(temperature), int(top_k), float(top_p),
+                                            float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, dt(logits), _st()),
+             "mk_decode_emit_sample_warp")
+
+
 def logits_process(logits, V, out, n_dev=None, n_add=0, prompt=None, prompt_len=None, repetition_penalty=1.0,
                    no_repeat_ngram_size=0, min_new_tokens=0, eos=None):
     """the logits processors in one launch, in place, in front of an emit (see mk_logits_process): logits [B, >= V]
@@ -1590,6 +1611,38 @@ def sample_rows(x, cols=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=
     _L.check(lib.mk_sample_rows(_p(x), _rowmajor(x), rows, cols, float(temperature), int(top_k), float(top_p),
                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _p(out), dt(x), _st()), "mk_sample_rows")
     return out
+
+
+def sample_rows_warp(x, cols=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, min_p=0.0, typical_p=1.0,
+                     epsilon_cutoff=0.0, eta_cutoff=0.0, step=0):
+    """sample_rows with the four warpers behind top-p, in front of the draw (rule 6 of the header; see
+    mk_sample_rows_warp): min_p, typical_p, epsilon_cutoff, eta_cutoff, off at 0, 1, 0, 0.  With all four off this IS the
+    sample_rows call."""
+    if not _warpers_on(min_p, typical_p, epsilon_cutoff, eta_cutoff):
+        return sample_rows(x, cols, temperature, top_k, top_p, seed, step)
+    lib = _L.load()
+    rows = x.shape[0]
+    cols = x.shape[1] if cols is None else cols
+    out = torch.empty(rows, dtype=torch.int64, device=x.device)
+    _L.check(lib.mk_sample_rows_warp(_p(x), _rowmajor(x), rows, cols, float(temperature), int(top_k), float(top_p),
+                                     float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _p(out), dt(x), _st()),
+             "mk_sample_rows_warp")
+    return out
+
+
+def sample_keep_rows(x, cols=None, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0,
+                     eta_cutoff=0.0):
+    """the kept mask of sample_rows_warp's filter -> bool [rows, cols]: True where a draw with these arguments can land (HF's
+    "which tokens survive the warpers"; see mk_sample_keep_rows).  A row without a finite logit is all False."""
+    lib = _L.load()
+    rows = x.shape[0]
+    cols = x.shape[1] if cols is None else cols
+    keep = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
+    _L.check(lib.mk_sample_keep_rows(_p(x), _rowmajor(x), rows, cols, float(temperature), int(top_k), float(top_p),
+                                     float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff), _p(keep),
+                                     cols, dt(x), _st()), "mk_sample_keep_rows")
+    return keep.bool()
 
 
 def adamw_(param, master, m, v, grad, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):

@@ -62,6 +62,9 @@ with torch.no_grad():
 # call of 72 tokens the difference is the search for the returned width behind the loop (one ops.stop_match launch per column).
 # Then the stand-alone time of one ops.seq_ban / ops.stop_match launch (tables of 4 and of 1000 sequences) against
 # ops.decode_emit on [B, V] logits with 100 generated ids
+#        bench_generate.py --warpers-ab [--reps R] [B ...]: four arms alternated in one process -- greedy; do_sample=True, top_k=50,
+#            top_p=0.9 (--sample-ab's sampled arm); that plus min_p=0.05; that plus typical_p=0.9, epsilon_cutoff=3e-4,
+#            eta_cutoff=2e-3 -- ms / token per arm with each arm's run-to-run spread, and the emit launch of each arm by itself
 #        bench_generate.py --nsample-ab [--prompt-tokens N] [--reps R]: parallel sampling for (B, n) = (1, 4), (2, 16), (8, 4).
 # Three arms alternated in this process on this model, all with do_sample=True, top_k=50, top_p=0.9, seed 1: "repeat" = the
 # prompts repeated n times, a batch of B * n (today's way); "shared R=1" = num_samples=n at batch B (the prompt cache stored once,
@@ -115,12 +118,13 @@ BEAM = "--beam-ab" in sys.argv
 MX4 = "--mxfp4-ab" in sys.argv
 RAGGED = "--ragged-ab" in sys.argv
 SAMPLE = "--sample-ab" in sys.argv
+WARPERS = "--warpers-ab" in sys.argv
 KV8 = "--kv8-ab" in sys.argv
 _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", "--warpers-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
 if SCORE:
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     N_OPT, L_OPT = 4, 16
@@ -794,6 +798,54 @@ if PROC:
             e1.record(); torch.cuda.synchronize()
             us[name] = e0.elapsed_time(e1) / 200 * 1e3
             st.zero_()
+        print(f"B={B:2d}: one launch on [B, 32000] bf16 logits (back to back, incl. launch gaps): " +
+              ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
+if WARPERS:
+    from macaw_llm_amd import ops
+    SKW = dict(do_sample=True, top_k=50, top_p=0.9, seed=1)
+    ARMS = {"greedy": {}, "sampled": SKW, "min_p": dict(SKW, min_p=0.05),
+            "typ+eps+eta": dict(SKW, typical_p=0.9, epsilon_cutoff=3e-4, eta_cutoff=2e-3)}
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {a: [] for a in ARMS}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            for arm, kw in ARMS.items():        # untimed: each arm's first call (code objects, allocator pools at this size)
+                model.llm.generate(inputs_embeds=emb, max_new_tokens=4, eos_token_id=-1, **kw)
+            for rep in range(REPS):
+                for arm, kw in ARMS.items():
+                    t = {}
+                    for new in (8, 72):
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, **kw)
+                        torch.cuda.synchronize(); t[new] = time.perf_counter() - t0
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {arm:11s}: decode {ms[arm][-1]:6.3f} ms/token", flush=True)
+        med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+        spread = {a: max(v) - min(v) for a, v in ms.items()}
+        print(f"B={B:2d}: " + ", ".join(f"{a} {med[a]:6.3f} ms/token (spread {spread[a] * 1e3:5.1f} us)" for a in ARMS), flush=True)
+        for a in ("min_p", "typ+eps+eta"):
+            d = med[a] - med["sampled"]
+            print(f"B={B:2d}: {a} - sampled = {d * 1e3:+7.1f} us / token ({d / med['sampled'] * 100:+5.2f} %): "
+                  f"{'inside' if abs(d) <= spread['sampled'] else 'OUTSIDE'} the sampled arm's spread", flush=True)
+        # the selection launch of each arm by itself: 200 back-to-back launches between two events, after 20 warm-up launches
+        x = torch.randn(B, 32000, device=dev).mul_(3).to(torch.bfloat16)
+        us = {}
+        for name, fn in (("argmax_rows", lambda i: ops.argmax_rows(x)),
+                         ("sampled", lambda i: ops.sample_rows(x, None, 1.0, 50, 0.9, 1, i)),
+                         ("min_p", lambda i: ops.sample_rows_warp(x, None, 1.0, 50, 0.9, 1, 0.05, step=i)),
+                         ("typ+eps+eta", lambda i: ops.sample_rows_warp(x, None, 1.0, 50, 0.9, 1, 0.0, 0.9, 3e-4, 2e-3, step=i)),
+                         ("typical k=0 p=1", lambda i: ops.sample_rows_warp(x, None, 1.0, 0, 1.0, 1, 0.0, 0.9, step=i)),
+                         ("keep mask typ+eps+eta", lambda i: ops.sample_keep_rows(x, None, 1.0, 50, 0.9, 0.0, 0.9, 3e-4, 2e-3))):
+            for i in range(20):
+                fn(i)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(200):
+                fn(i)
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 200 * 1e3
         print(f"B={B:2d}: one launch on [B, 32000] bf16 logits (back to back, incl. launch gaps): " +
               ", ".join(f"{k} {v:6.1f} us" for k, v in us.items()), flush=True)
     sys.exit(0)
