@@ -546,6 +546,52 @@ int mk_logits_process(void* logits, int64_t ld, int32_t V, int32_t B, const int6
                       const int32_t* p_len, const int64_t* out, int64_t out_ld, int32_t n_max, const int32_t* n_dev,
                       int32_t n_add, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens,
                       int64_t eos, int32_t dtype, void* stream);
+/* Per-request penalties (generate(frequency_penalty=, presence_penalty=, logit_bias=)): the additive penalties and the
+ *   bias every OpenAI-compatible front end forwards (OpenAI, vLLM, TGI, the llama.cpp server), with OpenAI's and vLLM's
+ *   definition, written down here; restated in torch in tests/penalties_ref.py, to which the kernel is pinned bit for
+ *   bit.  Unlike repetition_penalty they are additive, proportional to how often a token was generated and blind to the
+ *   prompt, and every value is PER ROW: a batch may mix requests.
+ *
+ * Inputs of row b:
+ *   g_b        the GENERATED ids only: the step's output matrix, int64 [B][n_max] at pitch out_ld, columns [0, n) of row
+ *              b, with n = clamp((n_dev ? *n_dev : 0) + n_add, 0, n_max), n_dev and n_add exactly as in "Logits
+ *              processors" (the graph loop passes state + 1, so a captured step replays).  The prompt is never counted.
+ *   cnt_c      the number of positions of g_b that hold id c.  An id outside [0, V) names no column.
+ *   f_b, p_b   frequency[b] and presence[b], float32 [B] on the device; a null array is all zeros.
+ *   bias       a list per row in CSR form: bias_off int32 [B + 1], ascending from 0; bias_ids int32 [nnz], row b's ids
+ *              bias_ids[bias_off[b] .. bias_off[b + 1]) ASCENDING and DISTINCT within the row, all inside [0, V);
+ *              bias_val float32 [nnz], finite.  A null bias_off means no bias.
+ *
+ * The rule.  Column c of row b is TOUCHED iff it has a bias entry beta_c, or cnt_c > 0 and (f_b != 0 or p_b != 0).  For a
+ *   touched column, all in fp32, every operation rounded by itself (no fused multiply-add), in this order:
+ *     x = float(logit[c])
+ *     if it has a bias entry:  x = x + beta_c
+ *     if cnt_c > 0:            x = x - (f_b * float(cnt_c));  x = x - p_b      (both steps, also when one of f_b, p_b is 0)
+ *     logit[c] = x rounded to nearest even to the logits' type (ONE rounding, also when bias and count meet)
+ *   On finite rows this is vLLM's logits -= f * counts; logits -= p * (counts > 0) with the bias added first.
+ *   Consequences: -inf stays -inf and a NaN stays NaN, so a ban or min_new_tokens in front cannot be undone (bias values
+ *   are finite); +inf stays +inf.  (Which NaN a touched NaN becomes, its sign and payload, is not part of the rule.)  Untouched columns, and the padding [V, ld), keep their bits exactly: -0 and NaN
+ *   payloads are not rewritten.  Token 0 (n = 0) sees only the bias.  cnt_c <= n_max <= 2^24, so float(cnt_c) is exact.
+ *   Its place in the chain: BEHIND mk_logits_process and in front of mk_seq_ban, mk_grammar_mask, mk_decode_emit_logprobs
+ *   and every selection: bans and the grammar have the last word, and log-probabilities are scored on the biased row.
+ *   One deliberate difference from vLLM: vLLM adds logit_bias in front of repetition_penalty, here it is added behind
+ *   it; the two differ only when both name the same token.
+ *
+ * mk_logits_penalize: one launch, one workgroup per row.  The generated ids are staged in LDS, the distinct ones found
+ *   with the V-bit LDS bitmap of mk_logits_process; the thread whose atomic OR sets an id's bit counts it over the staged
+ *   ids, looks its column up in the row's bias ids (binary search) and rewrites it once; the bias entries of columns
+ *   that were not generated are written by threads striding over the row's list.  Exact and deterministic whatever the
+ *   arrival order: a count is a sum of integers, and every touched column is written exactly once.  A history longer
+ *   than the staging buffer (2048 ids) is staged in rounds, not refused.  A row with f_b == 0, p_b == 0 and no bias entry
+ *   returns at once and keeps its bits; with frequency, presence and bias_off all null nothing is launched.  Logits
+ *   bf16 / f16 / f32 [B][V] at pitch ld >= V, in place.
+ *   MK_ERR_BAD_ARG: logits or out null, B <= 0, V <= 0, ld < V, n_max < 0, n_max > 2^24, out_ld < n_max, bias_off
+ *   without bias_ids or bias_val.  The bitmap takes 32 KiB of LDS: V <= 2^18 = 262144, else MK_ERR_UNSUPPORTED; another
+ *   dtype: MK_ERR_UNSUPPORTED. */
+int mk_logits_penalize(void* logits, int64_t ld, int32_t V, int32_t B, const int64_t* out, int64_t out_ld, int32_t n_max,
+                       const int32_t* n_dev, int32_t n_add, const float* frequency, const float* presence,
+                       const int32_t* bias_off, const int32_t* bias_ids, const float* bias_val, int32_t dtype,
+                       void* stream);
 /* Token-sequence matching (generate(bad_words_ids=, stop_sequences=)): HF's NoBadWordsLogitsProcessor, and the stop
  *   lists of TGI (stop_sequences) and vLLM (stop) -- HF's stop_strings at token level -- written down here; restated in
  *   torch in tests/stop_ref.py, to which both kernels are pinned exactly (integers and the -inf bit pattern only).

@@ -25,7 +25,7 @@ ARCH = "gfx950"
 # wave per SIMD: loses to the 8-wave kernel, profiles/r05_attn8.txt F; MK_ATTN_FWD4X64=1 selects it in such a build)
 EXPERIMENTS = bool(os.environ.get("MK_EXPERIMENTS"))
 SOURCES = ["gemm.hip", "gemm_v7.hip", *(["gemm_v8.hip"] if EXPERIMENTS else []), "gemm_v9.hip", "norm.hip",
-           "elementwise.hip", "softmax.hip", "attention.hip", "decode.hip", "decode_fp8.hip", "decode_mxfp4.hip", "sample.hip", "logits_process.hip", "stop.hip", "grammar.hip", "beam.hip", "spec.hip", "logprobs.hip", "cfg.hip", "preprocess.hip", "lora.hip",
+           "elementwise.hip", "softmax.hip", "attention.hip", "decode.hip", "decode_fp8.hip", "decode_mxfp4.hip", "sample.hip", "logits_process.hip", "penalty.hip", "stop.hip", "grammar.hip", "beam.hip", "spec.hip", "logprobs.hip", "cfg.hip", "preprocess.hip", "lora.hip",
            "lora_bgmv.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", *os.environ.get("MK_EXTRA_FLAGS", "").split(),
          *(["-DMK_WITH_V8", "-DMK_WITH_FWD4X64"] if EXPERIMENTS else []), "-Wno-unused-result"]
@@ -35,7 +35,10 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
 # default `#pragma unroll` size budget; left rolled, the fragment-row loop indexes the 256 accumulator
 # registers dynamically and the whole accumulator goes through scratch memory.
 FILE_FLAGS = {"gemm_v8.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
-              "gemm_v9.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
+              "gemm_v9.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+              # penalty.hip: its rule rounds the product f * count by itself (include/macaw_hip.h); hipcc's default
+              # contracts a * b - c into one fused multiply-add
+              "penalty.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -125,6 +125,7 @@ SIGNATURES = {
     "mk_sample_keep_rows": [_vp, _i64, _i32, _i32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _i64, _i32, _vp],
     "mk_logits_process": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _f32, _i32, _i32, _i64,
                           _i32, _vp],
+    "mk_logits_penalize": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "mk_seq_ban": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp],
     "mk_stop_match": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
     "mk_grammar_mask": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp],

@@ -86,6 +86,9 @@ SESSION = [False]
 ADAPTERS = [None]
 # MM_LLMs.set_grammar: the grammar MM_LLMs.forward hands to generate() (None = off: the call without it)
 GRAMMAR = [None]
+# MM_LLMs.set_penalties: the frequency_penalty, presence_penalty and logit_bias MM_LLMs.forward hands to generate() (only
+# when one is set)
+PENALTIES = [dict(frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None)]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -127,6 +130,64 @@ def _warpers_check(where, min_p, typical_p, epsilon_cutoff, eta_cutoff):
             raise ValueError(f"{where}: {name} must lie in [0, 1), got {v!r}")
     warp = (float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff))
     return () if warp == (0.0, 1.0, 0.0, 0.0) else warp
+
+
+MAX_LOGIT_BIAS = 1024         # entries per row of logit_bias (ops.MAX_BIAS)
+_PENALTIES_OFF = dict(frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None)
+
+
+def _penalties_check(where, frequency_penalty, presence_penalty, logit_bias, B=None, V=None):
+    """the penalty arguments of generate() / set_penalties -> None when nothing is on, else (f, p, bias): f and p lists
+    of one float per prompt (None: all zeros), bias a list of one dict | None per prompt (None: no entry anywhere).
+    B (None: not known yet) is the number of prompts a per-prompt form must match, V (None: not known yet) the vocabulary
+    size the ids stay below; a ValueError names what is wrong"""
+    def per_prompt(name, v):
+        if isinstance(v, torch.Tensor):
+            if v.dim() > 1:
+                raise ValueError(f"{where}: {name} must be a float or one float per prompt, got a tensor {tuple(v.shape)}")
+            v = v.detach().cpu().tolist()
+        vals = list(v) if isinstance(v, (list, tuple)) else [v]
+        for x in vals:
+            if not (isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x) and -2 <= x <= 2):
+                raise ValueError(f"{where}: {name} must be finite and in [-2, 2] (a float, or one per prompt), got {x!r}")
+        if isinstance(v, (list, tuple)):
+            if B is not None and len(vals) != B:
+                raise ValueError(f"{where}: {name} holds {len(vals)} values for {B} prompts (one per prompt)")
+            vals = [float(x) for x in vals]
+        elif B is not None:
+            vals = [float(v)] * B
+        return vals if any(x != 0 for x in vals) else None
+
+    f, p = per_prompt("frequency_penalty", frequency_penalty), per_prompt("presence_penalty", presence_penalty)
+    bias = None
+    if logit_bias is not None:
+        rows = logit_bias
+        if isinstance(rows, dict):
+            rows = [rows] * (B or 1)
+        elif isinstance(rows, (list, tuple)):
+            if B is not None and len(rows) != B:
+                raise ValueError(f"{where}: logit_bias holds {len(rows)} entries for {B} prompts (one dict or None per "
+                                 "prompt)")
+        else:
+            raise ValueError(f"{where}: logit_bias must be None, a dict {{token id: bias}} or a list with one dict or None "
+                             f"per prompt, got {type(rows).__name__}")
+        for r in rows:
+            if r is None:
+                continue
+            if not isinstance(r, dict):
+                raise ValueError(f"{where}: logit_bias: every row must be a dict {{token id: bias}} or None, got "
+                                 f"{type(r).__name__}")
+            if len(r) > MAX_LOGIT_BIAS:
+                raise ValueError(f"{where}: logit_bias: {len(r)} entries in one row; at most {MAX_LOGIT_BIAS}")
+            for c, v in r.items():
+                if isinstance(c, bool) or not isinstance(c, numbers.Integral) or c < 0 or (V is not None and c >= V):
+                    raise ValueError(f"{where}: logit_bias: token id {c!r} is not an integer in [0, "
+                                     f"{'V' if V is None else V})")
+                if not (isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v) and -100 <= v <= 100):
+                    raise ValueError(f"{where}: logit_bias[{c}] must be finite and in [-100, 100], got {v!r}")
+        if any(rows):
+            bias = [dict(r) if r else None for r in rows]
+    return None if f is None and p is None and bias is None else (f, p, bias)
 
 
 def _processors_check(where, repetition_penalty, no_repeat_ngram_size, min_new_tokens):
@@ -1044,7 +1105,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
                  negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
                  bad_words_ids=None, num_samples=1, session=None, return_session=False, session_capacity=None,
-                 adapter_names=None, grammar=None, **_):
+                 adapter_names=None, grammar=None, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -1348,7 +1409,28 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         marked broken and finishes.  ValueError naming the condition for an object that is not a TokenDFA, num_beams > 1,
         prompt_lookup_num_tokens > 0, session= / return_session=True (grammars along beams, through the verify step and
         across sessions are not built), a list of the wrong length and a vocabulary size that is not the model's.  None
-        (default): nothing is allocated, launched or read."""
+        (default): nothing is allocated, launched or read.
+
+        frequency_penalty, presence_penalty, logit_bias: the per-request controls of the OpenAI API, with OpenAI's and
+        vLLM's semantics (the rule: include/macaw_hip.h, "Per-request penalties"; restated in tests/penalties_ref.py).
+        A token generated cnt > 0 times has frequency_penalty * cnt + presence_penalty SUBTRACTED from its logit --
+        additive, proportional to the count, and blind to the prompt, where repetition_penalty is multiplicative,
+        idempotent and counts the prompt; logit_bias {token id: bias} is ADDED to its tokens at every step, token 0
+        included.  Each penalty is a float, or a sequence / tensor of one float per prompt, finite and in [-2, 2];
+        logit_bias is one dict for every prompt or a list with one dict | None per prompt, integer ids in [0, V), finite
+        values in [-100, 100], at most 1024 entries per row: a batch may mix requests, every value is per row.  One launch
+        (ops.logits_penalize) behind ops.logits_process and in front of ops.seq_ban, the grammar's mask, the
+        log-probabilities and every selection, in every loop, the counts read on the device: the graph loop stays one
+        hipGraph replay per token.  So bans and the grammar have the last word (a +100 bias cannot lift a banned
+        token), log-probabilities are scored on the biased row, and repetition_penalty is applied first (vLLM adds the
+        bias in front of it; the two differ only for a token both name).  Composes with sampling and the warpers,
+        the processors, stop sequences, bad_words_ids, grammars, log-probabilities, guidance (on the guided row), a
+        padded mask, use_cache=False, num_samples (a prompt's values go to each of its rows), decode_weights,
+        kv_cache, LoRA and adapter_names, and with sessions, where the count restarts with every call: this call's
+        generated tokens only, not those of earlier turns.  ValueError naming the condition for a value out of range, a
+        wrong count, a bad id or value, more than 1024 entries, another type, num_beams > 1 and
+        prompt_lookup_num_tokens > 0 (penalties along beams and behind the verify step are not built).  With the defaults
+        (0.0, 0.0, None) nothing is allocated or launched."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1387,6 +1469,19 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                        "for fp32)")
             if why is not None:
                 raise ValueError(f"generate(prompt_lookup_num_tokens={G}): {why}")
+        pen = None                # frequency_penalty / presence_penalty / logit_bias (None: off, nothing below runs)
+        if not (type(frequency_penalty) in (int, float) and frequency_penalty == 0 and type(presence_penalty) in (int, float)
+                and presence_penalty == 0 and logit_bias is None):                           # not the defaults
+            rows_of = inputs_embeds if inputs_embeds is not None else input_ids
+            pen = _penalties_check("generate", frequency_penalty, presence_penalty, logit_bias, rows_of.shape[0])
+        if pen is not None:
+            what = "generate(frequency_penalty=, presence_penalty=, logit_bias=)"
+            if K > 1:
+                raise ValueError(f"{what} with num_beams={K}: penalties along each beam's back-tracked history are not "
+                                 "built; use num_beams=1")
+            if G:
+                raise ValueError(f"{what} with prompt_lookup_num_tokens={G}: lookup behind "
+                                 "penalties is not built")
         n_top = None              # return_logprobs: the top columns per token (None: off, nothing below runs)
         if not (return_logprobs is False and type(top_logprobs) is int and top_logprobs == 0):   # not the defaults
             n_top = _logprobs_check("generate", return_logprobs, top_logprobs, K, G)
@@ -1533,6 +1628,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         layers = self.model.layers
         V = self.lm_head.weight.shape[0]
         hd = D // layers[0].self_attn.num_heads
+        if pen is not None:       # logit_bias: the ids against the vocabulary, now that it is known
+            _penalties_check("generate", frequency_penalty, presence_penalty, logit_bias, n_prompts, V)
         Tmax = S0 + max_new_tokens + G        # rows of the KV cache (prompt lookup: the G draft rows behind the last token)
         if sess:                  # a session's caches: the capacity asked for, or the one it has while that suffices
             need = Tmax
@@ -1635,13 +1732,22 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             g_tab, g_start = combine(gram, dev, V)
             g_state = torch.tensor(g_start, dtype=torch.int32).repeat_interleave(rows_per).to(dev)
             g_end = torch.full((Bs,), -1, dtype=torch.int32, device=dev)
+        pen_f = pen_p = pen_b = None      # the penalties per row, on the device: f32 [Bs], f32 [Bs], ops.BiasTable
+        if pen is not None:           # row r carries its prompt's values, as its history above
+            f, p, rows = pen
+            pen_f = torch.tensor(f, dtype=torch.float32).repeat_interleave(rows_per).to(dev) if f is not None else None
+            pen_p = torch.tensor(p, dtype=torch.float32).repeat_interleave(rows_per).to(dev) if p is not None else None
+            if rows is not None:
+                pen_b = ops.BiasTable([r for r in rows for _ in range(rows_per)], Bs, V, dev)
         process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add, done)
-        if proc is not None or bad is not None or g_tab is not None:
+        if proc is not None or pen is not None or bad is not None or g_tab is not None:
             bad_t = ops.SeqTable(bad, dev) if bad is not None else None
 
             def process(lg, gen, n_dev=None, n_add=0, done=None):
                 if proc is not None:
                     ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
+                if pen is not None:    # the penalties and the bias: behind the processors, on the generated ids alone
+                    ops.logits_penalize(lg, V, gen, n_dev, n_add, pen_f, pen_p, pen_b)
                 if bad_t is not None:  # bad_words_ids: one more launch behind the processors, on the same history
                     ops.seq_ban(lg, V, gen, bad_t, n_dev, n_add, hist, hist_len)
                 if g_tab is not None:  # grammar: behind both, so that the selection sees allowed columns alone
@@ -2309,6 +2415,9 @@ class MM_LLMs(PreTrainedModel):
             # a grammar set: every answer is constrained by it; unset: exactly the call without it
             if GRAMMAR[0] is not None:
                 par["grammar"] = GRAMMAR[0]
+            # a penalty or a bias set: passed on; unset: exactly the call without them
+            if PENALTIES[0] != _PENALTIES_OFF:
+                par.update(PENALTIES[0])
             # one of the four warpers behind top-p set: passed on; unset: exactly the call without them
             warpers = SAMPLING_WARPERS[0] if SAMPLING_WARPERS[0] != _WARPERS_OFF else {}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
@@ -2478,6 +2587,18 @@ class MM_LLMs(PreTrainedModel):
         if g is not None:
             g = _grammar_check("set_grammar", g)
         GRAMMAR[0] = g
+
+    @staticmethod
+    def set_penalties(frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None):
+        """The per-request penalties for `inputs["inference"] = True` (LlamaForCausalLM.generate's arguments of the same
+        names): off (0.0, 0.0, None) by default.  Each penalty is a float or one float per sample, logit_bias a dict
+        {token id: bias} for every sample or a list with one dict | None per sample.  The form and the ranges are
+        validated here; what depends on the call (the batch, the vocabulary size, beams, prompt lookup) is validated by
+        generate().  No arguments: back to off.  Process-wide switch, like set_logits_processors."""
+        frequency_penalty, presence_penalty = (v.detach().cpu().tolist() if isinstance(v, torch.Tensor) else v
+                                               for v in (frequency_penalty, presence_penalty))
+        _penalties_check("set_penalties", frequency_penalty, presence_penalty, logit_bias)
+        PENALTIES[0] = dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, logit_bias=logit_bias)
 
     @staticmethod
     def set_parallel_samples(num_samples=1):

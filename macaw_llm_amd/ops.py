@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
+import math
+import numbers
 import os
 from typing import Optional
 
@@ -830,6 +832,70 @@ def logits_process(logits, V, out, n_dev=None, n_add=0, prompt=None, prompt_len=
                                    max(out.stride(0), out.shape[1]), out.shape[1], _p(n_dev), int(n_add),
                                    float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
                                    -1 if eos is None else int(eos), dt(logits), _st()), "mk_logits_process")
+    return logits
+
+
+MAX_BIAS = 1024
+
+
+class BiasTable:
+    """the logit_bias lists of a batch on the device (include/macaw_hip.h, "Per-request penalties"), built once per call,
+    in CSR form: off int32 [B + 1], ids int32 [nnz] ascending and distinct within a row, val float32 [nnz].  rows: None,
+    one dict {token id: bias} for every row, or a list with one dict | None per row; ids are integers in [0, V), values
+    finite numbers, at most MAX_BIAS entries per row.  Without one entry the table is off: `on` is False, off / ids / val
+    are None and nothing is allocated"""
+
+    def __init__(self, rows, B, V, dev):
+        if rows is None or isinstance(rows, dict):
+            rows = [rows] * B
+        rows = list(rows)
+        if len(rows) != B:
+            raise MacawHipError(f"BiasTable: {len(rows)} rows for a batch of {B}")
+        ids, val, off = [], [], [0]
+        for b, r in enumerate(rows):
+            r = {} if r is None else r
+            if not isinstance(r, dict) or len(r) > MAX_BIAS:
+                raise MacawHipError(f"BiasTable: row {b} must be None or a dict of at most {MAX_BIAS} entries, got "
+                                    f"{type(r).__name__}" + (f" of {len(r)}" if isinstance(r, dict) else ""))
+            for c, v in r.items():
+                if (isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= c < V
+                        or isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v)):
+                    raise MacawHipError(f"BiasTable: row {b}: entry {c!r}: {v!r}; expected an integer id in [0, {V}) and a "
+                                        "finite bias")
+            r = sorted((int(c), float(v)) for c, v in r.items())      # (a dict's keys are distinct)
+            ids += [c for c, _ in r]
+            val += [v for _, v in r]
+            off.append(len(ids))
+        self.B, self.on = B, bool(ids)
+        self.off = self.ids = self.val = None
+        if self.on:
+            self.off = torch.tensor(off, dtype=torch.int32).to(dev)
+            self.ids = torch.tensor(ids, dtype=torch.int32).to(dev)
+            self.val = torch.tensor(val, dtype=torch.float32).to(dev)
+
+
+def logits_penalize(logits, V, out, n_dev=None, n_add=0, frequency=None, presence=None, bias=None):
+    """frequency_penalty, presence_penalty and logit_bias in one launch, in place, behind logits_process and in front of
+    seq_ban, grammar_mask and every selection (see mk_logits_penalize): logits [B, >= V] row-major; the generated ids of
+    row b are out[b, :n] (int64 [B, n_max], the emit's output matrix), n = (n_dev[0] if n_dev is not None else 0) + n_add
+    as logits_process takes them.  frequency, presence: contiguous float32 [B] device tensors or None (all zeros); bias:
+    a BiasTable of B rows or None.  Column c of row b gets + bias - frequency[b] * count - presence[b] (the last two
+    where count > 0), one rounding.  All three None (or the table off): no launch.  Returns logits"""
+    lib = _L.load()
+    B = logits.shape[0]
+    _gen_args("logits_penalize", B, out, n_dev)
+    for name, t in (("frequency", frequency), ("presence", presence)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()
+                              or t.device != logits.device):
+            raise MacawHipError(f"logits_penalize: {name} {t.dtype} {tuple(t.shape)} on {t.device}; expected a contiguous "
+                                f"float32 [{B}] on {logits.device}")
+    if bias is not None and bias.B != B:
+        raise MacawHipError(f"logits_penalize: a BiasTable of {bias.B} rows for logits of {B}")
+    on = bias is not None and bias.on
+    _L.check(lib.mk_logits_penalize(_p(logits), _rowmajor(logits), V, B, _p(out), max(out.stride(0), out.shape[1]),
+                                    out.shape[1], _p(n_dev), int(n_add), _p(frequency), _p(presence),
+                                    _p(bias.off) if on else None, _p(bias.ids) if on else None,
+                                    _p(bias.val) if on else None, dt(logits), _st()), "mk_logits_penalize")
     return logits
 
 

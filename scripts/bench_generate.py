@@ -103,6 +103,13 @@ with torch.no_grad():
 # teacher-forced decode steps would cost: generate()'s ms per token at batch B * n ((72 - 8 tokens) / 64, greedy) x 16.  ms per
 # call of every run, the medians, each arm's run-to-run spread and the ratios; the towers and the alignment
 # (prepare_inputs_for_generation) run once per prompt outside every arm and are timed alone
+#        bench_generate.py --penalties-ab [--reps R] [B ...]: the per-request penalties (default B = 1, 8, 32).  Three greedy arms
+# alternated in this process on this model: "greedy"; "penalties" = frequency_penalty=0.5, presence_penalty=0.5; "+bias" = the
+# same plus a 300-entry logit_bias (one ops.logits_penalize launch in front of the emit of every step): ms per token of every
+# run ((72 - 8 tokens) / 64), the medians, the differences to greedy and the greedy run-to-run spread (a difference counts only
+# beyond it).  Then the time of one ops.logits_penalize launch inside a hipGraph at n = 0 and at n = 2048 generated ids (what
+# the counting costs at the long end), with and without the 300-entry bias, against ops.decode_emit and ops.logits_process
+PENALTIES = "--penalties-ab" in sys.argv
 SCORE = "--score-ab" in sys.argv
 GRAMMAR = "--grammar-ab" in sys.argv
 ADAPTERS = "--adapters-ab" in sys.argv
@@ -124,7 +131,81 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", "--warpers-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", "--warpers-ab", "--penalties-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if PENALTIES:
+    from macaw_llm_amd import ops
+    V = model.llm.lm_head.weight.shape[0]
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    g = torch.Generator().manual_seed(5)
+    BIAS = {int(c): float(v) for c, v in zip(torch.randperm(V, generator=g)[:300], torch.rand(300, generator=g) * 10 - 5)}
+    ARMS = {"greedy": {}, "penalties": dict(frequency_penalty=0.5, presence_penalty=0.5),
+            "+bias": dict(frequency_penalty=0.5, presence_penalty=0.5, logit_bias=BIAS)}
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ms = {a: [] for a in ARMS}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            gen = lambda arm, new: model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, pad_token_id=0, **ARMS[arm])  # noqa: E731
+            for arm in ARMS:
+                gen(arm, 8)                         # warm-up of every arm
+            for rep in range(REPS):
+                for arm in ARMS:
+                    t = {}
+                    for new in (8, 72):
+                        ids, t[new] = timed(lambda: gen(arm, new))
+                        assert ids.shape[1] == new
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {arm:9s}: decode {ms[arm][-1]:6.3f} ms/token over 64 tokens", flush=True)
+        spread = max(ms["greedy"]) - min(ms["greedy"])
+        for arm in ("penalties", "+bias"):
+            d = med(ms[arm]) - med(ms["greedy"])
+            print(f"B={B:2d}: greedy {med(ms['greedy']):6.3f} ms/token, {arm} {med(ms[arm]):6.3f} ms/token, {arm} - greedy = "
+                  f"{d * 1e3:+7.1f} us per token ({d / med(ms['greedy']) * 100:+5.2f} %), greedy run-to-run spread "
+                  f"{spread * 1e3:6.1f} us: {'inside' if abs(d) <= spread else 'OUTSIDE'} the spread", flush=True)
+        # one launch by itself: 40 launches captured in a hipGraph (no host between them), replayed 4 times between two events.
+        # f = p = 2^-20: the 160 launches rewrite the same columns without ever driving a bf16 logit away
+        x = torch.randn(B, V, device=dev).mul_(3).to(torch.bfloat16)
+        out = torch.randint(3, V, (B, 2048), generator=torch.Generator(device=dev).manual_seed(3), device=dev)
+        tok, done = torch.zeros(B, dtype=torch.long, device=dev), torch.zeros(B, dtype=torch.bool, device=dev)
+        out_e = torch.zeros((B, 256), dtype=torch.long, device=dev)
+        st = torch.zeros(4, dtype=torch.int32, device=dev)
+        f = torch.full((B,), 2.0 ** -20, dtype=torch.float32, device=dev)
+        tab = ops.BiasTable({c: 2.0 ** -20 for c in BIAS}, B, V, dev)
+        n0, n2k = (torch.tensor([n], dtype=torch.int32, device=dev) for n in (0, 2048))
+        us = {}
+        for name, fn in (("decode_emit", lambda: ops.decode_emit(x, V, 0, -1, tok, done, out_e, st)),
+                         ("logits_process n=2048 (theta 1.0001)", lambda: ops.logits_process(x, V, out, n2k, 0, repetition_penalty=1.0001)),
+                         ("logits_penalize n=0 bias", lambda: ops.logits_penalize(x, V, out, n0, 0, f, f, tab)),
+                         ("logits_penalize n=100", lambda: ops.logits_penalize(x, V, out, n0, 100, f, f)),
+                         ("logits_penalize n=2048", lambda: ops.logits_penalize(x, V, out, n2k, 0, f, f)),
+                         ("logits_penalize n=2048 bias", lambda: ops.logits_penalize(x, V, out, n2k, 0, f, f, tab))):
+            for i in range(5):
+                fn()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for i in range(40):
+                    fn()
+            graph.replay()
+            st.zero_()                              # (the emit's output column: 5 + 5 * 40 launches stay inside out_e's 256)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(4):
+                graph.replay()
+            e1.record(); torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / 160 * 1e3
+            st.zero_()
+            del graph
+        print(f"B={B:2d}: one launch on [B, {V}] bf16 logits, 40 in a hipGraph (device time incl. the gap between two graph nodes): " +
+              ", ".join(f"{k} {v:6.2f} us" for k, v in us.items()), flush=True)
+    sys.exit(0)
 if SCORE:
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     N_OPT, L_OPT = 4, 16
