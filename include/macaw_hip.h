@@ -508,6 +508,42 @@ int mk_decode_emit_sample_warp(const void* logits, int64_t ld, int32_t V, int32_
 int mk_sample_keep_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, float temperature, int32_t top_k,
                         float top_p, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff, uint8_t* keep,
                         int64_t keep_ld, int32_t dtype, void* stream);
+/* Per-row sampling table (generate(sampling_params=[...])): the selection of the entries above with every parameter read
+ *   PER ROW from device memory, so one batch mixes greedy and sampled requests, temperatures, filters and seeds (OpenAI's
+ *   temperature / top_p / seed per request, vLLM's one SamplingParams per prompt); restated in
+ *   tests/sampling_params_ref.py on top of the restatements of rules 1-6.
+ *
+ * The table: `rows` records of 48 bytes, record r at byte 48 r, the table 16-byte aligned, little endian:
+ *     byte  0  float32  temperature        byte 16  float32  typical_p        byte 32  uint64   seed
+ *     byte  4  int32    top_k (0 = off)    byte 20  float32  epsilon_cutoff   byte 40  int32    mode: 0 greedy, 1 sampled
+ *     byte  8  float32  top_p              byte 24  float32  eta_cutoff       byte 44  int32    reserved, 0
+ *     byte 12  float32  min_p              byte 28  uint32   stream
+ *
+ * The rule for row r with record R:
+ *   mode 0 (greedy): the column mk_argmax_rows / mk_decode_emit select for that row -- the first NaN, else the first
+ *     maximum, column 0 for a row of -inf -- bit for bit; the other fields are not read.
+ *   mode 1 (sampled): rules 1-3 and 6 with R's seven values and the draw of rule 4 with
+ *     u = ((mk_hash32(R.seed, (uint64(step) << 32) | R.stream) >> 8) + 0.5) * 2^-24: rule 4 with the record's seed, and
+ *     the record's stream where rule 4 has the row index.  So the row's token is exactly what mk_sample_rows (with one of
+ *     R's four warpers on: mk_sample_rows_warp) returns at the same step, with R's values and seed, for the same logits
+ *     placed at row index R.stream: it does not depend on where the row sits in the batch, nor on the other rows.
+ *   A record outside the scalar entries' domain (temperature <= 0 or not finite, top_p outside (0, 1], top_k < 0, a warper
+ *     outside its range, another mode) is greedy: the kernel neither refuses nor loops.  Validation belongs where the
+ *     table is built.
+ *   The record is the workgroup's own, so the choice between the three forms (greedy, without the warpers, with them) is
+ *   uniform over the workgroup; the forms are the device functions of the scalar kernels, not copies of them.
+ *
+ * mk_sample_rows_table: out_ids[r] = that token for every row, the twin of mk_sample_rows / mk_sample_rows_warp.
+ * mk_decode_emit_sample_table: the twin of mk_decode_emit_sample / _warp, sample b by table[b] at step = state[1]: a
+ *   finished sample emits pad and draws nothing, eos sets done, and the last arriving workgroup advances state[0..2],
+ *   exactly as mk_decode_emit.
+ * One workgroup of 1024 threads per row; bf16 / f16 / f32.  MK_ERR_BAD_ARG: null pointers (the table included), rows or
+ *   B <= 0, V <= 0, ld < V.  MK_ERR_UNSUPPORTED: V > 2^23, a table that is not 16-byte aligned, another dtype. */
+int mk_sample_rows_table(const void* logits, int64_t ld, int32_t rows, int32_t V, const void* table, int32_t step,
+                         int64_t* out_ids, int32_t dtype, void* stream);
+int mk_decode_emit_sample_table(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad, int64_t eos,
+                                int64_t* tok, void* done, int64_t* out, int64_t out_ld, int32_t* state,
+                                const void* table, int32_t dtype, void* stream);
 /* Logits processors (generate(repetition_penalty=, no_repeat_ngram_size=, min_new_tokens=)): HF's
  *   RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor -> MinNewTokensLengthLogitsProcessor, in that
  *   order and with their arithmetic, written down here; restated in torch in tests/logits_proc_ref.py, to which the

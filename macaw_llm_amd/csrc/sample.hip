@@ -450,6 +450,35 @@ __global__ __launch_bounds__(SNT) void sample_keep_kernel(const T* logits, long 
   }
 }
 
+// decode_emit_kernel's bookkeeping for sample b at output column col, by one thread: pad for a finished sample, the eos
+// flag, the token fed next, and the step's hand-off by the last arriving workgroup
+MK_DEV void s_emit_books(int b, int col, bool fin, int idx, long pad, long eos, int64_t* tok, unsigned char* done,
+                         int64_t* out, long out_ld, int32_t* state) {
+  const long nxt = fin ? pad : (long)idx;
+  out[(long)b * out_ld + col] = nxt;
+  if (nxt == eos) done[b] = 1;
+  tok[b] = nxt;
+  __threadfence();
+  const int old = __hip_atomic_fetch_add(state + 2, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  if (old == (int)gridDim.x - 1) {              // every sample has read state[1]: advance the step
+    state[0] += 1;
+    state[1] = col + 1;
+    state[2] = 0;
+  }
+}
+
+// the domain of the scalar entries, and whether one of the four warpers is on (host: the C entries; device: a record)
+__host__ __device__ inline bool sample_args_ok(float temperature, int32_t top_k, float top_p) {
+  return isfinite(temperature) && temperature > 0.f && top_p > 0.f && top_p <= 1.f && top_k >= 0;
+}
+__host__ __device__ inline bool warp_args_ok(const SampleWarp& w) {        // (NaN fails every comparison)
+  return w.min_p >= 0.f && w.min_p <= 1.f && w.typical_p > 0.f && w.typical_p <= 1.f && w.eps >= 0.f && w.eps < 1.f &&
+         w.eta >= 0.f && w.eta < 1.f;
+}
+__host__ __device__ inline bool warp_on(const SampleWarp& w) {
+  return w.min_p > 0.f || w.typical_p < 1.f || w.eps > 0.f || w.eta > 0.f;
+}
+
 // decode_emit_kernel (decode.hip) with the argmax replaced by the draw; the RNG counter is the output column state[1]
 template <typename T, bool WARP>
 __global__ __launch_bounds__(SNT) void decode_emit_sample_kernel(const T* logits, long ld, int V, long pad, long eos,
@@ -462,31 +491,63 @@ __global__ __launch_bounds__(SNT) void decode_emit_sample_kernel(const T* logits
   const bool fin = done[b];
   const int idx =
       fin ? 0 : sample_row<T, WARP>(logits + (long)b * ld, V, temp, top_k, top_p, w, seed, (uint32_t)col, b, s);
-  if (threadIdx.x == 0) {
-    const long nxt = fin ? pad : (long)idx;
-    out[(long)b * out_ld + col] = nxt;
-    if (nxt == eos) done[b] = 1;
-    tok[b] = nxt;
-    __threadfence();
-    const int old = __hip_atomic_fetch_add(state + 2, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == (int)gridDim.x - 1) {            // every sample has read state[1]: advance the step
-      state[0] += 1;
-      state[1] = col + 1;
-      state[2] = 0;
-    }
-  }
+  if (threadIdx.x == 0) s_emit_books(b, col, fin, idx, pad, eos, tok, done, out, out_ld, state);
+}
+
+// The record of one row of the per-row sampling table ("Per-row sampling table", include/macaw_hip.h): 48 bytes.
+struct SampleRec {
+  float temp;
+  int32_t top_k;
+  float top_p;
+  SampleWarp w;
+  uint32_t stream;
+  uint64_t seed;
+  int32_t mode;       // 0 greedy, 1 sampled
+  int32_t rsv;
+};
+static_assert(sizeof(SampleRec) == 48 && offsetof(SampleRec, seed) == 32 && offsetof(SampleRec, mode) == 40,
+              "the per-row sampling record is 48 bytes");
+
+// the token of one row by its record: greedy (what mk_argmax_rows returns), sample_row<T, false>, or sample_row<T, true>
+// when one of the record's four warpers is on.  The record is the workgroup's own, so the branch is uniform; a record
+// outside the scalar entries' domain is greedy.
+template <typename T>
+MK_DEV int sample_row_rec(const T* xr, int V, const SampleRec* rec, uint32_t step, SampleLds& s) {
+  const SampleRec r = *rec;
+  int form = 0;
+  if (r.mode == 1 && sample_args_ok(r.temp, r.top_k, r.top_p) && warp_args_ok(r.w)) form = warp_on(r.w) ? 2 : 1;
+  form = __builtin_amdgcn_readfirstlane(form);
+  // (the warpers by reference to the table itself: a copy would have to live in scratch for the filter to address it)
+  if (form == 2) return sample_row<T, true>(xr, V, r.temp, r.top_k, r.top_p, rec->w, r.seed, step, r.stream, s);
+  if (form == 1) return sample_row<T, false>(xr, V, r.temp, r.top_k, r.top_p, rec->w, r.seed, step, r.stream, s);
+  int c0, c1;
+  s_chunk(V, c0, c1);
+  return s_greedy<T>(xr, c0, c1, s);
+}
+
+template <typename T>
+__global__ __launch_bounds__(SNT) void sample_rows_table_kernel(const T* logits, long ld, int V, const SampleRec* table,
+                                                                uint32_t step, int64_t* out) {
+  __shared__ SampleLds s;
+  const int idx = sample_row_rec<T>(logits + (long)blockIdx.x * ld, V, table + blockIdx.x, step, s);
+  if (threadIdx.x == 0) out[blockIdx.x] = idx;
+}
+
+// decode_emit_sample_kernel with the parameters of sample b read from table[b]
+template <typename T>
+__global__ __launch_bounds__(SNT) void decode_emit_sample_table_kernel(const T* logits, long ld, int V, long pad,
+                                                                       long eos, int64_t* tok, unsigned char* done,
+                                                                       int64_t* out, long out_ld, int32_t* state,
+                                                                       const SampleRec* table) {
+  __shared__ SampleLds s;
+  const int b = blockIdx.x;
+  const int col = state[1];                     // read by every thread before this workgroup's arrival
+  const bool fin = done[b];
+  const int idx = fin ? 0 : sample_row_rec<T>(logits + (long)b * ld, V, table + b, (uint32_t)col, s);
+  if (threadIdx.x == 0) s_emit_books(b, col, fin, idx, pad, eos, tok, done, out, out_ld, state);
 }
 
 constexpr int SAMPLE_MAX_V = 1 << 23;          // V masses of at most 2^40 each sum inside 64 bits
-
-bool sample_args_ok(float temperature, int32_t top_k, float top_p) {
-  return isfinite(temperature) && temperature > 0.f && top_p > 0.f && top_p <= 1.f && top_k >= 0;
-}
-bool warp_args_ok(const SampleWarp& w) {        // (NaN fails every comparison)
-  return w.min_p >= 0.f && w.min_p <= 1.f && w.typical_p > 0.f && w.typical_p <= 1.f && w.eps >= 0.f && w.eps < 1.f &&
-         w.eta >= 0.f && w.eta < 1.f;
-}
-bool warp_on(const SampleWarp& w) { return w.min_p > 0.f || w.typical_p < 1.f || w.eps > 0.f || w.eta > 0.f; }
 
 template <typename T>
 void launch_rows(bool warp, int rows, hipStream_t st, const void* logits, long ld, int V, float temperature, int top_k,
@@ -586,6 +647,45 @@ extern "C" int mk_decode_emit_sample_warp(const void* logits, int64_t ld, int32_
                                           int32_t dtype, void* stream) {
   return emit_sample_impl(logits, ld, V, B, pad, eos, tok, done, out, out_ld, state, temperature, top_k, top_p,
                           SampleWarp{min_p, typical_p, epsilon_cutoff, eta_cutoff}, seed, dtype, stream);
+}
+
+extern "C" int mk_sample_rows_table(const void* logits, int64_t ld, int32_t rows, int32_t V, const void* table,
+                                    int32_t step, int64_t* out_ids, int32_t dtype, void* stream) {
+  if (!logits || !table || !out_ids || rows <= 0 || V <= 0 || ld < V) return MK_ERR_BAD_ARG;
+  if (V > SAMPLE_MAX_V || (reinterpret_cast<uintptr_t>(table) & 15)) return MK_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const SampleRec* tb = (const SampleRec*)table;
+  if (dtype == MK_BF16)
+    MK_LAUNCH((sample_rows_table_kernel<bf16>), dim3(rows), dim3(SNT), 0, st, (const bf16*)logits, (long)ld, V, tb,
+              (uint32_t)step, out_ids);
+  else if (dtype == MK_F16)
+    MK_LAUNCH((sample_rows_table_kernel<_Float16>), dim3(rows), dim3(SNT), 0, st, (const _Float16*)logits, (long)ld, V,
+              tb, (uint32_t)step, out_ids);
+  else if (dtype == MK_F32)
+    MK_LAUNCH((sample_rows_table_kernel<float>), dim3(rows), dim3(SNT), 0, st, (const float*)logits, (long)ld, V, tb,
+              (uint32_t)step, out_ids);
+  else return MK_ERR_UNSUPPORTED;
+  return mk_check_launch();
+}
+
+extern "C" int mk_decode_emit_sample_table(const void* logits, int64_t ld, int32_t V, int32_t B, int64_t pad,
+                                           int64_t eos, int64_t* tok, void* done, int64_t* out, int64_t out_ld,
+                                           int32_t* state, const void* table, int32_t dtype, void* stream) {
+  if (!logits || !tok || !done || !out || !state || !table || V <= 0 || B <= 0 || ld < V) return MK_ERR_BAD_ARG;
+  if (V > SAMPLE_MAX_V || (reinterpret_cast<uintptr_t>(table) & 15)) return MK_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const SampleRec* tb = (const SampleRec*)table;
+  if (dtype == MK_BF16)
+    MK_LAUNCH((decode_emit_sample_table_kernel<bf16>), dim3(B), dim3(SNT), 0, st, (const bf16*)logits, (long)ld, V,
+              (long)pad, (long)eos, tok, (unsigned char*)done, out, (long)out_ld, state, tb);
+  else if (dtype == MK_F16)
+    MK_LAUNCH((decode_emit_sample_table_kernel<_Float16>), dim3(B), dim3(SNT), 0, st, (const _Float16*)logits, (long)ld,
+              V, (long)pad, (long)eos, tok, (unsigned char*)done, out, (long)out_ld, state, tb);
+  else if (dtype == MK_F32)
+    MK_LAUNCH((decode_emit_sample_table_kernel<float>), dim3(B), dim3(SNT), 0, st, (const float*)logits, (long)ld, V,
+              (long)pad, (long)eos, tok, (unsigned char*)done, out, (long)out_ld, state, tb);
+  else return MK_ERR_UNSUPPORTED;
+  return mk_check_launch();
 }
 
 extern "C" int mk_sample_keep_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, float temperature,

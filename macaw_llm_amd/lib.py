@@ -123,6 +123,8 @@ SIGNATURES = {
     "mk_decode_emit_sample_warp": [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _f32, _i32, _f32, _f32,
                                    _f32, _f32, _f32, _u64, _i32, _vp],
     "mk_sample_keep_rows": [_vp, _i64, _i32, _i32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _i64, _i32, _vp],
+    "mk_sample_rows_table": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp],
+    "mk_decode_emit_sample_table": [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp],
     "mk_logits_process": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _f32, _i32, _i32, _i64,
                           _i32, _vp],
     "mk_logits_penalize": [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp],

@@ -89,6 +89,8 @@ GRAMMAR = [None]
 # MM_LLMs.set_penalties: the frequency_penalty, presence_penalty and logit_bias MM_LLMs.forward hands to generate() (only
 # when one is set)
 PENALTIES = [dict(frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None)]
+# MM_LLMs.set_sampling_params: the sampling_params MM_LLMs.forward hands to generate() (None = off: the call without them)
+SAMPLING_PARAMS = [None]
 
 # what generate(return_logprobs=True) returns: ids as without it, logprobs f32 [B, width], top_ids int64 [B, width, n] and
 # top_logprobs f32 [B, width, n] (both None for top_logprobs=0)
@@ -130,6 +132,62 @@ def _warpers_check(where, min_p, typical_p, epsilon_cutoff, eta_cutoff):
             raise ValueError(f"{where}: {name} must lie in [0, 1), got {v!r}")
     warp = (float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff))
     return () if warp == (0.0, 1.0, 0.0, 0.0) else warp
+
+
+# the keys of one entry of generate(sampling_params=[...]) and what a missing one takes: generate()'s own defaults
+_SAMPLING_PARAMS_DEFAULTS = dict(temperature=1.0, top_k=50, top_p=1.0, min_p=None, typical_p=1.0, epsilon_cutoff=0.0,
+                                 eta_cutoff=0.0, seed=None)
+
+
+def _sampling_params_check(where, params, B=None):
+    """generate(sampling_params=) / set_sampling_params -> a list with one entry per prompt: None for a greedy prompt (an
+    entry None, or temperature == 0: OpenAI's and vLLM's rule; its other keys are validated all the same), else a dict of
+    temperature, top_k (0 = off), top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff as _sampling_check and
+    _warpers_check return them, and seed (an int, or None: to be drawn).  B (None: not known yet) is the number of
+    prompts the list must match; a ValueError names the entry and what is wrong with it"""
+    if not isinstance(params, (list, tuple)):
+        raise ValueError(f"{where}: sampling_params must be None or a list with one dict or None per prompt, got "
+                         f"{type(params).__name__}")
+    if B is not None and len(params) != B:
+        raise ValueError(f"{where}: sampling_params holds {len(params)} entries for {B} prompts (one dict or None per "
+                         "prompt)")
+    rows = []
+    for i, e in enumerate(params):
+        at = f"{where}: sampling_params[{i}]"
+        if e is None:
+            rows.append(None)
+            continue
+        if not isinstance(e, dict):
+            raise ValueError(f"{at} must be None or a dict, got {type(e).__name__}")
+        unknown = [k for k in e if k not in _SAMPLING_PARAMS_DEFAULTS]
+        if unknown:
+            raise ValueError(f"{at}: unknown key {unknown[0]!r}; the keys are {', '.join(_SAMPLING_PARAMS_DEFAULTS)}")
+        v = {**_SAMPLING_PARAMS_DEFAULTS, **e}
+        t = v["temperature"]
+        greedy = isinstance(t, numbers.Real) and not isinstance(t, bool) and t == 0
+        t, k, p = _sampling_check(at, 1.0 if greedy else t, v["top_k"], v["top_p"])
+        w = _warpers_check(at, v["min_p"], v["typical_p"], v["epsilon_cutoff"], v["eta_cutoff"]) or (0.0, 1.0, 0.0, 0.0)
+        seed = v["seed"]
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral)):
+            raise ValueError(f"{at}: seed must be None or an integer, got {seed!r}")
+        rows.append(None if greedy else dict(temperature=t, top_k=k, top_p=p, min_p=w[0], typical_p=w[1],
+                                             epsilon_cutoff=w[2], eta_cutoff=w[3],
+                                             seed=None if seed is None else int(seed)))
+    return rows
+
+
+def _sampling_params_rows(rows, n=1):
+    """the checked entries of _sampling_params_check -> the records of ops.SampleTable for the B * n decoded rows: row
+    b * n + j carries prompt b's values with stream = j.  A sampled prompt without a seed draws a 63-bit one from torch's
+    default CPU generator, in prompt order (torch.manual_seed governs them)"""
+    out = []
+    for r in rows:
+        if r is not None and r["seed"] is None:
+            r = dict(r, seed=int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)))
+        if r is not None:         # (top_k at or above the vocabulary is off: the record's field is an int32)
+            r = dict(r, top_k=min(r["top_k"], 2 ** 31 - 1))
+        out += [None if r is None else dict(r, stream=j) for j in range(n)]
+    return out
 
 
 MAX_LOGIT_BIAS = 1024         # entries per row of logit_bias (ops.MAX_BIAS)
@@ -967,7 +1025,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         one eager step that also serves as the warm-up, and replayed; the host only looks at the
         finished flags every few tokens.  sample = (temperature, top_k, top_p, seed), followed by (min_p, typical_p,
         epsilon_cutoff, eta_cutoff) when one of those four is on: ops.decode_emit_sample (ops.decode_emit_sample_warp) draws the
-        token instead, its random number a hash of (seed, output column, sample) computed on the device.  process(logits,
+        token instead, its random number a hash of (seed, output column, sample) computed on the device; an
+        ops.SampleTable (sampling_params): ops.decode_emit_sample_table, every sample by its own record.  process(logits,
         out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1].  n_top (None:
         off): ops.decode_emit_logprobs behind the emit, on the logits the emit selected from, writes the token's
         log-probability and the n_top most likely columns into device books (ops.LogprobState); the result is then
@@ -990,7 +1049,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             lg = logits(h_last)
             if process is not None:
                 process(lg, out_buf, state[1:2], done=done)
-            if sample is not None:
+            if isinstance(sample, ops.SampleTable):      # sampling_params: sample b by record b of the device table
+                ops.decode_emit_sample_table(lg, V, pad, eos, tok, done, out_buf, state, sample)
+            elif sample is not None:
                 emit = ops.decode_emit_sample if len(sample) == 4 else ops.decode_emit_sample_warp
                 emit(lg, V, pad, eos, tok, done, out_buf, state, *sample)
             else:
@@ -1105,7 +1166,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                  return_logprobs=False, top_logprobs=0, guidance_scale=None, negative_prompt_ids=None,
                  negative_prompt_attention_mask=None, negative_inputs_embeds=None, stop_sequences=None,
                  bad_words_ids=None, num_samples=1, session=None, return_session=False, session_capacity=None,
-                 adapter_names=None, grammar=None, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None, **_):
+                 adapter_names=None, grammar=None, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None,
+                 sampling_params=None, **_):
         """Greedy decode by default — the only mode the reference uses (modeling.py:959:
         `llm.generate(inputs_embeds=…, max_new_tokens=128, eos_token_id=2, bos_token_id=1,
         pad_token_id=32006)`, no attention mask).  Prefill runs the prompt once and fills a
@@ -1430,7 +1492,34 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         generated tokens only, not those of earlier turns.  ValueError naming the condition for a value out of range, a
         wrong count, a bad id or value, more than 1024 entries, another type, num_beams > 1 and
         prompt_lookup_num_tokens > 0 (penalties along beams and behind the verify step are not built).  With the defaults
-        (0.0, 0.0, None) nothing is allocated or launched."""
+        (0.0, 0.0, None) nothing is allocated or launched.
+
+        sampling_params=[...]: per-request sampling, one entry per prompt (OpenAI's temperature / top_p / seed per
+        request, vLLM's one SamplingParams per prompt), so a batch mixes greedy and sampled requests, temperatures,
+        filters and seeds.  An entry is None or a dict out of temperature, top_k, top_p, min_p, typical_p,
+        epsilon_cutoff, eta_cutoff, seed; a missing key takes this function's own default (1.0, 50, 1.0, None, 1.0, 0.0,
+        0.0, None) and the values obey the rules of the scalar arguments.  None, or temperature == 0, makes the prompt
+        greedy (its other keys are validated all the same); seed=None gives the prompt a fresh 63-bit seed from torch's
+        default CPU generator, drawn in prompt order (torch.manual_seed governs them).  The values go into one device
+        table (ops.SampleTable; the rule: include/macaw_hip.h, "Per-row sampling table", restated in
+        tests/sampling_params_ref.py) that the selection launch reads per row: ops.sample_rows_table in the eager loops,
+        ops.decode_emit_sample_table inside the captured step -- still one hipGraph replay per token -- in place of the
+        scalar launch, so everything in front of and behind the selection (a padded mask, use_cache=False, guidance on
+        its B guided rows, sessions, adapter_names, a grammar, the processors, the penalties, stop sequences,
+        log-probabilities, decode_weights, kv_cache) runs as it does for do_sample=True.  A greedy row gets the argmax
+        bit for bit.  A sampled row's random number is the counter hash of (its seed, the output column, its stream
+        index), the stream index being 0, and j for row b * n + j under num_samples=n: a request's draws depend on its
+        own seed, the output column and its sample index, never on its place in the batch, and they are the draws the
+        scalar call makes for it at batch 1 -- sampling_params=[d] at B = 1 returns the ids of do_sample=True, **d.  The
+        limit: the SELECTION is position-independent; the logits in front of it come from linears that choose their
+        kernel by the row count, so their last bits, and with them a draw that falls on a boundary, can differ between
+        batch sizes.  A list whose entries are all greedy is the greedy call: no table, no other launch.  ValueError
+        naming the condition, before anything is allocated, for the list together with do_sample=True (two ways to say
+        it), a value that is not a list or tuple, a wrong length, an entry that is neither None nor a dict, an unknown
+        key, a bad value, num_beams > 1, prompt_lookup_num_tokens > 0 and num_samples > 1 with a greedy entry (n
+        identical rows).  Out of scope: per-row max_new_tokens, eos, processors (repetition_penalty and its neighbours)
+        and stop sequences, per-request sampling along beams or behind the prompt-lookup verify step, and any tuning of
+        the selection launch itself.  None (default): not one launch, allocation, host read or message differs."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
@@ -1509,12 +1598,32 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
             sample = (temperature, top_k, top_p, int(seed)) + _warpers_check("generate", min_p, typical_p, epsilon_cutoff,
                                                                              eta_cutoff)
+        sp = None                 # sampling_params: per prompt None (greedy) or its values (None: off, nothing below runs)
+        if sampling_params is not None:
+            what = "generate(sampling_params=)"
+            if do_sample:
+                raise ValueError(f"{what} with do_sample=True: two ways to say how tokens are selected; pass the scalar "
+                                 "arguments or the list, not both")
+            rows_of = inputs_embeds if inputs_embeds is not None else input_ids
+            sp = _sampling_params_check("generate", sampling_params, rows_of.shape[0])
+            if K > 1:
+                raise ValueError(f"{what} with num_beams={K}: per-request sampling along beams is not built; use "
+                                 "num_beams=1")
+            if G:
+                raise ValueError(f"{what} with prompt_lookup_num_tokens={G}: per-request sampling behind the verify step "
+                                 "is not built")
         N = 1                     # num_samples: the rows per prompt (1: off, nothing below runs)
         if not (type(num_samples) is int and num_samples == 1):
             N = _num_samples_check("generate", num_samples)
+        if N > 1 and sp is not None and any(r is None for r in sp):
+            raise ValueError(f"generate(num_samples={N}) with a greedy entry in sampling_params (entry "
+                             f"{[r is None for r in sp].index(True)}): greedy decoding would return {N} identical rows for "
+                             "that prompt; give every entry a temperature > 0")
+        if sp is not None and all(r is None for r in sp):
+            sp = None             # every prompt greedy: today's greedy call, no table and no other launch
         if N > 1:
             what = f"generate(num_samples={N})"
-            if not do_sample:
+            if not do_sample and sp is None:
                 raise ValueError(f"{what} with do_sample=False: greedy decoding would return {N} identical rows per prompt; "
                                  "pass do_sample=True")
             if K > 1:
@@ -1739,6 +1848,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             pen_p = torch.tensor(p, dtype=torch.float32).repeat_interleave(rows_per).to(dev) if p is not None else None
             if rows is not None:
                 pen_b = ops.BiasTable([r for r in rows for _ in range(rows_per)], Bs, V, dev)
+        if sp is not None:            # the per-row sampling table: row b * n + j is prompt b's record with stream = j
+            sample = ops.SampleTable(_sampling_params_rows(sp, rows_per), dev)
         process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add, done)
         if proc is not None or pen is not None or bad is not None or g_tab is not None:
             bad_t = ops.SeqTable(bad, dev) if bad is not None else None
@@ -1795,6 +1906,8 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 process(lg, gen_buf, n_add=t, done=done)
             if sample is None:
                 ids = ops.argmax_rows(lg, V)
+            elif isinstance(sample, ops.SampleTable):     # sampling_params: every row by its own record
+                ids = ops.sample_rows_table(lg, V, sample, step=t)
             elif len(sample) == 4:
                 ids = ops.sample_rows(lg, V, *sample, step=t)
             else:                 # one of the four warpers on: the 8-tuple
@@ -2418,6 +2531,9 @@ class MM_LLMs(PreTrainedModel):
             # a penalty or a bias set: passed on; unset: exactly the call without them
             if PENALTIES[0] != _PENALTIES_OFF:
                 par.update(PENALTIES[0])
+            # per-request sampling set: one entry per prompt; unset: exactly the call without it
+            if SAMPLING_PARAMS[0] is not None:
+                par["sampling_params"] = SAMPLING_PARAMS[0]
             # one of the four warpers behind top-p set: passed on; unset: exactly the call without them
             warpers = SAMPLING_WARPERS[0] if SAMPLING_WARPERS[0] != _WARPERS_OFF else {}
             return self.llm.generate(inputs_embeds=text_embeddings, max_new_tokens=128,
@@ -2599,6 +2715,18 @@ class MM_LLMs(PreTrainedModel):
                                                for v in (frequency_penalty, presence_penalty))
         _penalties_check("set_penalties", frequency_penalty, presence_penalty, logit_bias)
         PENALTIES[0] = dict(frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, logit_bias=logit_bias)
+
+    @staticmethod
+    def set_sampling_params(params=None):
+        """Per-request sampling for `inputs["inference"] = True` (LlamaForCausalLM.generate's sampling_params): off (None)
+        by default.  params: a list with one entry per prompt, each None (greedy) or a dict out of temperature, top_k,
+        top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff and seed.  The form and the values are validated here; what
+        depends on the call (the batch, set_sampling(do_sample=True) next to it, beams, prompt lookup, parallel samples)
+        is validated by generate().  No argument: back to off.  Process-wide switch, like set_penalties."""
+        if params is not None:
+            _sampling_params_check("set_sampling_params", params)
+            params = [None if e is None else dict(e) for e in params]
+        SAMPLING_PARAMS[0] = params
 
     @staticmethod
     def set_parallel_samples(num_samples=1):

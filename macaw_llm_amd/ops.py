@@ -12,6 +12,7 @@ import itertools
 import math
 import numbers
 import os
+import struct
 from typing import Optional
 
 import torch
@@ -800,6 +801,18 @@ def decode_emit_sample_warp(logits, V, pad, eos, tok, done, out, state, temperat
                                             float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff),
                                             int(seed) & 0xFFFFFFFFFFFFFFFF, dt(logits), _st()),
              "mk_decode_emit_sample_warp")
+
+
+def decode_emit_sample_table(logits, V, pad, eos, tok, done, out, state, table):
+    """decode_emit with the selection of sample b read from record b of `table`, an ops.SampleTable (see
+    mk_decode_emit_sample_table): greedy and sampled rows, temperatures, filters and seeds mixed in one launch -- the same
+    ids as sample_rows_table(step=state[1]) on the same logits"""
+    lib = _L.load()
+    B = logits.shape[0]
+    _sample_table_check("decode_emit_sample_table", logits, table)
+    _L.check(lib.mk_decode_emit_sample_table(_p(logits), _rowmajor(logits), V, B, pad, eos, _p(tok), _p(done), _p(out),
+                                             out.stride(0), _p(state), _p(table.records), dt(logits), _st()),
+             "mk_decode_emit_sample_table")
 
 
 def logits_process(logits, V, out, n_dev=None, n_add=0, prompt=None, prompt_len=None, repetition_penalty=1.0,
@@ -1709,6 +1722,63 @@ def sample_keep_rows(x, cols=None, temperature=1.0, top_k=0, top_p=1.0, min_p=0.
                                      float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff), _p(keep),
                                      cols, dt(x), _st()), "mk_sample_keep_rows")
     return keep.bool()
+
+
+class SampleTable:
+    """the per-row sampling records of a batch on the device (include/macaw_hip.h, "Per-row sampling table"), built once
+    per call from validated host values.  rows: one entry per row of logits, None for a greedy row or a dict with the
+    keys temperature (1.0), top_k (0 = off), top_p (1.0), min_p (0.0), typical_p (1.0), epsilon_cutoff (0.0), eta_cutoff
+    (0.0), seed (0) and stream (0), every one optional.  A value outside the scalar entries' domain is refused here: the
+    kernel would decode such a row greedily.  records: uint8 [rows, 48] on `device`; sampled: bool per row on the host"""
+    RECORD = struct.Struct("<fifffffIQii")      # 48 bytes: the header's layout
+    KEYS = ("temperature", "top_k", "top_p", "min_p", "typical_p", "epsilon_cutoff", "eta_cutoff", "seed", "stream")
+
+    def __init__(self, rows, device):
+        rows = list(rows)
+        if not rows:
+            raise MacawHipError("SampleTable: no rows")
+        buf, self.sampled = bytearray(), []
+        for b, r in enumerate(rows):
+            if r is not None and (not isinstance(r, dict) or set(r) - set(self.KEYS)):
+                raise MacawHipError(f"SampleTable: row {b} must be None or a dict with keys out of {self.KEYS}, got {r!r}")
+            self.sampled.append(r is not None)
+            r = r or {}
+            t, k, p = r.get("temperature", 1.0), r.get("top_k", 0), r.get("top_p", 1.0)
+            w = (r.get("min_p", 0.0), r.get("typical_p", 1.0), r.get("epsilon_cutoff", 0.0), r.get("eta_cutoff", 0.0))
+            seed, stream = r.get("seed", 0), r.get("stream", 0)
+            ok = (all(isinstance(v, numbers.Real) and not isinstance(v, bool) for v in (t, p, *w))
+                  and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (k, seed, stream))
+                  and math.isfinite(t) and t > 0 and 0 < p <= 1 and 0 <= k < 2 ** 31 and 0 <= w[0] <= 1 and 0 < w[1] <= 1
+                  and 0 <= w[2] < 1 and 0 <= w[3] < 1 and 0 <= stream < 2 ** 32)
+            if not ok:
+                raise MacawHipError(f"SampleTable: row {b}: {r!r} lies outside the domain of sample_rows / sample_rows_warp")
+            buf += self.RECORD.pack(float(t), int(k), float(p), *map(float, w), int(stream),
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(self.sampled[-1]), 0)
+        self.rows = len(rows)
+        self.records = torch.frombuffer(buf, dtype=torch.uint8).view(self.rows, self.RECORD.size).to(device)
+
+
+def _sample_table_check(op, x, table):
+    if not isinstance(table, SampleTable):
+        raise MacawHipError(f"{op}: table must be an ops.SampleTable, got {type(table).__name__}")
+    if x.dim() != 2 or table.rows != x.shape[0]:
+        raise MacawHipError(f"{op}: a SampleTable of {table.rows} rows for logits {tuple(x.shape)}")
+    if table.records.device != x.device:
+        raise MacawHipError(f"{op}: the table lives on {table.records.device}, the logits on {x.device}")
+
+
+def sample_rows_table(x, cols, table: SampleTable, step=0):
+    """one column per row of a 2-D row-major (pitched) tensor -> int64 [rows], every row by its own record of `table` (see
+    mk_sample_rows_table): a greedy row what argmax_rows returns, a sampled row what sample_rows / sample_rows_warp return
+    with the record's values and seed for the same logits at row index record.stream, whatever its place in the batch"""
+    lib = _L.load()
+    rows = x.shape[0]
+    cols = x.shape[1] if cols is None else cols
+    _sample_table_check("sample_rows_table", x, table)
+    out = torch.empty(rows, dtype=torch.int64, device=x.device)
+    _L.check(lib.mk_sample_rows_table(_p(x), _rowmajor(x), rows, cols, _p(table.records), int(step), _p(out), dt(x),
+                                      _st()), "mk_sample_rows_table")
+    return out
 
 
 def adamw_(param, master, m, v, grad, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):

@@ -109,6 +109,12 @@ with torch.no_grad():
 # run ((72 - 8 tokens) / 64), the medians, the differences to greedy and the greedy run-to-run spread (a difference counts only
 # beyond it).  Then the time of one ops.logits_penalize launch inside a hipGraph at n = 0 and at n = 2048 generated ids (what
 # the counting costs at the long end), with and without the 300-entry bias, against ops.decode_emit and ops.logits_process
+#        bench_generate.py --params-ab [--reps R] [B ...]: per-request sampling (default B = 1, 8, 32).  Three sampled arms
+# alternated in this process on this model: "scalar" = do_sample=True, top_k=50, top_p=0.9 (seed 1); "table" = sampling_params
+# with that dict on every row (ops.decode_emit_sample_table in place of ops.decode_emit_sample: the same work plus one small
+# uniform load per workgroup); "mixed" = the same list with every second row greedy.  ms per token of every run ((72 - 8 tokens)
+# / 64), the medians, each table arm's difference to the scalar arm and the scalar arm's run-to-run spread, which is the yardstick
+PARAMS = "--params-ab" in sys.argv
 PENALTIES = "--penalties-ab" in sys.argv
 SCORE = "--score-ab" in sys.argv
 GRAMMAR = "--grammar-ab" in sys.argv
@@ -131,7 +137,43 @@ _VAL = ("--reps", "--prompt-tokens", "--short-tokens")
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else (5 if "--mxfp4-ab" in sys.argv else 3)
 PROMPT = int(sys.argv[sys.argv.index("--prompt-tokens") + 1]) if "--prompt-tokens" in sys.argv else (1900 if RAGGED or SESSION else 128)
 SHORT = int(sys.argv[sys.argv.index("--short-tokens") + 1]) if "--short-tokens" in sys.argv else 150
-_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", "--warpers-ab", "--penalties-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+_args = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--fp8-ab", "--mxfp4-ab", "--kv8-ab", "--sample-ab", "--ragged-ab", "--beam-ab", "--processors-ab", "--lookup-ab", "--logprobs-ab", "--cfg-ab", "--stop-ab", "--nsample-ab", "--session-ab", "--adapters-ab", "--grammar-ab", "--score-ab", "--warpers-ab", "--penalties-ab", "--params-ab", *_VAL) and sys.argv[i - 1] not in _VAL]
+if PARAMS:
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    D = dict(top_k=50, top_p=0.9, seed=1)
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+
+    for B in [int(a) for a in _args] or [1, 8, 32]:
+        inp = synthetic_inputs(cfg, B, 128, modalities=("images", "audios"), seed=2, device=dev)
+        ARMS = {"scalar": dict(do_sample=True, **D), "table": dict(sampling_params=[D] * B),
+                "mixed": dict(sampling_params=[None if b % 2 else D for b in range(B)])}
+        ms = {a: [] for a in ARMS}
+        with torch.no_grad():
+            emb = model.prepare_inputs_for_generation(inp)[0]
+            gen = lambda arm, new: model.llm.generate(inputs_embeds=emb, max_new_tokens=new, eos_token_id=-1, pad_token_id=0, **ARMS[arm])  # noqa: E731
+            for arm in ARMS:
+                gen(arm, 8)                         # warm-up of every arm
+            for rep in range(REPS):
+                for arm in ARMS:
+                    t = {}
+                    for new in (8, 72):
+                        ids, t[new] = timed(lambda: gen(arm, new))
+                        assert ids.shape[1] == new
+                    ms[arm].append((t[72] - t[8]) / 64 * 1e3)
+                    print(f"B={B:2d} rep {rep} {arm:6s}: decode {ms[arm][-1]:6.3f} ms/token over 64 tokens", flush=True)
+        spread = max(ms["scalar"]) - min(ms["scalar"])
+        for arm in ("table", "mixed"):
+            d = med(ms[arm]) - med(ms["scalar"])
+            print(f"B={B:2d}: scalar {med(ms['scalar']):6.3f} ms/token, {arm} {med(ms[arm]):6.3f} ms/token (spread "
+                  f"{(max(ms[arm]) - min(ms[arm])) * 1e3:6.1f} us), {arm} - scalar = {d * 1e3:+7.1f} us per token "
+                  f"({d / med(ms['scalar']) * 100:+5.2f} %), scalar run-to-run spread {spread * 1e3:6.1f} us: "
+                  f"{'inside' if abs(d) <= spread else 'OUTSIDE'} the spread", flush=True)
+    sys.exit(0)
 if PENALTIES:
     from macaw_llm_amd import ops
     V = model.llm.lm_head.weight.shape[0]
