@@ -597,6 +597,180 @@ def _decode_steps(step, done, n_steps, graph):
     return ran
 
 
+def _step_state(S0, dev):
+    """the device state of a decode loop: int32 [position fed, output column, 0, 0]"""
+    return torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)
+
+
+class _Sampler:
+    """How generate() picks a token from a row of logits, decided once behind the checks.  how: None (the argmax), the
+    scalar tuple of do_sample=True -- (temperature, top_k, top_p, seed), followed by (min_p, typical_p, epsilon_cutoff,
+    eta_cutoff) when one of those four is on -- or the ops.SampleTable of sampling_params.  kind: 0 the argmax, 1 the
+    4-tuple, 2 the 8-tuple, 3 the table; args: what the kind's launch takes behind the common arguments"""
+
+    def __init__(self, how):
+        table = isinstance(how, ops.SampleTable)
+        self.args = () if how is None else (how,) if table else tuple(how)
+        self.kind = 0 if how is None else 3 if table else 1 if len(how) == 4 else 2
+
+    def pick(self, lg, V, t):         # an eager loop: the ids [rows] of new token t
+        if not self.kind:
+            return ops.argmax_rows(lg, V)
+        return (ops.sample_rows, ops.sample_rows_warp, ops.sample_rows_table)[self.kind - 1](lg, V, *self.args, step=t)
+
+    def emit(self, lg, V, pad, eos, tok, done, out, state):       # the captured step: pick and bookkeeping in one launch
+        fn = (ops.decode_emit, ops.decode_emit_sample, ops.decode_emit_sample_warp, ops.decode_emit_sample_table)[self.kind]
+        fn(lg, V, pad, eos, tok, done, out, state, *self.args)
+
+
+class _Selection:
+    """What stands between the hidden rows of a step and its tokens in generate()'s greedy and sampled loops, once:
+
+        lm_head (guidance: ops.cfg_combine of the two rows of a sample)
+        -> rewrite: ops.logits_process, ops.logits_penalize, ops.seq_ban, ops.grammar_mask, in place
+        -> the pick (_Sampler)
+        -> flags: ops.grammar_advance (stateful: once per step), then match (ops.stop_match, stateless)
+        -> the log-probabilities of the rewritten logits
+
+    The object owns the device tables (bias, banned and stop sequences, grammar, sampling records), the per-row state
+    (ids [rows, n_max]: the generated ids, pad behind a row's end -- the captured loop's output matrix, and in an eager
+    loop allocated and written only where a rewrite or a flag reads it; done; the grammar's state and ends) and the prompt
+    history of the processors.  rows counts what the picks see: the samples, each once under guidance (the lm_head then
+    takes 2 * rows hidden rows), per_prompt of them for every entry of the per-prompt arguments pen / gram / params.
+
+    The two steps differ in ONE place, on purpose.  captured_step runs flags in FRONT of ops.decode_emit_logprobs: that
+    launch latches the done flag for the next step, and scores this step's token whatever the flag says, so the token
+    that completes a stop sequence keeps its value.  eager_step looks at the flags first (a row finished BEFORE this
+    step scores 0.0 / pad / 0.0), then ORs in eos, then runs flags: the same values, with the host holding the latch."""
+
+    def __init__(self, head, emb_w, rows, V, n_max, eos, pad, dev, per_prompt=1, sample=None, params=None, n_top=None,
+                 proc=None, hist=None, hist_len=None, pen=None, bad=None, stop=None, gram=None, cfg=None):
+        self.head, self.emb_w, self.B, self.V, self.n_max, self.eos, self.pad, self.dev = head, emb_w, rows, V, n_max, eos, pad, dev
+        self.n_top, self.proc, self.hist, self.hist_len, self.cfg = n_top, proc, hist, hist_len, cfg
+
+        def each(v, dtype):           # one value per prompt -> one per row, on the device
+            return torch.tensor(v, dtype=dtype).repeat_interleave(per_prompt).to(dev) if v is not None else None
+        self.g_tab = self.g_state = self.g_end = None
+        if gram is not None:
+            from .grammar import combine
+            self.g_tab, start = combine(gram, dev, V)
+            self.g_state = each(start, torch.int32)
+            self.g_end = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+        self.pen = None               # frequency f32 [rows], presence f32 [rows], ops.BiasTable
+        if pen is not None:
+            f, p, bias = pen
+            self.pen = (each(f, torch.float32), each(p, torch.float32),
+                        ops.BiasTable([r for r in bias for _ in range(per_prompt)], rows, V, dev) if bias is not None else None)
+        # row b * n + j is prompt b's record with stream = j
+        self.sampler = _Sampler(ops.SampleTable(_sampling_params_rows(params, per_prompt), dev) if params is not None else sample)
+        self.bad_t = ops.SeqTable(bad, dev) if bad is not None else None
+        self.stop_t = ops.SeqTable(stop, dev) if stop is not None else None
+        self.reads_ids = any(v is not None for v in (proc, pen, self.bad_t, self.stop_t, self.g_tab))
+        self.ids = None
+        self.done = torch.zeros(rows, dtype=torch.bool, device=dev)
+        self.out, self.lps = [], []   # an eager loop's ids and log-probabilities per token
+
+    def _new_ids(self):
+        return torch.full((self.B, self.n_max), self.pad, dtype=torch.long, device=self.dev)
+
+    def logits(self, h_last):         # [rows, D] -> [rows, V]; guidance: [2 rows, D] -> a view of the lm_head's rows [0, rows)
+        lg = self.head(h_last)
+        return lg if self.cfg is None else ops.cfg_combine(lg, self.V, self.B, self.cfg)
+
+    def feed(self, tok):              # the next step's token rows; guidance: both rows of a sample, two gathers into one buffer
+        if self.cfg is None:
+            return ops.embedding_fwd(self.emb_w, tok)
+        x = torch.empty((2 * self.B, self.emb_w.shape[1]), dtype=self.emb_w.dtype, device=self.dev)
+        ops.embedding_fwd(self.emb_w, tok, out=x[:self.B])
+        ops.embedding_fwd(self.emb_w, tok, out=x[self.B:])
+        return x
+
+    def rewrite(self, lg, done, n_dev=None, n_add=0):     # in front of a pick, in place; generated: ids[:, :n_dev[0] + n_add]
+        if self.proc is not None:
+            ops.logits_process(lg, self.V, self.ids, n_dev, n_add, self.hist, self.hist_len, *self.proc, eos=self.eos)
+        if self.pen is not None:      # behind the processors, on the generated ids alone
+            ops.logits_penalize(lg, self.V, self.ids, n_dev, n_add, *self.pen)
+        if self.bad_t is not None:    # on the processors' history
+            ops.seq_ban(lg, self.V, self.ids, self.bad_t, n_dev, n_add, self.hist, self.hist_len)
+        if self.g_tab is not None:    # behind all of them: the pick sees allowed columns alone
+            ops.grammar_mask(lg, self.V, self.g_tab, self.g_state, done, self.eos)
+
+    def match(self, done, n_dev=None, n_add=0):           # the stateless part of flags: run again per column for the width
+        if self.stop_t is not None:
+            ops.stop_match(self.ids, self.stop_t, done, n_dev, n_add)
+
+    def flags(self, done, n_dev=None, n_add=0):           # behind a pick, as eos: the advance, ONCE per step, then the match
+        if self.g_tab is not None:
+            ops.grammar_advance(self.ids, self.g_tab, self.g_state, done, self.g_end, n_dev, n_add)
+        self.match(done, n_dev, n_add)
+
+    def eager_step(self, h_last, t):  # -> ids [rows] of new token t, pad where a row had finished; the flags and books behind it
+        if t == 0 and self.reads_ids:
+            self.ids = self._new_ids()
+        done, lg = self.done, self.logits(h_last)
+        self.rewrite(lg, done, n_add=t)
+        ids = self.sampler.pick(lg, self.V, t)
+        pads = torch.full_like(ids, self.pad)
+        nxt = torch.where(done, pads, ids)
+        self.out.append(nxt)
+        if self.ids is not None:
+            self.ids[:, t] = nxt
+        if self.n_top is not None:    # 0.0 / pad / 0.0 where finished before
+            lp, ti, tl = ops.token_logprobs(lg, self.V, ids, self.n_top)
+            self.lps.append((torch.where(done, torch.zeros_like(lp), lp),
+                             torch.where(done[:, None], pads[:, None], ti) if self.n_top else None,
+                             torch.where(done[:, None], torch.zeros_like(tl), tl) if self.n_top else None))
+        self.done = done | (nxt == self.eos)
+        self.flags(self.done, n_add=t + 1)
+        return nxt
+
+    def finished(self):
+        return bool(self.done.all())
+
+    def eager_result(self):
+        ids = torch.stack(self.out, dim=1)
+        if self.n_top is None:
+            return ids
+        lp, top_ids, top_lp = (torch.stack(col, dim=1) if self.n_top or i == 0 else None for i, col in enumerate(zip(*self.lps)))
+        return GenerateLogprobs(ids, lp, top_ids, top_lp)
+
+    def start_captured(self, S0):     # the captured loop's books: step state, last ids, the log-probabilities' device books
+        self.state, self.ids = _step_state(S0, self.dev), self._new_ids()
+        self.tok = torch.zeros(self.B, dtype=torch.long, device=self.dev)
+        self.ls = ops.LogprobState(self.B, self.n_max, self.n_top, self.pad, self.dev) if self.n_top is not None else None
+
+    def captured_step(self, h_last):  # every launch reads its column from state[1] on the device: captured once, replayed
+        lg, n_dev = self.logits(h_last), self.state[1:2]
+        self.rewrite(lg, self.done, n_dev)
+        self.sampler.emit(lg, self.V, self.pad, self.eos, self.tok, self.done, self.ids, self.state)
+        self.flags(self.done, n_dev)
+        if self.ls is not None:       # neither emit writes the logits: the values in front of the selection
+            ops.decode_emit_logprobs(lg, self.V, self.tok, self.done, self.state, self.ls)
+
+    def captured_result(self, n):
+        """n columns ran (up to 7 past the end): trimmed to the width the eager loops return, which stop right after
+        the token at which every row has finished -- by eos, a stop sequence or the grammar"""
+        res = self.ids[:, :n]
+        fin = (res == self.eos).cumsum(1) > 0
+        if (self.stop_t is not None or self.g_tab is not None) and bool(self.done.all()):
+            if self.stop_t is not None:       # every column's tail, once more
+                hit = torch.zeros((n, self.B), dtype=torch.bool, device=self.dev)
+                for c in range(n):
+                    self.match(hit[c], n_add=c + 1)
+                fin |= hit.t().cumsum(1) > 0
+            if self.g_tab is not None:        # the ends were written when they happened: the advance is not run again
+                cols = torch.arange(n, dtype=torch.int32, device=self.dev)
+                fin |= (self.g_end >= 0)[:, None] & (cols[None, :] >= self.g_end[:, None] - 1)
+        fin = fin.all(0)
+        if bool(fin.any()):
+            res = res[:, : int(torch.nonzero(fin)[0]) + 1]
+        w, ls = res.shape[1], self.ls
+        if ls is None:
+            return res.clone()
+        return GenerateLogprobs(res.clone(), ls.lp[:, :w].clone(), ls.top_ids[:, :w].clone() if self.n_top else None,
+                                ls.top_lp[:, :w].clone() if self.n_top else None)
+
+
 def _append_column(emb, emb_w, ids, src=None):
     """use_cache=False: the prefixes emb [R, S, D] grown by the embedding of the new ids [R'] -> [R', S + 1, D].  Row r
     continues row src[r] of emb (a beam continues its parent); None: row r, R' = R"""
@@ -1011,81 +1185,26 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None,
                                       hidden_states=None, attentions=None)
 
-    # The three decode loops on device state.  Each is its state, its emit and its step closure: token 0 comes from the
-    # prefill's rows, then _decode_steps runs the step max_new_tokens - 1 times at the most -- with graph captured once
-    # after one eager step and replayed, the host looking at the done flags every 8 steps; otherwise kernel by kernel, the
-    # host looking before every step.
+    # The three decode loops on device state.  Each is its state, its emit and its step closure (the greedy / sampled
+    # loop's state and emit are its _Selection's): token 0 comes from the prefill's rows, then _decode_steps runs the step
+    # max_new_tokens - 1 times at the most -- with graph captured once after one eager step and replayed, the host looking
+    # at the done flags every 8 steps; otherwise kernel by kernel, the host looking before every step.
     @torch.no_grad()
-    def _generate_graph(self, run, logits, last, emb_w, B, S0, max_new_tokens, eos, pad, dev, sample=None, process=None,
-                        n_top=None, feed=None, stopped=None, rematch=None, ends=None):
-        """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device
-        memory -- the position (int32 counter read by the fused RoPE + cache append + attention
-        kernel), the last token ids, the per-sample finished flags and the output matrix (all advanced
-        by ops.decode_emit) -- so the launches of a step (5 per layer + 3) are captured once, after
-        one eager step that also serves as the warm-up, and replayed; the host only looks at the
-        finished flags every few tokens.  sample = (temperature, top_k, top_p, seed), followed by (min_p, typical_p,
-        epsilon_cutoff, eta_cutoff) when one of those four is on: ops.decode_emit_sample (ops.decode_emit_sample_warp) draws the
-        token instead, its random number a hash of (seed, output column, sample) computed on the device; an
-        ops.SampleTable (sampling_params): ops.decode_emit_sample_table, every sample by its own record.  process(logits,
-        out_buf, n_dev): the logits processors in front of the emit, their history length read from state[1].  n_top (None:
-        off): ops.decode_emit_logprobs behind the emit, on the logits the emit selected from, writes the token's
-        log-probability and the n_top most likely columns into device books (ops.LogprobState); the result is then
-        GenerateLogprobs, trimmed to the ids' columns.  feed(tok) (None: the embedding of tok): the token rows a step runs
-        on -- with guidance_scale both rows of every sample, B counting the samples: `logits` then takes 2B hidden rows
-        and returns the B guided rows, and tok, done, out_buf, state and the books stay per sample.  stopped(out_buf,
-        done, n_dev) (None: off): what sets done flags directly behind the emit as eos does -- the grammar's advance, which
-        is stateful and runs once per step, then the stop-sequence match.  rematch (None: none): the stateless part of it,
-        the match, which the loop evaluates once more over every returned column for the width; ends (None: no grammar):
-        int32 [B], the count at which the grammar finished a row (-1: it did not), which gives the width its part."""
-        state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
-        t_dev = state[:1]
-        tok = torch.zeros(B, dtype=torch.long, device=dev)
-        done = torch.zeros(B, dtype=torch.bool, device=dev)
-        out_buf = torch.full((B, max_new_tokens), pad, dtype=torch.long, device=dev)
-        V = self.lm_head.weight.shape[0]
-        ls = ops.LogprobState(B, max_new_tokens, n_top, pad, dev) if n_top is not None else None
-
-        def emit(h_last):                # argmax, pad / eos handling, output column, position += 1
-            lg = logits(h_last)
-            if process is not None:
-                process(lg, out_buf, state[1:2], done=done)
-            if isinstance(sample, ops.SampleTable):      # sampling_params: sample b by record b of the device table
-                ops.decode_emit_sample_table(lg, V, pad, eos, tok, done, out_buf, state, sample)
-            elif sample is not None:
-                emit = ops.decode_emit_sample if len(sample) == 4 else ops.decode_emit_sample_warp
-                emit(lg, V, pad, eos, tok, done, out_buf, state, *sample)
-            else:
-                ops.decode_emit(lg, V, pad, eos, tok, done, out_buf, state)
-            if stopped is not None:      # in front of the log-probabilities' latch: the stop token keeps its value
-                stopped(out_buf, done, state[1:2])
-            if ls is not None:           # neither emit writes the logits: the values in front of the selection
-                ops.decode_emit_logprobs(lg, V, tok, done, state, ls)
+    def _generate_graph(self, run, chain, last, S0, max_new_tokens):
+        """Decode loop with ONE hipGraph launch per token.  Everything a step needs lives in device memory -- the
+        position (the int32 counter the fused RoPE + cache append + attention kernel reads), the last token ids, the
+        finished flags and the output matrix, all advanced by the emit of chain (a _Selection), which also holds them --
+        so the launches of a step (5 per layer + 3, and what the chain adds) are captured once, after one eager step
+        that also serves as the warm-up, and replayed; the host only looks at the finished flags every few tokens."""
+        chain.start_captured(S0)
+        t_dev = chain.state[:1]
 
         def step():
-            emit(run(ops.embedding_fwd(emb_w, tok) if feed is None else feed(tok), 1, 0, pos=t_dev, t_dev=t_dev))
+            chain.captured_step(run(chain.feed(chain.tok), 1, 0, pos=t_dev, t_dev=t_dev))
 
-        emit(last)                       # token 0 (from the prefill) ...
-        state[0] = S0                    # ... is the one fed at position S0
-        res = out_buf[:, :1 + _decode_steps(step, done, max_new_tokens - 1, True)]
-        # the eager loop stops right after the token at which every sample has finished
-        fin = (res == eos).cumsum(1) > 0
-        if stopped is not None and bool(done.all()):     # ... by eos or by a stop sequence: every column's tail, once more
-            if rematch is not None:
-                hit = torch.zeros((res.shape[1], B), dtype=torch.bool, device=dev)
-                for c in range(res.shape[1]):
-                    rematch(out_buf, hit[c], n_add=c + 1)
-                fin |= hit.t().cumsum(1) > 0
-            if ends is not None:     # the grammar's ends were written when they happened: the advance is not run again
-                cols = torch.arange(res.shape[1], dtype=torch.int32, device=dev)
-                fin |= (ends >= 0)[:, None] & (cols[None, :] >= ends[:, None] - 1)
-        fin = fin.all(0)
-        if bool(fin.any()):
-            res = res[:, : int(torch.nonzero(fin)[0]) + 1]
-        if ls is None:
-            return res.clone()
-        w = res.shape[1]
-        return GenerateLogprobs(res.clone(), ls.lp[:, :w].clone(), ls.top_ids[:, :w].clone() if n_top else None,
-                                ls.top_lp[:, :w].clone() if n_top else None)
+        chain.captured_step(last)        # token 0 (from the prefill) ...
+        chain.state[0] = S0              # ... is the one fed at position S0
+        return chain.captured_result(1 + _decode_steps(step, chain.done, max_new_tokens - 1, True))
 
     @torch.no_grad()
     def _generate_beam(self, run, logits, last, emb_w, B, K, S0, max_new_tokens, eos, pad, dev, length_penalty,
@@ -1094,7 +1213,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         the indirection table): token 0 from the prefill's B rows (K_in = 1), then one step per token -- embedding of the
         K tokens per sample, the layers with engine.Beam, the lm_head, the emit.  Returns the device books and the step
         state for generate's beam_out."""
-        state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)   # position fed, output column, 0
+        state = _step_state(S0, dev)
         t_dev = state[:1]
         bs = ops.BeamState(B, K, max_new_tokens, pad, dev)
         beam = eng.Beam(bs.ind, K, S0)
@@ -1522,6 +1641,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         the selection launch itself.  None (default): not one launch, allocation, host read or message differs."""
         # ---- refusals (a): what the arguments alone decide, before the model is touched
         K = beam_check("generate", num_beams)
+        rows_of = inputs_embeds if inputs_embeds is not None else input_ids      # its shape[0]: the prompts
         proc = _processors_check("generate", repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         if proc is not None and K > 1:
             on = [f"{k}={v!r}" for k, v, off in (("repetition_penalty", repetition_penalty, 1.0),
@@ -1535,7 +1655,6 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             raise ValueError(f"generate: kv_cache must be None or 'fp8', got {kv_cache!r}")
         G = _lookup_check("generate", prompt_lookup_num_tokens, max_matching_ngram_size)
         if G:                     # what prompt lookup does not compose with
-            rows_of = inputs_embeds if inputs_embeds is not None else input_ids
             why = None
             if K > 1:
                 why = f"num_beams={K} > 1 (lookup along beams is not built)"
@@ -1561,7 +1680,6 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         pen = None                # frequency_penalty / presence_penalty / logit_bias (None: off, nothing below runs)
         if not (type(frequency_penalty) in (int, float) and frequency_penalty == 0 and type(presence_penalty) in (int, float)
                 and presence_penalty == 0 and logit_bias is None):                           # not the defaults
-            rows_of = inputs_embeds if inputs_embeds is not None else input_ids
             pen = _penalties_check("generate", frequency_penalty, presence_penalty, logit_bias, rows_of.shape[0])
         if pen is not None:
             what = "generate(frequency_penalty=, presence_penalty=, logit_bias=)"
@@ -1604,7 +1722,6 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if do_sample:
                 raise ValueError(f"{what} with do_sample=True: two ways to say how tokens are selected; pass the scalar "
                                  "arguments or the list, not both")
-            rows_of = inputs_embeds if inputs_embeds is not None else input_ids
             sp = _sampling_params_check("generate", sampling_params, rows_of.shape[0])
             if K > 1:
                 raise ValueError(f"{what} with num_beams={K}: per-request sampling along beams is not built; use "
@@ -1770,6 +1887,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 own = own_mask is not None and not bool((own_mask != 0).all())
                 hist_rg = eng.Ragged(ragged.kmask[:Bs, :Sc], ragged.slot[:Bs, :Sc], ragged.t_off[:Bs]) if own else None
             hist, hist_len = _prompt_history(input_ids, Bs, dev, "the processors' prompt history", hist_rg)
+        no_attn = _attn_refusal(dtype, hd, Tmax)      # why the per-sample-position step kernels do not take this call
         if K > 1:
             beam_check("generate", K, num_return_sequences, V, do_sample, kv_cache, ragged is not None, length_penalty)
             why = _attn_refusal(dtype, hd, S0 + max_new_tokens) if use_cache else None
@@ -1777,7 +1895,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 raise ValueError(f"generate(num_beams={K}) with use_cache=True: {why}; the beam step attention takes bf16 / "
                                  "fp16 inside ops.decode_attn_ok: pass use_cache=False")
         if N > 1:                 # (use_cache=True: the other case became a batch of B * N rows above)
-            why = _attn_refusal(dtype, hd, Tmax)
+            why = no_attn
             if why is None and not ops.shared_attn_ok(dtype, hd, N):
                 why = f"ops.shared_attn_ok is false for head size {hd} and {N} rows per prompt"
             if why is not None:
@@ -1795,12 +1913,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                                  "for it")
             if input_ids is not None:
                 hist, hist_len = _prompt_history(input_ids, B, dev, "the lookup history")
-        if sess:
-            why = _attn_refusal(dtype, hd, Tmax)
-            if why is not None:
-                raise ValueError(f"generate({'session=' if session is not None else 'return_session=True'}): {why}; a "
-                                 "continued call needs the per-sample-position decode kernels, which take bf16 / fp16 inside "
-                                 "ops.decode_attn_ok")
+        if sess and no_attn is not None:
+            raise ValueError(f"generate({'session=' if session is not None else 'return_session=True'}): {no_attn}; a "
+                             "continued call needs the per-sample-position decode kernels, which take bf16 / fp16 inside "
+                             "ops.decode_attn_ok")
         ad_idx = None             # adapter_names: per sample its adapter's index in the bank, -1 for "__base__"
         if bank is not None:
             what = "generate(adapter_names=)"
@@ -1808,7 +1924,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             if len(names) != B:
                 raise ValueError(f"{what}: {len(names)} names for {B} samples (one per sample, '__base__' for none)")
             ad_idx = bank.indices(names)          # (ValueError for an unknown name)
-            why = _attn_refusal(dtype, hd, Tmax)
+            why = no_attn
             if dtype not in _16BIT:
                 why = f"fp32 parameters ({dtype}): the adapter kernels of a decode step take bf16 / fp16"
             elif any(w is None for lyr in layers for w in lyr.fused_weights()):
@@ -1818,14 +1934,12 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
                 why = f"{B} rows: an adapted decode step takes at most 32"
             if why is not None:
                 raise ValueError(f"{what}: {why}")
-        if ragged is not None and use_cache:
-            why = _attn_refusal(dtype, hd, Tmax)
-            if why is not None:
-                call = ("generate(attention_mask=) with a padded mask" if cfg is None else
-                        f"generate(guidance_scale={guidance_scale!r}) with prompts of two lengths or a padded mask")
-                raise ValueError(f"{call} and use_cache=True: {why}; the "
-                                 "per-sample-position decode kernels take bf16 / fp16 inside ops.decode_attn_ok and "
-                                 "there is no masked attention over a cache: pass use_cache=False")
+        if ragged is not None and use_cache and no_attn is not None:
+            call = ("generate(attention_mask=) with a padded mask" if cfg is None else
+                    f"generate(guidance_scale={guidance_scale!r}) with prompts of two lengths or a padded mask")
+            raise ValueError(f"{call} and use_cache=True: {no_attn}; the per-sample-position decode kernels take bf16 / "
+                             "fp16 inside ops.decode_attn_ok and there is no masked attention over a cache: pass "
+                             "use_cache=False")
         if gram is not None:
             gram = _grammar_rows(gram, n_prompts, V)
             if all(g is None for g in gram):          # a list of unconstrained rows: the plain call
@@ -1835,49 +1949,6 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             Bs = B * N
             if hist is not None:  # row r's history starts with its prompt's ids
                 hist, hist_len = hist.repeat_interleave(N, 0).contiguous(), hist_len.repeat_interleave(N).contiguous()
-        g_tab = g_state = g_end = None    # grammar=: the device table, and per row its state and the count it ended at
-        if gram is not None:
-            from .grammar import combine
-            g_tab, g_start = combine(gram, dev, V)
-            g_state = torch.tensor(g_start, dtype=torch.int32).repeat_interleave(rows_per).to(dev)
-            g_end = torch.full((Bs,), -1, dtype=torch.int32, device=dev)
-        pen_f = pen_p = pen_b = None      # the penalties per row, on the device: f32 [Bs], f32 [Bs], ops.BiasTable
-        if pen is not None:           # row r carries its prompt's values, as its history above
-            f, p, rows = pen
-            pen_f = torch.tensor(f, dtype=torch.float32).repeat_interleave(rows_per).to(dev) if f is not None else None
-            pen_p = torch.tensor(p, dtype=torch.float32).repeat_interleave(rows_per).to(dev) if p is not None else None
-            if rows is not None:
-                pen_b = ops.BiasTable([r for r in rows for _ in range(rows_per)], Bs, V, dev)
-        if sp is not None:            # the per-row sampling table: row b * n + j is prompt b's record with stream = j
-            sample = ops.SampleTable(_sampling_params_rows(sp, rows_per), dev)
-        process = gen_buf = None      # the logits processors: process(logits, generated ids [B, n_max], n_dev, n_add, done)
-        if proc is not None or pen is not None or bad is not None or g_tab is not None:
-            bad_t = ops.SeqTable(bad, dev) if bad is not None else None
-
-            def process(lg, gen, n_dev=None, n_add=0, done=None):
-                if proc is not None:
-                    ops.logits_process(lg, V, gen, n_dev, n_add, hist, hist_len, *proc, eos=eos_token_id)
-                if pen is not None:    # the penalties and the bias: behind the processors, on the generated ids alone
-                    ops.logits_penalize(lg, V, gen, n_dev, n_add, pen_f, pen_p, pen_b)
-                if bad_t is not None:  # bad_words_ids: one more launch behind the processors, on the same history
-                    ops.seq_ban(lg, V, gen, bad_t, n_dev, n_add, hist, hist_len)
-                if g_tab is not None:  # grammar: behind both, so that the selection sees allowed columns alone
-                    ops.grammar_mask(lg, V, g_tab, g_state, done, eos_token_id)
-        stopped = None                # stop_sequences: stopped(generated ids [B, n_max], done, n_dev, n_add) behind an emit
-        if stop is not None:
-            stop_t = ops.SeqTable(stop, dev)
-
-            def stopped(gen, done, n_dev=None, n_add=0):
-                ops.stop_match(gen, stop_t, done, n_dev, n_add)
-        rematch = stopped             # what the graph loop may evaluate once more behind its steps: the stateless match
-        if g_tab is not None:         # grammar: the state moves in front of the match, exactly once per step
-
-            def stopped(gen, done, n_dev=None, n_add=0):
-                ops.grammar_advance(gen, g_tab, g_state, done, g_end, n_dev, n_add)
-                if rematch is not None:
-                    rematch(gen, done, n_dev, n_add)
-        if process is not None or stopped is not None:
-            gen_buf = torch.full((Bs, max_new_tokens), pad, dtype=torch.long, device=dev)  # the eager loops' ids so far
         w8_head = None            # decode_weights="fp8" / "mxfp4": (q, scales) of the lm_head, e4m3 in both modes
 
         def logits(h_last):       # h_last [B, D] -> [B, V] (final norm folded into the lm_head stream)
@@ -1886,53 +1957,10 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             _, y, _ = ops.rmsnorm_fwd(h_last, self.model.norm.weight, eps)
             return ops.linear_fwd(y, self.lm_head.weight)
 
-        feed = None               # guidance: the token rows of a step from the samples' ids (None: their embedding)
-        if cfg is not None:
-            head = logits
-
-            def logits(h_last):   # h_last [2 Bs, D] -> the guided scores [Bs, V], a view of the lm_head's rows [0, Bs)
-                return ops.cfg_combine(head(h_last), V, Bs, cfg)
-
-            def feed(ids):        # the emitted token feeds both rows of its sample: two gathers into one [2 Bs, D] buffer
-                x = torch.empty((B, D), dtype=dtype, device=dev)
-                ops.embedding_fwd(emb_w, ids, out=x[:Bs])
-                ops.embedding_fwd(emb_w, ids, out=x[Bs:])
-                return x
-
-        def select(h_last, t, done):  # h_last [B, D] -> ids [B] of new token t (pad where done), the flags behind it
-            pads = torch.full((Bs,), pad, dtype=torch.long, device=dev)
-            lg = logits(h_last)
-            if process is not None:
-                process(lg, gen_buf, n_add=t, done=done)
-            if sample is None:
-                ids = ops.argmax_rows(lg, V)
-            elif isinstance(sample, ops.SampleTable):     # sampling_params: every row by its own record
-                ids = ops.sample_rows_table(lg, V, sample, step=t)
-            elif len(sample) == 4:
-                ids = ops.sample_rows(lg, V, *sample, step=t)
-            else:                 # one of the four warpers on: the 8-tuple
-                ids = ops.sample_rows_warp(lg, V, *sample, step=t)
-            nxt = torch.where(done, pads, ids)
-            if gen_buf is not None:
-                gen_buf[:, t] = nxt
-            if n_top is not None:     # of the processed logits, in front of the warpers; 0.0 / pad / 0.0 where finished before
-                lp, ti, tl = ops.token_logprobs(lg, V, ids, n_top)
-                lps.append((torch.where(done, torch.zeros_like(lp), lp),
-                            torch.where(done[:, None], pads[:, None], ti) if n_top else None,
-                            torch.where(done[:, None], torch.zeros_like(tl), tl) if n_top else None))
-            done = done | (nxt == eos_token_id)
-            if stopped is not None:   # behind the log-probabilities' look at the flags: the stop token keeps its value
-                stopped(gen_buf, done, n_add=t + 1)
-            return nxt, done
-
-        lps = []                      # return_logprobs in the eager loops: per new token (lp [B], top ids, top values)
-
-        def with_logprobs(ids):       # ids [B, width] -> what generate returns
-            if n_top is None:
-                return ids
-            return GenerateLogprobs(ids, torch.stack([e[0] for e in lps], dim=1),
-                                    torch.stack([e[1] for e in lps], dim=1) if n_top else None,
-                                    torch.stack([e[2] for e in lps], dim=1) if n_top else None)
+        # the greedy and sampled loops' way from a step's hidden rows to its tokens (beams and lookup have emits of their own)
+        chain = None if K > 1 or G else _Selection(
+            logits, emb_w, Bs, V, max_new_tokens, eos_token_id, pad, dev, per_prompt=rows_per, sample=sample, params=sp,
+            n_top=n_top, proc=proc, hist=hist, hist_len=hist_len, pen=pen, bad=bad, stop=stop, gram=gram, cfg=cfg)
 
         def beam_out(bs, state):      # the books after the loop -> what generate returns
             n_cols = int(state[1])
@@ -1942,7 +1970,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             return (ids.to(dev), sc.to(dev)) if return_beam_scores else ids.to(dev)
 
         if not use_cache and K > 1:   # the B * K prefixes recomputed per step, the same ops.beam_emit
-            state = torch.tensor([S0, 0, 0, 0], dtype=torch.int32, device=dev)
+            state = _step_state(S0, dev)
             bs = ops.BeamState(B, K, max_new_tokens, pad, dev)
             emb = inputs_embeds.contiguous()
             own = torch.arange(B, device=dev).repeat_interleave(K)      # the sample of row (b, j) ...
@@ -1959,18 +1987,16 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         if not use_cache:
             emb = inputs_embeds.contiguous()
             mask = ragged.kmask if ragged is not None else None        # grows by a one per new token
-            done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
             for t in range(max_new_tokens):
                 # under a mask token 0 is predicted by each sample's last valid row
-                nxt, done = select(self._hidden_last(emb, mask, rg_last if mask is not None and t == 0 else None), t, done)
-                out.append(nxt)
-                if bool(done.all()):
+                nxt = chain.eager_step(self._hidden_last(emb, mask, rg_last if mask is not None and t == 0 else None), t)
+                if chain.finished():
                     break
                 # (guidance: the token continues both prefixes of its sample)
                 emb = _append_column(emb, emb_w, nxt.contiguous() if cfg is None else torch.cat([nxt, nxt]))
                 if mask is not None:
                     mask = torch.cat([mask, torch.ones((B, 1), dtype=mask.dtype, device=dev)], dim=1)
-            return with_logprobs(torch.stack(out, dim=1))
+            return chain.eager_result()
 
         rot = layers[0].self_attn.rotary_emb
         cos, sin = rot.tables(Tmax, dtype, dev)
@@ -2098,27 +2124,24 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
             return beam_out(*self._generate_beam(run, logits, last, emb_w, B, K, S0, max_new_tokens, eos_token_id, pad, dev,
                                                  length_penalty, early_stopping, graph))
         if graph and ops.decode_attn_ok(dtype, hd, Tmax):
-            res = self._generate_graph(run, logits, last, emb_w, Bs, S0, max_new_tokens, eos_token_id, pad, dev, sample,
-                                       process, n_top, feed, stopped, rematch, g_end)
+            res = self._generate_graph(run, chain, last, S0, max_new_tokens)
             return hand_over(res) if sess else res
         # the host-position loop (fp32, a shape outside ops.decode_attn_ok), and every eager loop of a padded batch or of
         # parallel samples
         # (parallel samples and adapters take the padded batch's route: a device position)
         dyn = ragged is not None or N > 1 or adapt is not None
         t_dev = torch.tensor([S0], dtype=torch.int32, device=dev) if dyn else None
-        done, out = torch.zeros(Bs, dtype=torch.bool, device=dev), []
         for t in range(max_new_tokens):
-            nxt, done = select(last, t, done)
-            out.append(nxt)
-            if t + 1 == max_new_tokens or bool(done.all()):
+            nxt = chain.eager_step(last, t)
+            if t + 1 == max_new_tokens or chain.finished():
                 break
-            x = ops.embedding_fwd(emb_w, nxt.contiguous()) if feed is None else feed(nxt.contiguous())   # [B, D]
+            x = chain.feed(nxt.contiguous())                               # [B, D]
             if dyn:                                                        # the graph path's step launches, one by one
                 last = run(x, 1, 0, pos=t_dev, t_dev=t_dev)
                 t_dev += 1
             else:
                 last = run(x, 1, S0 + t)                                   # decode step
-        res = with_logprobs(torch.stack(out, dim=1))
+        res = chain.eager_result()
         return hand_over(res) if sess else res
 
     @torch.no_grad()
